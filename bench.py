@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Benchmark of the reverse-diffusion sampling path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K PC steps, writes the last step's outputs when --dump-outputs is given
+and prints the JSON line.  Everything else it can measure (the keys marked [--full] below) runs only with --full.
 
 N > 1: one process per GPU.  Under `python -m torch.distributed.run --nproc-per-node N ...` the ranks come from
 the environment; started directly, this script first starts N fresh child processes of itself (before it touches
@@ -20,19 +23,24 @@ HBM when the timed region starts; the per-run text K/V projection is loop-invari
 Chains shard over ranks with no per-step collective (per-GPU batches, SURVEY 8(e) option A); one
 RCCL all_gather of the final samples closes the timed region.
 
+--dump-outputs DIR writes what the last timed step returned, as float32 .npy files (rank 0): x_mean.npy, the denoised
+samples of every chain in rank order (what the sampler hands its caller after the last step), and x.npy, rank 0's
+sampler state.  Inputs are seeded, so the same arguments give the same inputs on every run.  Above 64 MB in all, each
+array is replaced by a fixed seeded sample of its elements (<name>_sample.npy).
+
 The JSON line (rank 0), beyond the contract's keys:
-  dispatches_per_step       device dispatches one PC step enqueues (graph nodes of a captured, unexecuted step)
-  roofline                  the dominant 3x3-convolution instantiation of the benchmarked precision against the dense MFMA peak:
+  dispatches_per_step       [--full] device dispatches one PC step enqueues (graph nodes of a captured, unexecuted step)
+  roofline                  [--full, or --shapes / --layers] the dominant 3x3-convolution instantiation of the benchmarked precision against the dense MFMA peak:
                             every GEMM launch of one PC step timed with HIP events on the launch stream (t2p_profile_*)
   traffic_measured_in_run   false: roofline.traffic is the HBM byte count of the committed rocprofv3 --pmc passes of this
                             command (profiles/), not a figure of this run
-  f32                       N = 1: the SAME workload on the exact-f32 engine (v_mfma_f32_32x32x2_f32, the reference's own
+  f32                       [--full] N = 1: the SAME workload on the exact-f32 engine (v_mfma_f32_32x32x2_f32, the reference's own
                             arithmetic type): --f32-steps (10) steps after a warm-up step, with its own kernel roofline
                             against the 157.3 TFLOP/s f32 matrix peak
-  train_step                N = 1: the fp32 training step (loss + backward + Adam + EMA) on cond_length.yml at full size, 16 samples: an
+  train_step                [--full] N = 1: the fp32 training step (loss + backward + Adam + EMA) on cond_length.yml at full size, 16 samples: an
                             extra, not the headline
-  cpu_baseline              N = 1: the oracle on the host cores, 2 chains x 3 PC steps after one warm-up step, scaled by N
-  cfg3, cfg5                N > 1: BASELINE configs[2] (cond_length.yml, 32 chains per GPU, length condition: the workload the north
+  cpu_baseline              [--full] N = 1: the oracle on the host cores, 2 chains x 3 PC steps after one warm-up step, scaled by N
+  cfg3, cfg5                [--full] N > 1: BASELINE configs[2] (cond_length.yml, 32 chains per GPU, length condition: the workload the north
                             star's 1000 samples/min is about) and configs[4] (cond_length_inpainting.yml, 16 chains per GPU, length +
                             inpainting) measured by the same ranks with the same bracketing
   per_rank_ms_per_step      every rank's OWN device time per PC step (HIP events around its steps, all-gathered after the timed
@@ -83,7 +91,32 @@ def parse():
     ap.add_argument("--f32-steps", type=int, default=10)
     ap.add_argument("--no-train", action="store_true", help="skip the training-step line (rank 0, N = 1)")
     ap.add_argument("--no-cfg3", action="store_true", help="with --gpus N > 1: skip the additional cfg3 / cfg5 (BASELINE configs[2] / configs[4]) measurements")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="after the headline, run every extra measurement too: dispatch count, kernel "
+                    "roofline, exact-f32 engine, training step, CPU baseline (N = 1) or cfg3 / cfg5 (N > 1); the --no-* switches "
+                    "drop single extras")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_BUDGET = 64 << 20          # bytes of all --dump-outputs files together
+
+
+def dump_outputs(path, arrays):
+    """Write each tensor as float32 DIR/<name>.npy.  When they would exceed DUMP_BUDGET together, each is replaced by a fixed
+    seeded sample of its elements, in index order (DIR/<name>_sample.npy; the same elements on every run of the same shape)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() for t in arrays.values()) * 4
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if total > DUMP_BUDGET:
+            keep = max(1, a.numel() * (DUMP_BUDGET - 4096 * len(arrays)) // total)     # (room for the .npy headers)
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(path, name + ".npy"), a.numpy())
 
 
 def cpu_baseline(cfg, sd, ctx_cpu, n_scales, k_steps=3):
@@ -197,6 +230,7 @@ class Job:
             torch.cuda.current_stream().wait_stream(side)
         ev1.record()                                         # this rank's own steps end here (device time, no host wait added)
         gathered = D.gather_samples(xm, dist)                # the single collective of a run (no-op at N = 1)
+        self.gathered = gathered
         D.barrier(dist, dev)
         dt = D.max_over_ranks(time.perf_counter() - t0, dist, dev)
         # every rank's OWN device time per step, gathered after the region: a short scaling curve can then be read as "the code"
@@ -347,11 +381,15 @@ def main():
         "traffic_measured_in_run": False,
         "per_rank_ms_per_step": job.per_rank_ms,
     }
-    if rank == 0 and not args.graph:
+    if rank == 0 and args.dump_outputs:
+        # before any extra: the extras below step the same state on
+        dump_outputs(args.dump_outputs, {"x_mean": job.gathered, "x": job.x})
+    job.gathered = None
+    if rank == 0 and args.full and not args.graph:
         job.stepper.reset(0)
         out["dispatches_per_step"] = job.stepper.count_dispatches(job.x, job.x_mean)     # graph nodes of one captured PC step
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and (args.full or args.shapes or args.layers) and not args.no_roofline:
         r = kernel_roofline(job, job.stepper, lib, MFMA_PEAK_TFLOPS[args.dtype], args.shapes, args.layers)
         tfile = sorted(__import__("glob").glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")))
         r["traffic_from_profile"] = None
@@ -363,7 +401,7 @@ def main():
                 r["traffic"] = t[r["kernel"]]["hbm_bytes_per_launch"]
                 r["traffic_from_profile"] = {"bytes_per_launch": r["traffic"], "file": os.path.relpath(tfile[-1], ROOT)}
         out["roofline"] = r
-    if world > 1 and args.workload == "cfg2" and not args.no_cfg3:
+    if args.full and world > 1 and args.workload == "cfg2" and not args.no_cfg3:
         # BASELINE.json configs[2] (cond_length.yml, 32 chains per GPU, length condition: the workload the north star's
         # ">= 1000 samples/min on 8 GPUs" is about) and configs[4] (cond_length_inpainting.yml, 16 chains per GPU, length + inpainting:
         # the other 8-GPU configuration), measured by the same ranks with the same bracketing; cfg2 stays the headline
@@ -375,7 +413,7 @@ def main():
                          "per_rank_ms_per_step": jobx.per_rank_ms, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                          "finite": finx, "workload": jobx.describe()}
             del jobx
-    if rank == 0 and world == 1 and not args.no_f32 and args.dtype != "f32":
+    if args.full and rank == 0 and world == 1 and not args.no_f32 and args.dtype != "f32":
         # the same workload on the exact-f32 engine (v_mfma_f32_32x32x2_f32: the reference's own arithmetic type), timed over
         # the same kind of region, with its own kernel roofline against the 157.3 TFLOP/s f32 matrix peak
         job.stepper = None
@@ -401,9 +439,9 @@ def main():
         if not args.no_roofline:
             out["f32"]["roofline"] = kernel_roofline(job, st32, lib, MFMA_PEAK_TFLOPS["f32"])
         del st32, m32
-    if rank == 0 and world == 1 and not args.no_train and not args.no_f32:      # (the measurement tools pass --no-f32: no extras)
+    if args.full and rank == 0 and world == 1 and not args.no_train and not args.no_f32:      # (the measurement tools pass --no-f32: no extras)
         out["train_step"] = train_step_line(dev)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(job.cfg, job.sd, job.ctx_cpu, N)
     if dist is not None:
         dist.barrier()

@@ -29,6 +29,24 @@ def rel_l2(a, b):
     return float((a - b).norm() / b.norm().clamp_min(1e-30))
 
 
+# The float32 schedule tables of tables.npz are the reference's arithmetic on the host that wrote them.  exp, log and linspace
+# round differently in the last bits on other hosts (vector width, libm); the product is held to the reference arithmetic bit for bit
+# on the host the test runs on (against the oracle), and to the stored tables within this relative bound (about 8 ulp).
+F32_HOST_RTOL = 1e-6
+
+
+def ve_g_rtol(N, sigma_min=0.01, sigma_max=100.0):
+    """G = sqrt(sigma_k^2 - sigma_{k-1}^2) magnifies a relative error of the sigmas by 1 / (1 - (sigma_{k-1} / sigma_k)^2)."""
+    return F32_HOST_RTOL / (1.0 - (sigma_min / sigma_max) ** (2.0 / (N - 1)))
+
+
+def assert_table_close(got, want, rtol=F32_HOST_RTOL):
+    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
+    assert got.shape == want.shape and np.all(want != 0)
+    err = float(np.max(np.abs(got - want) / np.abs(want)))
+    assert err <= rtol, f"max relative difference {err:.3e} > {rtol:.3e}"
+
+
 def cfg_smallC():
     """Wide enough (64/128 channels, 32x32 maps) for the LDS-DMA GEMM kernel to be selected."""
     return tiny_config(**{"model.nf": 64, "model.ch_mult": [1, 2], "model.num_res_blocks": 1, "data.max_res_num": 32,

@@ -88,16 +88,24 @@ def test_apply_conditions_matches_oracle():
 
 
 def test_sde_tables_match_golden():
-    from helpers import load_golden
+    """The product's tables are the reference's float32 arithmetic: bit for bit against the oracle's restatement on this host,
+    and within float32 rounding of the reference's own tables (helpers.F32_HOST_RTOL)."""
+    import torch
+    from helpers import assert_table_close, load_golden, ve_g_rtol
+    from oracle import t2p_oracle as O
     from text2protein_amd import sde_lib
     g = load_golden("tables")
     for N in (100, 1000, 2000):
         sde = sde_lib.VESDE(0.01, 100.0, N)
-        assert np.array_equal(sde.discrete_sigmas.numpy(), g[f"discrete_sigmas_{N}"])
-        assert np.array_equal(sde.g_table(1e-5).numpy(), g[f"G_{N}"])
-        vp = sde_lib.VPSDE(0.1, 20.0, N)
-        assert np.array_equal(vp.alphas.numpy(), g[f"vp_alphas_{N}"])
-        assert np.array_equal(vp.sqrt_1m_alphas_cumprod.numpy(), g[f"vp_sqrt_1m_acp_{N}"])
+        dsig, ts = O.ve_discrete_sigmas(0.01, 100.0, N), O.timesteps(N, 1e-5)
+        assert torch.equal(sde.discrete_sigmas, dsig)
+        assert torch.equal(sde.g_table(1e-5), torch.cat([O.ve_discretize_G(ts[i:i + 1], dsig, N) for i in range(N)]))
+        assert_table_close(sde.discrete_sigmas, g[f"discrete_sigmas_{N}"])
+        assert_table_close(sde.g_table(1e-5), g[f"G_{N}"], ve_g_rtol(N))
+        vp, ovp = sde_lib.VPSDE(0.1, 20.0, N), O.vp_tables(0.1, 20.0, N)
+        assert torch.equal(vp.alphas, ovp["alphas"]) and torch.equal(vp.sqrt_1m_alphas_cumprod, ovp["sqrt_1m_alphas_cumprod"])
+        assert_table_close(vp.alphas, g[f"vp_alphas_{N}"])
+        assert_table_close(vp.sqrt_1m_alphas_cumprod, g[f"vp_sqrt_1m_acp_{N}"])
 
 
 def test_registries_and_errors():

@@ -7,7 +7,7 @@ import torch
 from oracle import t2p_oracle as O
 from text2protein_amd import synth
 from text2protein_amd.config import tiny_config
-from helpers import load_golden, cfg_tiny, cfg_tinyB, rel_l2
+from helpers import load_golden, cfg_tiny, cfg_tinyB, rel_l2, assert_table_close, ve_g_rtol
 
 TOL = 1e-5   # float32 restatement with the same torch CPU ops as the reference
 
@@ -67,20 +67,22 @@ def test_pc_sampler_matches_reference(kind):
 
 @pytest.mark.parametrize("N", [100, 1000, 2000])
 def test_schedule_tables(N):
+    """The oracle's tables against the reference's (tables.npz, written on another host): integers exactly, float32 tables within
+    float32 rounding (helpers.F32_HOST_RTOL)."""
     g = load_golden("tables")
     dsig = O.ve_discrete_sigmas(0.01, 100.0, N)
-    assert np.array_equal(dsig.numpy(), g[f"discrete_sigmas_{N}"])
+    assert_table_close(dsig, g[f"discrete_sigmas_{N}"])
     ts = O.timesteps(N, 1e-5)
     labels = torch.stack([O.ve_label(ts[i:i + 1].clone(), N)[0] for i in range(N)])
     assert np.array_equal(labels.numpy(), g[f"labels_{N}"])
     assert np.array_equal(labels.numpy(), np.arange(N))              # SURVEY 3.3: label at step i is i
     G = torch.cat([O.ve_discretize_G(ts[i:i + 1], dsig, N) for i in range(N)])
-    assert np.array_equal(G.numpy(), g[f"G_{N}"])
+    assert_table_close(G, g[f"G_{N}"], ve_g_rtol(N))
     cfg = tiny_config(**{"model.num_scales": N})
     assert np.array_equal(O.model_sigmas(cfg).numpy(), g[f"model_sigmas_{N}"])
     vp = O.vp_tables(0.1, 20.0, N)
-    assert np.array_equal(vp["alphas"].numpy(), g[f"vp_alphas_{N}"])
-    assert np.allclose(vp["sqrt_1m_alphas_cumprod"].numpy(), g[f"vp_sqrt_1m_acp_{N}"], rtol=0, atol=0)
+    assert_table_close(vp["alphas"], g[f"vp_alphas_{N}"])
+    assert_table_close(vp["sqrt_1m_alphas_cumprod"], g[f"vp_sqrt_1m_acp_{N}"])
 
 
 def test_timestep_embedding():
@@ -205,11 +207,17 @@ def test_training_step_matches_reference_autograd(name):
     got = {"grads": raw, "post": {n: P[n].detach() for n in names}, "ema": state["ema"], "m": state["m"], "v": state["v"]}
     T = float(g["grad_total_norm"])     # exactly-zero gradients (key bias of an AttnBlockpp) hold rounding noise only: floor the scale
     floor = {"grads": 3e-5 * T, "m": 3e-6 * T, "v": 1e-12 * T * T, "post": 0.0, "ema": 0.0}
+    # Adam's first step moves a parameter by lr * g / (|g| + eps) per element: for those noise-only gradients the step is set by the
+    # host's rounding, so the post-step state and its EMA can match the reference's only to within both steps' norms
+    lr, eps = O.warmup_lr(cfg, case["step0"]), cfg.optim.eps
     for key, tol in (("grads", 1e-4), ("post", 1e-6), ("ema", 1e-6), ("m", 1e-4), ("v", 2e-4)):
         for i, n in enumerate(names):
             scale = max(float(g[key + "_norm"][i]), floor[key], 1e-30)
-            assert abs(float(got[key][n].double().norm()) - float(g[key + "_norm"][i])) <= tol * scale, (key, n)
-            assert abs(projection(n, got[key][n]) - float(g[key + "_proj"][i])) <= tol * scale * 10, (key, n)
+            noise_step = 0.0
+            if key in ("post", "ema") and float(g["grads_norm"][i]) < floor["grads"]:
+                noise_step = lr * (float(raw[n].double().norm()) + float(g["grads_norm"][i])) / eps
+            assert abs(float(got[key][n].double().norm()) - float(g[key + "_norm"][i])) <= tol * scale + noise_step, (key, n)
+            assert abs(projection(n, got[key][n]) - float(g[key + "_proj"][i])) <= tol * scale * 10 + noise_step * got[key][n].numel() ** 0.5, (key, n)
     full = [k[5:] for k in g if k.startswith("grad:")]
     assert len(full) >= 15
     for n in full:

@@ -6,7 +6,7 @@ python bench.py --workload cfg3 --steps 1000 --warmup 5 --no-cpu-baseline --no-f
 # an evaluation is batch-independent latency)
 python bench.py --workload cfg3 --batch 64 --steps 10 --warmup 3 --no-cpu-baseline --no-f32 > gpurun_out/bench_cfg3_b64.json 2>/dev/null
 # two ranks on this one card over gloo: the N > 1 control flow of bench.py with its cfg3 / cfg5 keys and per-rank times (NOT a scaling measurement)
-T2P_FORCE_DEVICE=0 T2P_DIST_BACKEND=gloo timeout -k 10 600 python bench.py --gpus 2 --steps 5 --warmup 2 > gpurun_out/bench_2rank_gloo.json 2> gpurun_out/bench_2rank_gloo.err || echo "2-rank rehearsal failed"
+T2P_FORCE_DEVICE=0 T2P_DIST_BACKEND=gloo timeout -k 10 600 python bench.py --gpus 2 --steps 5 --warmup 2 --full 2>&1 | grep '^{' || echo "2-rank rehearsal failed"
 B="python3 bench.py --workload cfg3 --steps 5 --warmup 2 --no-cpu-baseline --no-f32"
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d gpurun_out/pmc_r04c3_sq1 -- $B > gpurun_out/pmc_c3_sq1.log 2>&1
 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d gpurun_out/pmc_r04c3_tcc -- $B > gpurun_out/pmc_c3_tcc.log 2>&1
