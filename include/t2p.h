@@ -153,7 +153,15 @@ int t2p_sampler_run(t2p_sampler* s, float* x, float* out, int prior_given, int n
  * on `stream` (not the default stream) and discarded, nothing executes; call after at least one eager step */
 int t2p_sampler_count_dispatches(t2p_sampler* s, float* x, float* x_mean, void* stream, int* n_out);
 
-/* ---- training step (first slice: fp32 arithmetic only, VE SDE) ------------------
+/* ---- training step (VE SDE) ------------------------------------------------------
+ * model->compute_dtype selects the products: T2P_DTYPE_F32 exact f32; T2P_DTYPE_F16 / T2P_DTYPE_BF16 16-bit operands with fp32
+ * accumulation (residual-block 3x3 convolutions on the 16-bit implicit GEMM, every other product on t2p_op_tgemm16; input / head
+ * convolutions, norms, softmax and elementwise work stay fp32).  Parameters, gradients, Adam moments, EMA and loss are fp32 in every
+ * mode.  16-bit modes seed the backward pass with S dL/do (S = 2^round(log2(B C L L))) and divide S out of the gradient buffer, so
+ * t2p_train_read(GRAD) and t2p_train_grad_buffer hold true gradients; every reduction that feeds a gradient or an update runs in a
+ * fixed order (gradients and post-step state bitwise reproducible; the scalar loss is summed with double atomics), and
+ * t2p_train_step / t2p_train_apply return an error and change nothing (parameters, moments, EMA, counters) when the loss or the
+ * gradient norm is not finite.
  * t2p_train_create      <- get_model + get_optimizer + ExponentialMovingAverage(model.parameters(), decay)
  *                          (score_sde_pytorch/utils.py:4-9, losses.py:26-36, models/ema.py:13-30; train.py builds `state` from them)
  * t2p_train_load_param  <- load_state_dict of one tensor; the EMA shadow starts as a copy (ema.py:28-29)
@@ -217,6 +225,12 @@ int64_t t2p_train_device_bytes(const t2p_trainer* t);
 int t2p_op_tgemm(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBk, int64_t sBn, float* C, int64_t ldc, int M, int N,
                  int K, int nz, int64_t sAz, int64_t sBz, int64_t sCz, float alpha, float beta, const float* bias_n, int ksplit, int conv,
                  int H, int W, int conv_C, void* stream);
+/* the same product on the 16-bit matrix pipe (dtype 1 = bf16, 2 = f16; the mixed-precision training step): A, B, C and bias stay fp32 in
+ * memory, A and B are rounded to dtype (nearest even, no saturation: an overflow becomes +-inf) as they are staged, products accumulate
+ * in fp32; split-K sums its partial tiles in a fixed order (bitwise reproducible, any beta).  Same arguments as t2p_op_tgemm. */
+int t2p_op_tgemm16(int dtype, const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBk, int64_t sBn, float* C, int64_t ldc,
+                   int M, int N, int K, int nz, int64_t sAz, int64_t sBz, int64_t sCz, float alpha, float beta, const float* bias_n, int ksplit,
+                   int conv, int H, int W, int conv_C, void* stream);
 /* backward halves of the operators (gradients accumulate into dx / dgamma / dbeta / du) */
 int t2p_op_groupnorm_backward(const float* x, const float* dy, const float* gamma, const float* beta, int silu, int batch, int HW, int C,
                               int groups, float eps, float* dx, float* dgamma, float* dbeta, void* stream);

@@ -10,6 +10,15 @@
 // everything else -- linear layers both ways, weight gradients, the attention products -- on the strided GEMM of
 // train_kernels.hip.  Every gradient buffer is zero-initialised at first use and accumulated into, so fan-out (residual
 // connections, U-Net skips, the shared time embedding) needs no special cases.
+//
+// Mixed precision (compute_dtype F16 / BF16): the residual-block convolutions run forward and data-gradient on the engine's 16-bit
+// implicit GEMM (fp32 activations rounded once into a pass-local 16-bit copy, 16-bit weight copies made by prep_weights), every strided product on
+// launch_tgemm16; the input and head convolutions (5 or 8 channels) keep the exact-f32 kernel for their forward and data gradient.
+// The backward pass is seeded with S dL/do, S = 2^round(log2(B C L L)) (the fp32 seed is ~1e-5 at full size, at the bottom of
+// f16's normal range), and S is divided out of the flat gradient buffer once at the end.  Every reduction that feeds a gradient, the
+// gradient norm or an update runs in a fixed order, so the gradients and the state after a 16-bit step are bitwise reproducible (the
+// scalar loss itself is still summed with double atomics, shared with the fp32 step).  apply() refuses (and changes nothing) when the
+// loss or the gradient norm is not finite.
 #include "train.h"
 
 #include <algorithm>
@@ -92,7 +101,9 @@ int Trainer::map_layer(const Layer& l, LayerT* o) {
 }
 
 int Trainer::build() {
-  T2P_REQUIRE(mc_.compute_dtype == DT_F32, "the training step is fp32 only (first slice of SURVEY.md 8(f)4)");
+  T2P_REQUIRE(mc_.compute_dtype == DT_F32 || mc_.compute_dtype == DT_F16 || mc_.compute_dtype == DT_BF16,
+              "the training step computes in f32, f16 or bf16");
+  dt_ = mc_.compute_dtype;
   T2P_REQUIRE(tc_.dropout >= 0.0 && tc_.dropout < 1.0 && tc_.ema_rate >= 0.0 && tc_.ema_rate <= 1.0, "dropout / ema_rate");
   int dev = 0;
   T2P_HIP_CHECK(hipGetDevice(&dev));       // fails without a HIP device: there is no CPU fallback
@@ -160,6 +171,15 @@ int Trainer::build() {
       if (!c->wd) return T2P_ERR_HIP;
     }
     dwc_floats_ = std::max(dwc_floats_, (size_t)c->Co * 9 * c->Cip);
+    if (dt_ != DT_F32 && c != &pre_conv_ && c != &head_conv_) {
+      c->wf16 = pool_.persistent((size_t)c->Co * 9 * c->Cip * 2);
+      c->wd16 = pool_.persistent((size_t)c->Ci * 9 * c->Cop * 2);
+      if (!c->wf16 || !c->wd16) return T2P_ERR_HIP;
+    }
+  }
+  if (dt_ != DT_F32) {
+    sumsq_part_ = (double*)pool_.persistent(1024 * 8);
+    if (!sumsq_part_) return T2P_ERR_HIP;
   }
   dwc_ = (float*)pool_.persistent(dwc_floats_ * 4);
   if (!dwc_) return T2P_ERR_HIP;
@@ -255,20 +275,65 @@ void Trainer::release() {
 
 int Trainer::prep_weights(const float* P, hipStream_t s) {
   for (Conv* c : convs_) T2P_TRY(launch_conv_w_prep(P + c->w, c->wf, c->wd, c->Co, c->Ci, c->Cip, c->Cop, s));
+  for (Conv* c : convs_) {
+    if (!c->wf16) continue;
+    T2P_TRY(launch_convert(c->wf, c->wf16, dt_, (long)c->Co * 9 * c->Cip, s));
+    T2P_TRY(launch_convert(c->wd, c->wd16, dt_, (long)c->Ci * 9 * c->Cop, s));
+  }
   return T2P_OK;
+}
+
+// out += column sums of dy (bias gradients): ld_out == 0 -> over all `rows` (launch_colsum); else per sample, nz samples of `rows` rows
+// each, into out [nz][ld_out] (launch_colsum_per_sample)
+int Trainer::colsum(const float* dy, int nz, long rows, int N, long ld, float* out, long ld_out) {
+  if (dt_ == DT_F32) return ld_out == 0 ? launch_colsum(dy, rows, N, ld, out, s_) : launch_colsum_per_sample(dy, nz, (int)rows, N, out, ld_out, 1, s_);
+  float* ws = (float*)pool_.get((size_t)colsum_fixed_ws_floats(nz, rows, N) * 4);
+  if (!ws) return T2P_ERR_HIP;
+  const int rc = launch_colsum_fixed(dy, nz, rows, N, ld, out, ld_out == 0 ? N : ld_out, 1, ws, s_);
+  pool_.put(ws);
+  return rc;
+}
+
+int Trainer::tg(const TGemmArgs& a) {
+  if (dt_ == DT_F32) return launch_tgemm(a, s_);
+  const long n = tgemm16_ws_floats(a);
+  float* ws = nullptr;
+  if (n > 0) {
+    ws = (float*)pool_.get((size_t)n * 4);
+    if (!ws) return T2P_ERR_HIP;
+  }
+  const int rc = launch_tgemm16(a, dt_, ws, s_);
+  if (ws) pool_.put(ws);             // stream-ordered: the next user of the block runs after this product
+  return rc;
 }
 
 // ---- operators -----------------------------------------------------------------------------------------------------------------------------
 // y [B][H W][ldc] = conv3x3(x) + bias (+ bias_bn[b][:]: Dense_0(act(temb)) of the block, layers.py:316) (+ residual_inplace, which may be y:
-// the register-staged kernel reads and writes an output element in the same thread) on the engine's exact-f32 implicit-GEMM kernel
+// the register-staged kernel reads and writes an output element in the same thread) on the engine's exact-f32 implicit-GEMM kernel, or
+// with dtype F16 / BF16 on its 16-bit kernels: x16 = x rounded to dtype (the layout x has), w16 = the 16-bit copy of w
 static int conv_forward(const float* x, int B, int H, int W, int Cin, const float* w, long ldb, const float* bias, const float* bias_bn, int N,
-                        float* y, long ldc, const float* residual_inplace, hipStream_t s) {
+                        float* y, long ldc, const float* residual_inplace, hipStream_t s, int dtype = DT_F32, const void* w16 = nullptr,
+                        const void* x16 = nullptr) {
   GemmParams p;
-  p.dtype = DT_F32; p.a_f32 = 1; p.A0 = x; p.C0 = Cin; p.lda0 = Cin; p.taps = 9; p.H = H; p.W = W;
-  p.Bw = w; p.ldb = ldb; p.M = B * H * W; p.N = N; p.bias_n = bias; p.bias_bn = bias_bn; p.rows_per_batch = H * W; p.ld_bn = N;
+  p.dtype = dtype; p.a_f32 = 1; p.A0 = x; p.C0 = Cin; p.lda0 = Cin; p.taps = 9; p.H = H; p.W = W;
+  if (dtype != DT_F32) { p.a_f32 = 0; p.A0 = x16; }
+  p.Bw = dtype == DT_F32 ? (const void*)w : w16; p.ldb = ldb; p.M = B * H * W; p.N = N; p.bias_n = bias; p.bias_bn = bias_bn; p.rows_per_batch = H * W; p.ld_bn = N;
   p.R = residual_inplace; p.ldr = ldc;
   p.C = y; p.c_f32 = 1; p.ldc = ldc;
   return launch_gemm(p, s);
+}
+
+// a residual-block 3x3 convolution in 16-bit modes: the fp32 input is rounded once into a pass-local 16-bit copy, so the engine's
+// LDS-DMA implicit GEMM (16-bit A only) takes the layers it covers
+int Trainer::conv16(const float* x, int B, int H, int W, int Cin, const void* w16, long ldb, const float* bias, const float* bias_bn, int N,
+                    float* y, long ldc, const float* residual_inplace) {
+  const long n = (long)B * H * W * Cin;
+  void* x16 = pool_.get((size_t)n * 2);
+  if (!x16) return T2P_ERR_HIP;
+  int rc = launch_convert(x, x16, dt_, n, s_);
+  if (rc == T2P_OK) rc = conv_forward(x, B, H, W, Cin, nullptr, ldb, bias, bias_bn, N, y, ldc, residual_inplace, s_, dt_, w16, x16);
+  pool_.put(x16);                  // stream-ordered: the next user of the block runs after this convolution
+  return rc;
 }
 
 int Trainer::linear(TT* x, const Lin& l, TT** out) {
@@ -281,7 +346,7 @@ int Trainer::linear(TT* x, const Lin& l, TT** out) {
   a.B = Pc_ + l.w; a.sBk = l.nin ? l.N : 1; a.sBn = l.nin ? 1 : l.K;
   a.C = y->p; a.ldc = l.N; a.M = (int)rows; a.N = l.N; a.K = l.K;
   a.bias_n = l.b >= 0 ? Pc_ + l.b : nullptr;
-  T2P_TRY(launch_tgemm(a, s_));
+  T2P_TRY(tg(a));
   *out = y;
   const Lin L = l;
   tape_.push_back([this, x, y, L, rows]() -> int {
@@ -292,14 +357,14 @@ int Trainer::linear(TT* x, const Lin& l, TT** out) {
       d.A = y->g; d.sAm = L.N; d.sAk = 1;
       d.B = Pc_ + L.w; d.sBk = L.nin ? 1 : L.K; d.sBn = L.nin ? L.N : 1;       // B(k = n', n = k') = W[n'][k'] (Linear) / W[k'][n'] (NIN)
       d.C = gx; d.ldc = L.K; d.M = (int)rows; d.N = L.K; d.K = L.N; d.beta = 1.f;
-      T2P_TRY(launch_tgemm(d, s_));
+      T2P_TRY(tg(d));
     }
     TGemmArgs w;                                  // dW += dy^T x (Linear [N][K]) / x^T dy (NIN [K][N]); K of this product = the rows
     if (!L.nin) { w.A = y->g; w.sAm = 1; w.sAk = L.N; w.B = x->p; w.sBk = L.K; w.sBn = 1; w.M = L.N; w.N = L.K; }
     else        { w.A = x->p; w.sAm = 1; w.sAk = L.K; w.B = y->g; w.sBk = L.N; w.sBn = 1; w.M = L.K; w.N = L.N; }
     w.C = Gr_ + L.w; w.ldc = w.N; w.K = (int)rows; w.beta = 1.f; w.ksplit = 0;
-    T2P_TRY(launch_tgemm(w, s_));
-    if (L.b >= 0) T2P_TRY(launch_colsum(y->g, rows, L.N, L.N, Gr_ + L.b, s_));
+    T2P_TRY(tg(w));
+    if (L.b >= 0) T2P_TRY(colsum(y->g, 1, rows, L.N, L.N, Gr_ + L.b, 0));
     return T2P_OK;
   });
   return T2P_OK;
@@ -327,6 +392,7 @@ int Trainer::group_norm(TT* x, const Norm& n, int silu, TT** out) {
     T2P_GRAD(gx, x);
     float* ws = tmp((size_t)gn_bwd_ws_floats(B, HW, N.C, N.G) * 4);
     if (!ws) return T2P_ERR_HIP;
+    if (dt_ != DT_F32) return launch_gn_backward_fixed(x->p, y->g, stats, Pc_ + N.g, Pc_ + N.b, silu, B, HW, N.C, N.G, gx, Gr_ + N.g, Gr_ + N.b, ws, s_);
     return launch_gn_backward(x->p, y->g, stats, Pc_ + N.g, Pc_ + N.b, silu, B, HW, N.C, N.G, gx, Gr_ + N.g, Gr_ + N.b, ws, s_);
   });
   return T2P_OK;
@@ -341,6 +407,11 @@ int Trainer::layer_norm(TT* x, const Norm& n, TT** out) {
   tape_.push_back([this, x, y, N]() -> int {
     if (!y->g) return T2P_OK;
     T2P_GRAD(gx, x);
+    if (dt_ != DT_F32) {
+      float* ws = tmp((size_t)ln_bwd_fixed_ws_floats(x->rows(), N.C) * 4);
+      if (!ws) return T2P_ERR_HIP;
+      return launch_ln_backward_fixed(x->p, y->g, Pc_ + N.g, x->rows(), N.C, 1e-5f, gx, Gr_ + N.g, Gr_ + N.b, ws, s_);
+    }
     return launch_ln_backward(x->p, y->g, Pc_ + N.g, x->rows(), N.C, 1e-5f, gx, Gr_ + N.g, Gr_ + N.b, s_);
   });
   return T2P_OK;
@@ -362,14 +433,14 @@ int Trainer::attention(TT* q, TT* k, TT* v, int heads, float scale, TT** out) {
   a.B = k->p; a.sBk = 1; a.sBn = C; a.sBz0 = (long)nk * C; a.sBz1 = d;
   a.C = S; a.ldc = nk; a.sCz0 = (long)heads * nq * nk; a.sCz1 = (long)nq * nk; a.M = nq; a.N = nk; a.K = d;
   heads_of(a);
-  T2P_TRY(launch_tgemm(a, s_));
+  T2P_TRY(tg(a));
   T2P_TRY(launch_softmax(S, nk, P, nk, DT_F32, (long)B * heads * nq, nk, scale, s_));
   TGemmArgs b;                                   // o = P v
   b.A = P; b.sAm = nk; b.sAk = 1; b.sAz0 = (long)heads * nq * nk; b.sAz1 = (long)nq * nk;
   b.B = v->p; b.sBk = C; b.sBn = 1; b.sBz0 = (long)nk * C; b.sBz1 = d;
   b.C = o->p; b.ldc = C; b.sCz0 = (long)nq * C; b.sCz1 = d; b.M = nq; b.N = d; b.K = nk;
   heads_of(b);
-  T2P_TRY(launch_tgemm(b, s_));
+  T2P_TRY(tg(b));
   *out = o;
   tape_.push_back([this, q, k, v, o, P, S, B, heads, nq, nk, C, d, scale]() -> int {
     if (!o->g) return T2P_OK;
@@ -379,14 +450,14 @@ int Trainer::attention(TT* q, TT* k, TT* v, int heads, float scale, TT** out) {
     e.A = o->g; e.sAm = C; e.sAk = 1; e.sAz0 = (long)nq * C; e.sAz1 = d;
     e.B = v->p; e.sBk = 1; e.sBn = C; e.sBz0 = (long)nk * C; e.sBz1 = d;
     e.C = dP; e.ldc = nk; e.sCz0 = sP0; e.sCz1 = sP1; e.M = nq; e.N = nk; e.K = d; e.nz0 = B; e.nz1 = heads;
-    T2P_TRY(launch_tgemm(e, s_));
+    T2P_TRY(tg(e));
     if (v->needs_grad) {                         // dv += P^T dO
       T2P_GRAD(gv, v);
       TGemmArgs f;
       f.A = P; f.sAm = 1; f.sAk = nk; f.sAz0 = sP0; f.sAz1 = sP1;
       f.B = o->g; f.sBk = C; f.sBn = 1; f.sBz0 = (long)nq * C; f.sBz1 = d;
       f.C = gv; f.ldc = C; f.sCz0 = (long)nk * C; f.sCz1 = d; f.M = nk; f.N = d; f.K = nq; f.nz0 = B; f.nz1 = heads; f.beta = 1.f;
-      T2P_TRY(launch_tgemm(f, s_));
+      T2P_TRY(tg(f));
     }
     T2P_TRY(launch_softmax_backward(P, dP, (long)B * heads * nq, nk, scale, s_));     // dS (w.r.t. the raw scores q k^T)
     if (q->needs_grad) {                         // dq += dS k
@@ -395,7 +466,7 @@ int Trainer::attention(TT* q, TT* k, TT* v, int heads, float scale, TT** out) {
       f.A = dP; f.sAm = nk; f.sAk = 1; f.sAz0 = sP0; f.sAz1 = sP1;
       f.B = k->p; f.sBk = C; f.sBn = 1; f.sBz0 = (long)nk * C; f.sBz1 = d;
       f.C = gq; f.ldc = C; f.sCz0 = (long)nq * C; f.sCz1 = d; f.M = nq; f.N = d; f.K = nk; f.nz0 = B; f.nz1 = heads; f.beta = 1.f;
-      T2P_TRY(launch_tgemm(f, s_));
+      T2P_TRY(tg(f));
     }
     if (k->needs_grad) {                         // dk += dS^T q
       T2P_GRAD(gk, k);
@@ -403,7 +474,7 @@ int Trainer::attention(TT* q, TT* k, TT* v, int heads, float scale, TT** out) {
       f.A = dP; f.sAm = 1; f.sAk = nk; f.sAz0 = sP0; f.sAz1 = sP1;
       f.B = q->p; f.sBk = C; f.sBn = 1; f.sBz0 = (long)nq * C; f.sBz1 = d;
       f.C = gk; f.ldc = C; f.sCz0 = (long)nk * C; f.sCz1 = d; f.M = nk; f.N = d; f.K = nq; f.nz0 = B; f.nz1 = heads; f.beta = 1.f;
-      T2P_TRY(launch_tgemm(f, s_));
+      T2P_TRY(tg(f));
     }
     return T2P_OK;
   });
@@ -460,25 +531,27 @@ int Trainer::res_block(const LayerT& L, TT* x, TT* stemb, TT** out) {
   // h = Conv_0(a0) + bias + tb
   T2P_REQUIRE(a0->C == r.c0.Cip && r.c0.Cop == r.c0.Co && r.c1.Cop == r.c1.Co && r.c1.Cip == r.c1.Ci, "residual block channels are multiples of 8");
   T2P_ACT(h, B, H, W, r.c0.Co);
-  T2P_TRY(conv_forward(a0->p, B, H, W, a0->C, r.c0.wf, 9L * r.c0.Cip, Pc_ + r.c0.b, tb->p, r.c0.Co, h->p, r.c0.Co, nullptr, s_));
+  if (dt_ == DT_F32) T2P_TRY(conv_forward(a0->p, B, H, W, a0->C, r.c0.wf, 9L * r.c0.Cip, Pc_ + r.c0.b, tb->p, r.c0.Co, h->p, r.c0.Co, nullptr, s_));
+  else T2P_TRY(conv16(a0->p, B, H, W, a0->C, r.c0.wf16, 9L * r.c0.Cip, Pc_ + r.c0.b, tb->p, r.c0.Co, h->p, r.c0.Co, nullptr));
   auto conv_backward = [this](TT* in, TT* y, const Conv c, TT* tbias) -> int {
     if (!y->g) return T2P_OK;
     const int Bq = in->B, Hq = in->H, Wq = in->W;
     const long rows = in->rows();
     if (in->needs_grad) {                          // dX = conv3x3(dY, flipped transposed taps), accumulated in place through the residual operand
       T2P_GRAD(gi, in);
-      T2P_TRY(conv_forward(y->g, Bq, Hq, Wq, c.Cop, c.wd, 9L * c.Cop, nullptr, nullptr, c.Ci, gi, in->C, gi, s_));
+      if (dt_ == DT_F32) T2P_TRY(conv_forward(y->g, Bq, Hq, Wq, c.Cop, c.wd, 9L * c.Cop, nullptr, nullptr, c.Ci, gi, in->C, gi, s_));
+      else T2P_TRY(conv16(y->g, Bq, Hq, Wq, c.Cop, c.wd16, 9L * c.Cop, nullptr, nullptr, c.Ci, gi, in->C, gi));
     }
     T2P_HIP_CHECK(hipMemsetAsync(dwc_, 0, (size_t)c.Co * 9 * c.Cip * 4, s_));
     TGemmArgs w;                                   // dW[co][tap][ci] = sum_pixels dY[pixel][co] X[pixel + tap][ci]
     w.A = y->g; w.sAm = 1; w.sAk = y->C; w.B = in->p; w.conv_b = 1; w.H = Hq; w.W = Wq; w.conv_C = c.Cip; w.ldx = in->C;
     w.C = dwc_; w.ldc = 9L * c.Cip; w.M = c.Co; w.N = 9 * c.Cip; w.K = (int)rows; w.beta = 1.f; w.ksplit = 0;
-    T2P_TRY(launch_tgemm(w, s_));
+    T2P_TRY(tg(w));
     T2P_TRY(launch_conv_w_grad_fold(dwc_, Gr_ + c.w, c.Co, c.Ci, c.Cip, s_));
-    T2P_TRY(launch_colsum(y->g, rows, c.Co, y->C, Gr_ + c.b, s_));
+    T2P_TRY(colsum(y->g, 1, rows, c.Co, y->C, Gr_ + c.b, 0));
     if (tbias) {
       T2P_GRAD(gt, tbias);
-      T2P_TRY(launch_colsum_per_sample(y->g, Bq, Hq * Wq, c.Co, gt, c.Co, 1, s_));
+      T2P_TRY(colsum(y->g, Bq, (long)Hq * Wq, c.Co, c.Co, gt, c.Co));
     }
     return T2P_OK;
   };
@@ -513,7 +586,8 @@ int Trainer::res_block(const LayerT& L, TT* x, TT* stemb, TT** out) {
     a1 = y;
   }
   T2P_ACT(h2, B, H, W, r.c1.Co);
-  T2P_TRY(conv_forward(a1->p, B, H, W, a1->C, r.c1.wf, 9L * r.c1.Cip, Pc_ + r.c1.b, nullptr, r.c1.Co, h2->p, r.c1.Co, nullptr, s_));
+  if (dt_ == DT_F32) T2P_TRY(conv_forward(a1->p, B, H, W, a1->C, r.c1.wf, 9L * r.c1.Cip, Pc_ + r.c1.b, nullptr, r.c1.Co, h2->p, r.c1.Co, nullptr, s_));
+  else T2P_TRY(conv16(a1->p, B, H, W, a1->C, r.c1.wf16, 9L * r.c1.Cip, Pc_ + r.c1.b, nullptr, r.c1.Co, h2->p, r.c1.Co, nullptr));
   {
     const Conv c = r.c1;
     tape_.push_back([conv_backward, a1, h2, c]() -> int { return conv_backward(a1, h2, c, nullptr); });
@@ -644,9 +718,9 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool bac
       TGemmArgs w;
       w.A = h0->g; w.sAm = 1; w.sAk = h0->C; w.B = x0->p; w.conv_b = 1; w.H = x0->H; w.W = x0->W; w.conv_C = c.Cip; w.ldx = x0->C;
       w.C = dwc_; w.ldc = 9L * c.Cip; w.M = c.Co; w.N = 9 * c.Cip; w.K = (int)x0->rows(); w.beta = 1.f; w.ksplit = 0;
-      T2P_TRY(launch_tgemm(w, s_));
+      T2P_TRY(tg(w));
       T2P_TRY(launch_conv_w_grad_fold(dwc_, Gr_ + c.w, c.Co, c.Ci, c.Cip, s_));
-      return launch_colsum(h0->g, h0->rows(), c.Co, h0->C, Gr_ + c.b, s_);
+      return colsum(h0->g, 1, h0->rows(), c.Co, h0->C, Gr_ + c.b, 0);
     });
   }
   std::vector<TT*> hs{h0};
@@ -689,9 +763,9 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool bac
       TGemmArgs w;
       w.A = o->g; w.sAm = 1; w.sAk = 8; w.B = a->p; w.conv_b = 1; w.H = a->H; w.W = a->W; w.conv_C = c.Cip; w.ldx = a->C;
       w.C = dwc_; w.ldc = 9L * c.Cip; w.M = c.Co; w.N = 9 * c.Cip; w.K = (int)a->rows(); w.beta = 1.f; w.ksplit = 0;
-      T2P_TRY(launch_tgemm(w, s_));
+      T2P_TRY(tg(w));
       T2P_TRY(launch_conv_w_grad_fold(dwc_, Gr_ + c.w, c.Co, c.Ci, c.Cip, s_));
-      return launch_colsum(o->g, a->rows(), c.Co, 8, Gr_ + c.b, s_);
+      return colsum(o->g, 1, a->rows(), c.Co, 8, Gr_ + c.b, 0);
     });
   }
   float* d_o = nullptr;
@@ -701,14 +775,19 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool bac
   }
   T2P_TRY(launch_dsm_loss(o->p, 8, z, stdv, scale, mask, num_elem, B, Cx, L, loss_sum, d_o, 8, score_out, s_));
   T2P_TRY(launch_dsm_finish(loss_sum, num_elem, B, loss_dev, s_));
+  // 16-bit modes: seed the backward pass with S dL/do (S a power of two: exact in fp32) and divide S out of the flat gradient buffer
+  const float S = dt_ == DT_F32 ? 1.f : std::ldexp(1.f, (int)std::lround(std::log2((double)B * Cx * HW)));
+  if (backward && S != 1.f) T2P_TRY(launch_scale(d_o, S, o->numel(), s_));
   if (backward)
     for (auto it = tape_.rbegin(); it != tape_.rend(); ++it) T2P_TRY((*it)());
+  if (backward && S != 1.f) T2P_TRY(launch_scale(Gr_, 1.f / S, total_, s_));
   return T2P_OK;
 }
 
 int Trainer::loss(const t2p_train_batch& b, bool backward, bool use_ema, float* loss_host, float* score_out, hipStream_t s) {
   T2P_REQUIRE(loss_host, "loss output");
   s_ = s;
+  if (backward) last_loss_finite_ = false;        // the overflow guard trusts only a completed backward pass
   if (backward) T2P_HIP_CHECK(hipMemsetAsync(Gr_, 0, (size_t)total_ * 4, s));      // optimizer.zero_grad()
   const double keep_dropout = tc_.dropout;
   if (use_ema) tc_.dropout = 0.0;                 // eval mode (models/utils.py:113-115)
@@ -720,6 +799,7 @@ int Trainer::loss(const t2p_train_batch& b, bool backward, bool use_ema, float* 
   if (rc != T2P_OK) return rc;
   T2P_HIP_CHECK(e);
   T2P_HIP_CHECK(hipMemcpy(loss_host, loss_dev_, 4, hipMemcpyDeviceToHost));
+  if (backward) last_loss_finite_ = std::isfinite(*loss_host);
   return T2P_OK;
 }
 
@@ -738,7 +818,19 @@ int Trainer::apply(hipStream_t s) {
   a.bias1 = (float)(1.0 - std::pow(tc_.beta1, (double)k));
   a.bias2_sqrt = (float)std::sqrt(1.0 - std::pow(0.999, (double)k));
   a.grad_clip = (float)tc_.grad_clip;
-  if (tc_.grad_clip >= 0) {
+  if (dt_ != DT_F32) {
+    // overflow guard (AMP's skipped step, reported): a loss or gradient norm that is not finite changes nothing
+    double sumsq = 0.0;
+    T2P_TRY(launch_sumsq_fixed(Gr_, total_, sumsq_part_, sumsq_, s));
+    T2P_HIP_CHECK(hipMemcpyAsync(&sumsq, sumsq_, 8, hipMemcpyDeviceToHost, s));
+    T2P_HIP_CHECK(hipStreamSynchronize(s));
+    T2P_REQUIRE(last_loss_finite_ && std::isfinite(sumsq),
+                std::string("16-bit training step skipped: ") +
+                    (last_loss_finite_ ? "the gradient norm is not finite (f16 / bf16 overflow)"
+                                       : "the loss of the last backward pass is not finite (f16 / bf16 overflow), or that pass did not complete") +
+                    "; parameters, optimizer state, EMA and step counters are unchanged");
+    if (tc_.grad_clip >= 0) a.sumsq = sumsq_;
+  } else if (tc_.grad_clip >= 0) {
     T2P_HIP_CHECK(hipMemsetAsync(sumsq_, 0, 8, s));
     T2P_TRY(launch_sumsq(Gr_, total_, sumsq_, s));
     a.sumsq = sumsq_;

@@ -1,6 +1,7 @@
-// Training step of the score network (first slice: fp32 only): forward pass that keeps what the backward pass
-// needs, backward pass, denoising score-matching loss, Adam / warm-up / clipping and the EMA update
-// (reference score_sde_pytorch/losses.py:26-186, score_sde_pytorch/models/ema.py:32-49).
+// Training step of the score network: forward pass that keeps what the backward pass needs, backward pass,
+// denoising score-matching loss, Adam / warm-up / clipping and the EMA update (reference score_sde_pytorch/losses.py:26-186,
+// score_sde_pytorch/models/ema.py:32-49).  compute_dtype F32: exact-f32 products; F16 / BF16: 16-bit products with fp32 accumulation,
+// everything the optimizer sees (parameters, gradients, moments, EMA, loss) fp32.
 #pragma once
 #include <deque>
 #include <functional>
@@ -53,7 +54,8 @@ class Trainer {
   int64_t device_bytes() const { return (int64_t)pool_.held_bytes(); }
 
  private:
-  struct Conv { long w = 0, b = 0; int Co = 0, Ci = 0, Cip = 0, Cop = 0; float* wf = nullptr; float* wd = nullptr; };   // offsets into the flat buffers
+  struct Conv { long w = 0, b = 0; int Co = 0, Ci = 0, Cip = 0, Cop = 0; float* wf = nullptr; float* wd = nullptr;   // offsets into the flat buffers
+                void* wf16 = nullptr; void* wd16 = nullptr; };   // 16-bit copies of wf / wd (16-bit modes, residual-block convolutions)
   struct Lin { long w = 0, b = -1; int N = 0, K = 0; bool nin = false; };
   struct Norm { long g = 0, b = 0; int C = 0, G = 0; };
   struct ResL { Norm gn0, gn1; Conv c0, c1; Lin dense, sc; bool has_sc = false; };
@@ -64,6 +66,10 @@ class Trainer {
   long poff(const std::string& name, std::vector<int64_t> shape);
   int map_layer(const Layer& l, LayerT* out);
   int prep_weights(const float* P, hipStream_t s);
+  int tg(const TGemmArgs& a);               // one strided product: launch_tgemm (F32) or launch_tgemm16 (F16 / BF16)
+  int conv16(const float* x, int B, int H, int W, int Cin, const void* w16, long ldb, const float* bias, const float* bias_bn, int N,
+             float* y, long ldc, const float* residual_inplace);   // residual-block 3x3 convolution, 16-bit modes
+  int colsum(const float* dy, int nz, long rows, int N, long ld, float* out, long ld_out);   // bias gradients (fixed order in 16-bit modes)
 
   // forward ops: each appends its backward to tape_
   TT* act(int B, int H, int W, int C, bool needs_grad = true);
@@ -94,6 +100,9 @@ class Trainer {
   float* loss_dev_ = nullptr;
   float* inv_sigma_ = nullptr;
   int64_t step_ = 0, adam_k_ = 0, ema_k_ = 0, loss_calls_ = 0;
+  int dt_ = DT_F32;                 // compute dtype of the products
+  double* sumsq_part_ = nullptr;    // 16-bit modes: fixed-order gradient norm (launch_sumsq_fixed)
+  bool last_loss_finite_ = false;   // 16-bit modes: the last backward pass completed with a finite loss (the overflow guard of apply)
   std::vector<LayerT> in_layers_;
   std::vector<std::vector<LayerT>> in_stages_, out_stages_;
   std::vector<LayerT> mid_;

@@ -148,6 +148,30 @@ int t2p_op_tgemm(const float* A, int64_t sAm, int64_t sAk, const float* B, int64
   API_END
 }
 
+int t2p_op_tgemm16(int dtype, const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBk, int64_t sBn, float* C, int64_t ldc,
+                   int M, int N, int K, int nz, int64_t sAz, int64_t sBz, int64_t sCz, float alpha, float beta, const float* bias_n, int ksplit,
+                   int conv, int H, int W, int conv_C, void* stream) {
+  API_BEGIN
+  TGemmArgs a;
+  a.A = A; a.sAm = sAm; a.sAk = sAk; a.sAz0 = sAz;
+  a.B = B; a.sBk = sBk; a.sBn = sBn; a.sBz0 = sBz;
+  a.C = C; a.ldc = ldc; a.sCz0 = sCz; a.M = M; a.N = N; a.K = K; a.nz0 = nz; a.nz1 = 1;
+  a.alpha = alpha; a.beta = beta; a.bias_n = bias_n; a.ksplit = ksplit;
+  if (conv) { a.conv_b = 1; a.H = H; a.W = W; a.conv_C = conv_C; a.ldx = sBz; a.sBz0 = 0; }
+  T2P_REQUIRE(M > 0 && N > 0 && K > 0 && nz >= 1 && ksplit >= 0, "tgemm16 shapes");
+  hipStream_t s = (hipStream_t)stream;
+  const long n = tgemm16_ws_floats(a);
+  float* ws = nullptr;
+  if (n > 0) T2P_HIP_CHECK(hipMalloc(&ws, (size_t)n * 4));
+  int rc = launch_tgemm16(a, dtype, ws, s);
+  if (ws) {
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(ws);
+  }
+  return rc;
+  API_END
+}
+
 // the op-level backward entry points take eps and recompute the forward statistics themselves (tests hold no engine state)
 int t2p_op_groupnorm_backward(const float* x, const float* dy, const float* gamma, const float* beta, int silu, int batch, int HW, int C,
                               int groups, float eps, float* dx, float* dgamma, float* dbeta, void* stream) {

@@ -25,6 +25,12 @@ struct TGemmArgs {
   int conv_b = 0, H = 0, W = 0, conv_C = 0; long ldx = 0;
 };
 int launch_tgemm(const TGemmArgs& a, hipStream_t s);
+// the same product on the 16-bit matrix pipe (mixed-precision training step): A and B stay fp32 in memory and are rounded to dtype
+// (DT_F16 / DT_BF16, round to nearest even, no saturation) on the way into LDS; fp32 accumulation and epilogue.  Split-K (ksplit > 1,
+// or chosen when ksplit == 0) writes partial tiles to ws and a second pass sums them in a fixed order: bitwise reproducible, any beta.
+// ws: tgemm16_ws_floats(a) floats (0: no workspace needed)
+long tgemm16_ws_floats(const TGemmArgs& a);
+int launch_tgemm16(const TGemmArgs& a, int dtype, float* ws, hipStream_t s);
 
 // ---- GroupNorm backward (nn.GroupNorm + optional SiLU, layers.py:282,304,317; attention.py:77) -------------------------------------
 // y = act(gamma (x - mean) rstd + beta); x, dy, dx: NHWC [B][HW][C] fp32; stats [B][G][2] = (mean, rstd) of the forward pass.
@@ -32,9 +38,16 @@ int launch_tgemm(const TGemmArgs& a, hipStream_t s);
 long gn_bwd_ws_floats(int B, int HW, int C, int G);
 int launch_gn_backward(const float* x, const float* dy, const float* stats, const float* gamma, const float* beta, int silu,
                        int B, int HW, int C, int G, float* dx, float* dgamma, float* dbeta, float* ws, hipStream_t s);
+// the same with d gamma / d beta summed over the batch in a fixed order (bitwise reproducible)
+int launch_gn_backward_fixed(const float* x, const float* dy, const float* stats, const float* gamma, const float* beta, int silu,
+                             int B, int HW, int C, int G, float* dx, float* dgamma, float* dbeta, float* ws, hipStream_t s);
 // ---- LayerNorm backward (attention.py:203-205), rows x C, eps as the forward -----------------------------------------------------
 int launch_ln_backward(const float* x, const float* dy, const float* gamma, long rows, int C, float eps, float* dx, float* dgamma,
                        float* dbeta, hipStream_t s);
+// the same with a fixed summation order for d gamma / d beta (bitwise reproducible); ws: ln_bwd_fixed_ws_floats(rows, C) floats
+long ln_bwd_fixed_ws_floats(long rows, int C);
+int launch_ln_backward_fixed(const float* x, const float* dy, const float* gamma, long rows, int C, float eps, float* dx, float* dgamma,
+                             float* dbeta, float* ws, hipStream_t s);
 // ---- softmax backward, in place: dP[r][j] <- scale P[r][j] (dP[r][j] - sum_j dP[r][j] P[r][j])  (P = softmax(scale S)) ------------------
 int launch_softmax_backward(const float* P, float* dP, long rows, int n, float scale, hipStream_t s);
 // ---- GEGLU backward (attention.py:37-44): u = [a | g], out = a gelu(g);  du += [dy gelu(g) | dy a gelu'(g)] ----------------------------
@@ -51,6 +64,10 @@ int launch_copy_cols(const float* src, long ld_src, long src_off, float* dst, lo
 int launch_colsum(const float* dy, long rows, int N, long ld, float* out, hipStream_t s);
 // out[b][n] (+)= sum_p dy[b][p][n]              (gradient of the per-sample time-embedding bias, layers.py:316)
 int launch_colsum_per_sample(const float* dy, int B, int HW, int N, float* out, long ld_out, int accumulate, hipStream_t s);
+// fixed-order column sums (bitwise reproducible): out[z][n] (+)= sum_r dy[z rows_per_z + r][n]; ws: colsum_fixed_ws_floats floats
+long colsum_fixed_ws_floats(int nz, long rows_per_z, int N);
+int launch_colsum_fixed(const float* dy, int nz, long rows_per_z, int N, long ld, float* out, long ld_out, int accumulate, float* ws,
+                        hipStream_t s);
 // nearest 2x up-sampling / 2x2 mean down-sampling of NHWC maps (layers.py:179-188) and their backward (+=)
 int launch_up2(const float* x, float* y, int B, int H, int W, int C, hipStream_t s);               // x [B][H][W][C] -> y [B][2H][2W][C]
 int launch_up2_backward(const float* dy, float* dx, int B, int H, int W, int C, hipStream_t s);
@@ -87,6 +104,7 @@ int launch_dsm_finish(const double* loss_sum, const float* num_elem, int B, floa
 
 // ---- optimizer (losses.py:26-51: Adam, warm-up, clip_grad_norm_) and EMA (ema.py:32-49) over flat parameter buffers ------------------------
 int launch_sumsq(const float* g, long n, double* out, hipStream_t s);      // *out += sum g^2   (zero it first)
+int launch_sumsq_fixed(const float* g, long n, double* partial, double* out, hipStream_t s);   // *out = sum g^2, fixed order; partial: 1024 doubles
 struct AdamArgs {
   float* p = nullptr; float* g = nullptr; float* m = nullptr; float* v = nullptr; long n = 0;
   float lr = 0.f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f, weight_decay = 0.f;
@@ -96,5 +114,6 @@ struct AdamArgs {
 };
 int launch_adam(const AdamArgs& a, hipStream_t s);
 int launch_ema(float* shadow, const float* p, float one_minus_decay, long n, hipStream_t s);   // shadow -= (1 - d) (shadow - p)
+int launch_scale(float* x, float a, long n, hipStream_t s);                                   // x *= a
 
 }  // namespace t2p

@@ -1,4 +1,7 @@
-// Kernels of the training step (first slice): fp32, gfx950 only.
+// Kernels of the training step: fp32 storage, gfx950 only.
+//
+//   * tgemm16_kernel     the same strided GEMM with 16-bit products (v_mfma_f32_32x32x16_{f16,bf16}, fp32 accumulation) for the
+//                        mixed-precision step: operands rounded as they are staged, split-K reduced in a fixed order
 //
 //   * tgemm_kernel       strided batched GEMM on v_mfma_f32_32x32x2_f32 (exact fp32 products): every product of the backward pass that
 //                        is not a 3x3 convolution over pixels -- dY W, dY^T X, q k^T, P v, P^T dO, dS^T q ... -- reads its operands
@@ -200,6 +203,302 @@ int launch_tgemm(const TGemmArgs& a, hipStream_t s) {
 }
 
 // =====================================================================================================================================
+// strided GEMM, 16-bit products (mixed-precision training step): the same TGemmArgs views, batches, epilogue and convolution gather
+// as tgemm_kernel; the fp32 operands are rounded to f16 / bf16 (round to nearest even, no saturation: an overflow becomes +-inf) while
+// they are staged into LDS and multiplied on v_mfma_f32_32x32x16_{f16,bf16} with fp32 accumulation.
+//   * LDS holds both tiles K-contiguous, [row][BK + 8] 16-bit elements: one ds_read_b128 per 32 x 16 fragment, an 80-byte row pitch
+//     (20 banks) keeps the eight rows a 16-byte read phase touches on disjoint banks
+//   * a thread stages 8 consecutive k of one row (one 16-byte LDS store); along the contiguous global dimension the lanes of a wave
+//     read neighbouring addresses (m- / n-contiguous views), or each lane reads two float4 (k-contiguous views that are 16-byte aligned)
+//   * split-K writes raw partial tiles to a workspace [ks][z][M][N]; tgemm16_reduce_kernel sums them in ks order and applies the
+//     epilogue, so the result does not depend on the order in which workgroups finish (no atomics: bitwise reproducible)
+// =====================================================================================================================================
+template <typename TC> __device__ inline uint4 tg_pack8(const float* f) {
+  uint32_t w[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    uint16_t lo, hi;
+    if constexpr (sizeof(TC) == 2 && dtype_of<TC>::value == DT_F16) {
+      lo = __builtin_bit_cast(uint16_t, (_Float16)f[2 * i]);
+      hi = __builtin_bit_cast(uint16_t, (_Float16)f[2 * i + 1]);
+    } else {
+      lo = f32_to_bf16_bits(f[2 * i]);
+      hi = f32_to_bf16_bits(f[2 * i + 1]);
+    }
+    w[i] = (uint32_t)lo | ((uint32_t)hi << 16);
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+typedef _Float16 tg_f16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 tg_bf16x8 __attribute__((ext_vector_type(8)));
+template <typename TC> __device__ inline void tg_mma16(const uint4& a, const uint4& b, tg_f32x16& c) {
+  if constexpr (dtype_of<TC>::value == DT_F16)
+    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(tg_f16x8, a), __builtin_bit_cast(tg_f16x8, b), c, 0, 0, 0);
+  else
+    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(tg_bf16x8, a), __builtin_bit_cast(tg_bf16x8, b), c, 0, 0, 0);
+}
+
+template <typename TC, int BM, int BN, bool AMC, bool BNC, bool CONVB>
+__global__ __launch_bounds__(256) void tgemm16_kernel(const TGemmArgs p, const int kper, float* __restrict__ ws, const int vec_a,
+                                                      const int vec_b) {
+  constexpr int BK = 32, LDK = BK + 8;
+  constexpr int TM = BM / 64, TN = BN / 64;
+  constexpr int EA = BM * BK / (256 * 8), EB = BN * BK / (256 * 8);   // 8-element k-groups staged per thread
+  __shared__ __attribute__((aligned(16))) uint16_t As[BM * LDK];
+  __shared__ __attribute__((aligned(16))) uint16_t Bs[BN * LDK];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, lr = lane & 31, lh = lane >> 5;
+  int zz = blockIdx.z;
+  const int ks = zz % p.ksplit; zz /= p.ksplit;
+  const int z1 = zz % p.nz1, z0 = zz / p.nz1;
+  const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+  const int kb = ks * kper, ke = min(p.K, kb + kper);
+
+  const float* A = p.A + (long)z0 * p.sAz0 + (long)z1 * p.sAz1;
+  const float* B = p.B + (long)z0 * p.sBz0 + (long)z1 * p.sBz1;
+  const int HW = p.H * p.W;
+
+  tg_f32x16 acc[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) acc[i][j][v] = 0.f;
+
+  // staging slots of this thread: item e = (row r / column n, k-group q); fixed for the whole K loop
+  int ar[EA], aq[EA], bnl[EB], bq[EB];
+#pragma unroll
+  for (int e = 0; e < EA; ++e) {
+    const int idx = tid + 256 * e;
+    ar[e] = AMC ? idx % BM : idx / 4; aq[e] = AMC ? idx / BM : idx % 4;
+  }
+  constexpr bool NCONT = BNC || CONVB;
+#pragma unroll
+  for (int e = 0; e < EB; ++e) {
+    const int idx = tid + 256 * e;
+    bnl[e] = NCONT ? idx % BN : idx / 4; bq[e] = NCONT ? idx / BN : idx % 4;
+  }
+  // convolution gather: the column (tap, channel) of a slot is fixed; the pixel (b, y, x) of its first k is carried from K-tile to K-tile
+  // (divisions only here)
+  int cv_c[CONVB ? EB : 1], cv_dy[CONVB ? EB : 1], cv_dx[CONVB ? EB : 1], cv_b[CONVB ? EB : 1], cv_y[CONVB ? EB : 1], cv_x[CONVB ? EB : 1];
+  if (CONVB) {
+#pragma unroll
+    for (int e = 0; e < EB; ++e) {
+      const int gn = n0 + bnl[e];
+      const int tap = gn < p.N ? gn / p.conv_C : 0;
+      cv_c[e] = gn - tap * p.conv_C;
+      cv_dy[e] = tap / 3 - 1;
+      cv_dx[e] = tap - (tap / 3) * 3 - 1;
+      const int gk = kb + 8 * bq[e];
+      cv_b[e] = gk / HW;
+      const int rem = gk - cv_b[e] * HW;
+      cv_y[e] = rem / p.W;
+      cv_x[e] = rem - cv_y[e] * p.W;
+    }
+  }
+
+  // global -> registers (fp32, not yet rounded: the loads of K-tile t + 1 stay in flight while tile t is multiplied)
+  float fa[EA][8], fb[EB][8];
+  auto gload = [&](const int k0) {
+#pragma unroll
+    for (int e = 0; e < EA; ++e) {
+      const int gm = m0 + ar[e], gk = k0 + 8 * aq[e];
+      if (!AMC && vec_a && gm < p.M && gk + 8 <= ke) {
+        const float4* src = (const float4*)(A + (long)gm * p.sAm + gk);
+        const float4 x = src[0], y = src[1];
+        fa[e][0] = x.x; fa[e][1] = x.y; fa[e][2] = x.z; fa[e][3] = x.w; fa[e][4] = y.x; fa[e][5] = y.y; fa[e][6] = y.z; fa[e][7] = y.w;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) fa[e][j] = (gm < p.M && gk + j < ke) ? A[(long)gm * p.sAm + (long)(gk + j) * p.sAk] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < EB; ++e) {
+      const int gn = n0 + bnl[e], gk = k0 + 8 * bq[e];
+      if (CONVB) {
+        // B(k = output pixel, n = tap conv_C + c) = X[pixel + offset(tap)][c], zero outside the map
+        const int sy = cv_y[e] + cv_dy[e], sx = cv_x[e] + cv_dx[e];
+        const bool ok = gn < p.N && gk + 8 <= ke;
+        if (ok && cv_x[e] + 8 <= p.W && sy >= 0 && sy < p.H && sx >= 0 && sx + 8 <= p.W) {
+          // the 8 pixels lie in one row, inside the map: plain strided loads
+          const float* src = B + ((long)(cv_b[e] * p.H + sy) * p.W + sx) * p.ldx + cv_c[e];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) fb[e][j] = src[(long)j * p.ldx];
+        } else {
+          int b = cv_b[e], y = cv_y[e], x = cv_x[e];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const int yy = y + cv_dy[e], xx = x + cv_dx[e];
+            fb[e][j] = (gn < p.N && gk + j < ke && yy >= 0 && yy < p.H && xx >= 0 && xx < p.W)
+                           ? B[((long)(b * p.H + yy) * p.W + xx) * p.ldx + cv_c[e]] : 0.f;
+            if (++x == p.W) { x = 0; if (++y == p.H) { y = 0; ++b; } }
+          }
+        }
+        cv_x[e] += BK;                      // the first pixel this slot stages in the next K-tile
+        while (cv_x[e] >= p.W) { cv_x[e] -= p.W; if (++cv_y[e] == p.H) { cv_y[e] = 0; ++cv_b[e]; } }
+      } else if (!BNC && vec_b && gn < p.N && gk + 8 <= ke) {
+        const float4* src = (const float4*)(B + gk + (long)gn * p.sBn);
+        const float4 x = src[0], y = src[1];
+        fb[e][0] = x.x; fb[e][1] = x.y; fb[e][2] = x.z; fb[e][3] = x.w; fb[e][4] = y.x; fb[e][5] = y.y; fb[e][6] = y.z; fb[e][7] = y.w;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) fb[e][j] = (gn < p.N && gk + j < ke) ? B[(long)(gk + j) * p.sBk + (long)gn * p.sBn] : 0.f;
+      }
+    }
+  };
+
+  if (kb < ke) gload(kb);
+  for (int k0 = kb; k0 < ke; k0 += BK) {
+    uint4 ra[EA], rb[EB];
+#pragma unroll
+    for (int e = 0; e < EA; ++e) ra[e] = tg_pack8<TC>(fa[e]);
+#pragma unroll
+    for (int e = 0; e < EB; ++e) rb[e] = tg_pack8<TC>(fb[e]);
+    __syncthreads();     // the previous K-tile has been consumed
+#pragma unroll
+    for (int e = 0; e < EA; ++e) *(uint4*)&As[ar[e] * LDK + 8 * aq[e]] = ra[e];
+#pragma unroll
+    for (int e = 0; e < EB; ++e) *(uint4*)&Bs[bnl[e] * LDK + 8 * bq[e]] = rb[e];
+    __syncthreads();
+    if (k0 + BK < ke) gload(k0 + BK);
+#pragma unroll
+    for (int s = 0; s < BK / 16; ++s) {
+      uint4 af[TM], bf[TN];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) af[i] = *(const uint4*)&As[(wm * (BM / 2) + i * 32 + lr) * LDK + 16 * s + 8 * lh];
+#pragma unroll
+      for (int j = 0; j < TN; ++j) bf[j] = *(const uint4*)&Bs[(wn * (BN / 2) + j * 32 + lr) * LDK + 16 * s + 8 * lh];
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) tg_mma16<TC>(af[i], bf[j], acc[i][j]);
+    }
+  }
+
+  float* C = p.C + (long)z0 * p.sCz0 + (long)z1 * p.sCz1;
+  float* part = p.ksplit > 1 ? ws + ((long)ks * p.nz0 * p.nz1 + (long)z0 * p.nz1 + z1) * p.M * p.N : nullptr;
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      const int row = m0 + wm * (BM / 2) + i * 32 + (v & 3) + 8 * (v >> 2) + 4 * lh;
+      if (row >= p.M) continue;
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        const int col = n0 + wn * (BN / 2) + j * 32 + lr;
+        if (col >= p.N) continue;
+        if (part) {
+          part[(long)row * p.N + col] = acc[i][j][v];
+        } else {
+          float val = p.alpha * acc[i][j][v];
+          float* dst = C + (long)row * p.ldc + col;
+          if (p.bias_n) val += p.bias_n[col];
+          if (p.beta != 0.f) val += p.beta * *dst;
+          *dst = val;
+        }
+      }
+    }
+}
+
+// C = alpha (sum over ks of the partial tiles, in ks order) + bias_n + beta C
+__global__ __launch_bounds__(256) void tgemm16_reduce_kernel(const TGemmArgs p, const float* __restrict__ ws, const int ksplit) {
+  const long MN = (long)p.M * p.N, total = MN * p.nz0 * p.nz1;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    float s = 0.f;
+    for (int k = 0; k < ksplit; ++k) s += ws[k * total + i];
+    const long z = i / MN, e = i - z * MN;
+    const int row = (int)(e / p.N), col = (int)(e - (long)row * p.N);
+    const int z0 = (int)(z / p.nz1), z1 = (int)(z - (long)z0 * p.nz1);
+    float* dst = p.C + (long)z0 * p.sCz0 + (long)z1 * p.sCz1 + (long)row * p.ldc + col;
+    float val = p.alpha * s;
+    if (p.bias_n) val += p.bias_n[col];
+    if (p.beta != 0.f) val += p.beta * *dst;
+    *dst = val;
+  }
+}
+
+// tile edge and K split of a 16-bit launch: the f32 rule with the 32-deep K-tile
+static void tgemm16_plan(const TGemmArgs& a, int* bt, int* ksplit) {
+  const long nz = (long)a.nz0 * a.nz1;
+  const long tiles128 = (long)cdiv_l(a.M, 128) * cdiv_l(a.N, 128) * nz;
+  const bool big = a.M >= 128 && a.N >= 128 && (tiles128 >= 128 || (a.ksplit == 0 && tiles128 * (a.K / 256) >= 128));
+  *bt = big ? 128 : 64;
+  int ks = a.ksplit;
+  if (ks == 0) {
+    const long tiles = (long)cdiv_l(a.M, *bt) * cdiv_l(a.N, *bt) * nz;
+    ks = (int)std::max<long>(1, std::min<long>(512 / std::max<long>(tiles, 1), a.K / 256));
+  }
+  *ksplit = ks;
+}
+
+long tgemm16_ws_floats(const TGemmArgs& a) {
+  int bt = 0, ks = 1;
+  tgemm16_plan(a, &bt, &ks);
+  return ks > 1 ? (long)ks * a.nz0 * a.nz1 * a.M * a.N : 0;
+}
+
+template <typename TC, int BT, bool AMC, bool BNC, bool CONVB>
+static int tgemm16_launch_t(const TGemmArgs& a, int ksplit, float* ws, int vec_a, int vec_b, hipStream_t s) {
+  TGemmArgs p = a;
+  p.ksplit = ksplit;
+  int kper = (a.K + ksplit - 1) / ksplit;
+  kper = (kper + 31) / 32 * 32;
+  dim3 grid(cdiv_l(a.N, BT), cdiv_l(a.M, BT), a.nz0 * a.nz1 * ksplit);
+  hipLaunchKernelGGL((tgemm16_kernel<TC, BT, BT, AMC, BNC, CONVB>), grid, dim3(256), 0, s, p, kper, ws, vec_a, vec_b);
+  T2P_HIP_CHECK(hipGetLastError());
+  if (ksplit > 1) {
+    const long total = (long)a.M * a.N * a.nz0 * a.nz1;
+    hipLaunchKernelGGL(tgemm16_reduce_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, p, (const float*)ws, ksplit);
+    T2P_HIP_CHECK(hipGetLastError());
+  }
+  return T2P_OK;
+}
+
+template <typename TC>
+static int tgemm16_dispatch(const TGemmArgs& a, int bt, int ksplit, float* ws, int vec_a, int vec_b, hipStream_t s) {
+  const bool amc = a.sAm == 1, bnc = a.sBn == 1;
+  if (a.conv_b)
+    return bt == 128 ? tgemm16_launch_t<TC, 128, true, true, true>(a, ksplit, ws, 0, 0, s)
+                     : tgemm16_launch_t<TC, 64, true, true, true>(a, ksplit, ws, 0, 0, s);
+#define T2P_TG16(AM, BN_)                                                                                   \
+  if (amc == AM && bnc == BN_)                                                                              \
+    return bt == 128 ? tgemm16_launch_t<TC, 128, AM, BN_, false>(a, ksplit, ws, vec_a, vec_b, s)            \
+                     : tgemm16_launch_t<TC, 64, AM, BN_, false>(a, ksplit, ws, vec_a, vec_b, s);
+  T2P_TG16(true, true) T2P_TG16(true, false) T2P_TG16(false, true) T2P_TG16(false, false)
+#undef T2P_TG16
+  return T2P_ERR_INVALID;
+}
+
+int launch_tgemm16(const TGemmArgs& a, int dtype, float* ws, hipStream_t s) {
+  T2P_REQUIRE(dtype == DT_F16 || dtype == DT_BF16, "tgemm16: dtype must be f16 or bf16");
+  T2P_REQUIRE(a.A && a.B && a.C && a.M > 0 && a.N > 0 && a.K > 0 && a.nz0 >= 1 && a.nz1 >= 1, "tgemm operands");
+  T2P_REQUIRE(a.sAm == 1 || a.sAk == 1, "tgemm: A must be a row- or column-major view");
+  T2P_REQUIRE(a.conv_b || a.sBn == 1 || a.sBk == 1, "tgemm: B must be a row- or column-major view");
+  T2P_REQUIRE(a.ldc >= a.N, "tgemm: ldc");
+  if (a.conv_b) T2P_REQUIRE(a.H > 0 && a.W > 0 && a.conv_C > 0 && a.N == 9 * a.conv_C && a.K % (a.H * a.W) == 0 && a.ldx >= a.conv_C,
+                            "tgemm: convolution gather shapes");
+  if (a.conv_b) T2P_REQUIRE(a.sAm == 1, "tgemm: the convolution weight gradient takes dY^T (column-major view) as A");
+  const long nz = (long)a.nz0 * a.nz1;
+  T2P_REQUIRE(nz <= 65535, "tgemm: batch count");
+  int bt = 64, ksplit = 1;
+  tgemm16_plan(a, &bt, &ksplit);
+  T2P_REQUIRE(ksplit >= 1 && nz * ksplit <= 65535, "tgemm: ksplit");
+  T2P_REQUIRE(ksplit == 1 || ws, "tgemm16: a split-K launch needs its workspace (tgemm16_ws_floats)");
+  T2P_REQUIRE((long)ksplit * nz * a.M * a.N < (1L << 40), "tgemm16: workspace size");
+  // two float4 per staged k-group: the k-contiguous operand rows must start on 16 bytes
+  auto aligned = [](const float* p, long s1, long s2, long s3) {
+    return ((uintptr_t)p % 16) == 0 && s1 % 4 == 0 && s2 % 4 == 0 && s3 % 4 == 0;
+  };
+  const int vec_a = a.sAk == 1 && aligned(a.A, a.sAm, a.sAz0, a.sAz1);
+  const int vec_b = !a.conv_b && a.sBk == 1 && aligned(a.B, a.sBn, a.sBz0, a.sBz1);
+  return dtype == DT_F16 ? tgemm16_dispatch<f16_t>(a, bt, ksplit, ws, vec_a, vec_b, s)
+                         : tgemm16_dispatch<bf16_t>(a, bt, ksplit, ws, vec_a, vec_b, s);
+}
+
+// =====================================================================================================================================
 // reductions shared below
 // =====================================================================================================================================
 __device__ inline float wave_sum(float v) {
@@ -265,6 +564,7 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const float* __rest
 }
 
 // per sample: fold the chunks -> sums [B][C][2], group sums gs [B][G][2] = (sum gamma dv, sum gamma dv n); dgamma / dbeta += over the batch
+template <bool ATOMIC>   // false: dgamma / dbeta are left to gn_bwd_param_sum_kernel (fixed order over the batch)
 __global__ __launch_bounds__(256) void gn_bwd_finalize_kernel(const float* __restrict__ partial, const float* __restrict__ gamma,
                                                               const int nchunk, const int C, const int G, float* __restrict__ sums,
                                                               float* __restrict__ gs, float* __restrict__ dgamma, float* __restrict__ dbeta) {
@@ -277,8 +577,10 @@ __global__ __launch_bounds__(256) void gn_bwd_finalize_kernel(const float* __res
     }
     sums[((long)b * C + c) * 2] = a;
     sums[((long)b * C + c) * 2 + 1] = bq;
-    unsafeAtomicAdd(dbeta + c, a);
-    unsafeAtomicAdd(dgamma + c, bq);
+    if (ATOMIC) {
+      unsafeAtomicAdd(dbeta + c, a);
+      unsafeAtomicAdd(dgamma + c, bq);
+    }
   }
   __syncthreads();
   for (int g = tid; g < G; g += 256) {
@@ -329,7 +631,33 @@ int launch_gn_backward(const float* x, const float* dy, const float* stats, cons
   float* sums = partial + (long)B * nchunk * C * 2;
   float* gs = sums + (long)B * C * 2;
   hipLaunchKernelGGL(gn_bwd_partial_kernel, dim3(nchunk, B), dim3(256), 0, s, x, dy, stats, gamma, beta, silu, HW, C, G, partial);
-  hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(B), dim3(256), 0, s, partial, gamma, nchunk, C, G, sums, gs, dgamma, dbeta);
+  hipLaunchKernelGGL(gn_bwd_finalize_kernel<true>, dim3(B), dim3(256), 0, s, partial, gamma, nchunk, C, G, sums, gs, dgamma, dbeta);
+  const long total = (long)B * HW * C;
+  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, x, dy, stats, gamma, beta, silu, HW, C, G, gs, dx, total);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+
+__global__ __launch_bounds__(256) void gn_bwd_param_sum_kernel(const float* __restrict__ sums, const int B, const int C, float* __restrict__ dgamma,
+                                                               float* __restrict__ dbeta) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  float a = 0.f, bq = 0.f;
+  for (int b = 0; b < B; ++b) { a += sums[((long)b * C + c) * 2]; bq += sums[((long)b * C + c) * 2 + 1]; }
+  dbeta[c] += a;
+  dgamma[c] += bq;
+}
+int launch_gn_backward_fixed(const float* x, const float* dy, const float* stats, const float* gamma, const float* beta, int silu,
+                             int B, int HW, int C, int G, float* dx, float* dgamma, float* dbeta, float* ws, hipStream_t s) {
+  T2P_REQUIRE(x && dy && stats && gamma && beta && dx && dgamma && dbeta && ws, "gn_backward pointers");
+  T2P_REQUIRE(B > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0 && B <= 65535, "gn_backward shapes");
+  const int nchunk = (HW + GN_CHUNK - 1) / GN_CHUNK;
+  float* partial = ws;
+  float* sums = partial + (long)B * nchunk * C * 2;
+  float* gs = sums + (long)B * C * 2;
+  hipLaunchKernelGGL(gn_bwd_partial_kernel, dim3(nchunk, B), dim3(256), 0, s, x, dy, stats, gamma, beta, silu, HW, C, G, partial);
+  hipLaunchKernelGGL(gn_bwd_finalize_kernel<false>, dim3(B), dim3(256), 0, s, partial, gamma, nchunk, C, G, sums, gs, dgamma, dbeta);
+  hipLaunchKernelGGL(gn_bwd_param_sum_kernel, dim3(cdiv_l(C, 256)), dim3(256), 0, s, (const float*)sums, B, C, dgamma, dbeta);
   const long total = (long)B * HW * C;
   hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, x, dy, stats, gamma, beta, silu, HW, C, G, gs, dx, total);
   T2P_HIP_CHECK(hipGetLastError());
@@ -385,6 +713,75 @@ int launch_ln_backward(const float* x, const float* dy, const float* gamma, long
                        float* dbeta, hipStream_t s) {
   T2P_REQUIRE(x && dy && gamma && dx && dgamma && dbeta && rows > 0 && C > 0 && C <= 8192, "ln_backward arguments");
   hipLaunchKernelGGL(ln_bwd_kernel, dim3(cdiv_l(rows, LN_ROWS)), dim3(256), 2 * C * sizeof(float), s, x, dy, gamma, rows, C, eps, dx, dgamma, dbeta);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+
+// the same in a fixed summation order (mixed-precision step, which is bitwise reproducible): pass 1 = one wavefront per row, dx and the
+// row's (mean, rstd); pass 2 = per chunk of LN_COL_ROWS rows one thread per channel sums d gamma / d beta in row order; pass 3 adds the
+// chunks in order
+constexpr int LN_COL_ROWS = 256;
+__global__ __launch_bounds__(256) void ln_bwd_rows_kernel(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ gamma,
+                                                          const long rows, const int C, const float eps, float* __restrict__ dx,
+                                                          float* __restrict__ stats) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const float inv_c = 1.f / C;
+  const float* xr = x + r * C;
+  const float* dr = dy + r * C;
+  float sum = 0.f;
+  for (int c = lane; c < C; c += 64) sum += xr[c];
+  const float mean = wave_sum(sum) * inv_c;
+  float var = 0.f;
+  for (int c = lane; c < C; c += 64) { const float d = xr[c] - mean; var += d * d; }
+  const float rstd = rsqrtf(wave_sum(var) * inv_c + eps);
+  float c1 = 0.f, c2 = 0.f;
+  for (int c = lane; c < C; c += 64) {
+    const float n = (xr[c] - mean) * rstd, dg = dr[c] * gamma[c];
+    c1 += dg; c2 += dg * n;
+  }
+  c1 = wave_sum(c1) * inv_c; c2 = wave_sum(c2) * inv_c;
+  for (int c = lane; c < C; c += 64) {
+    const float n = (xr[c] - mean) * rstd;
+    dx[r * C + c] += rstd * (dr[c] * gamma[c] - c1 - n * c2);
+  }
+  if (lane == 0) { stats[2 * r] = mean; stats[2 * r + 1] = rstd; }
+}
+__global__ __launch_bounds__(256) void ln_bwd_cols_kernel(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ stats,
+                                                          const long rows, const int C, float* __restrict__ partial) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  const long r0 = (long)blockIdx.y * LN_COL_ROWS, r1 = min(rows, r0 + LN_COL_ROWS);
+  float g = 0.f, b = 0.f;
+  for (long r = r0; r < r1; ++r) {
+    const float d = dy[r * C + c];
+    g += d * ((x[r * C + c] - stats[2 * r]) * stats[2 * r + 1]);
+    b += d;
+  }
+  partial[(long)blockIdx.y * 2 * C + c] = g;
+  partial[(long)blockIdx.y * 2 * C + C + c] = b;
+}
+__global__ __launch_bounds__(256) void ln_bwd_cols_finish_kernel(const float* __restrict__ partial, const int nchunk, const int C,
+                                                                 float* __restrict__ dgamma, float* __restrict__ dbeta) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  float g = 0.f, b = 0.f;
+  for (int k = 0; k < nchunk; ++k) { g += partial[(long)k * 2 * C + c]; b += partial[(long)k * 2 * C + C + c]; }
+  dgamma[c] += g;
+  dbeta[c] += b;
+}
+long ln_bwd_fixed_ws_floats(long rows, int C) { return 2 * rows + 2L * C * cdiv_l(rows, LN_COL_ROWS); }
+int launch_ln_backward_fixed(const float* x, const float* dy, const float* gamma, long rows, int C, float eps, float* dx, float* dgamma,
+                             float* dbeta, float* ws, hipStream_t s) {
+  T2P_REQUIRE(x && dy && gamma && dx && dgamma && dbeta && ws && rows > 0 && C > 0, "ln_backward arguments");
+  const int nchunk = cdiv_l(rows, LN_COL_ROWS);
+  T2P_REQUIRE(nchunk <= 65535, "ln_backward rows");
+  float* stats = ws;
+  float* partial = ws + 2 * rows;
+  hipLaunchKernelGGL(ln_bwd_rows_kernel, dim3(cdiv_l(rows, 4)), dim3(256), 0, s, x, dy, gamma, rows, C, eps, dx, stats);
+  hipLaunchKernelGGL(ln_bwd_cols_kernel, dim3(cdiv_l(C, 256), nchunk), dim3(256), 0, s, x, dy, (const float*)stats, rows, C, partial);
+  hipLaunchKernelGGL(ln_bwd_cols_finish_kernel, dim3(cdiv_l(C, 256)), dim3(256), 0, s, (const float*)partial, nchunk, C, dgamma, dbeta);
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }
@@ -498,6 +895,48 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ d
   red[rl][cl] = a;
   __syncthreads();
   if (rl == 0 && n < N) unsafeAtomicAdd(out + (long)z * ld_out + n, red[0][cl] + red[1][cl] + red[2][cl] + red[3][cl]);
+}
+// fixed-order form: the block sums of colsum_kernel go to ws [z][chunk][N], colsum_finish_kernel adds the chunks in order
+__global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __restrict__ dy, const long rows_per_z, const int N, const long ld,
+                                                             float* __restrict__ ws, const int rows_per_block) {
+  __shared__ float red[4][64];
+  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
+  const int n = blockIdx.x * 64 + cl, z = blockIdx.z;
+  const long r0 = (long)blockIdx.y * rows_per_block, r1 = min(rows_per_z, r0 + rows_per_block);
+  float a = 0.f;
+  if (n < N)
+    for (long r = r0 + rl; r < r1; r += 4) a += dy[((long)z * rows_per_z + r) * ld + n];
+  red[rl][cl] = a;
+  __syncthreads();
+  if (rl == 0 && n < N) ws[((long)z * gridDim.y + blockIdx.y) * N + n] = red[0][cl] + red[1][cl] + red[2][cl] + red[3][cl];
+}
+// 64 columns x 4 row lanes per block: lane l adds chunks l, l + 4, ... in order, then the four lane sums are added in lane order
+__global__ __launch_bounds__(256) void colsum_finish_kernel(const float* __restrict__ ws, const int nchunk, const int N, float* __restrict__ out,
+                                                            const long ld_out, const int accumulate) {
+  __shared__ float red[4][64];
+  const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
+  const int n = blockIdx.x * 64 + cl, z = blockIdx.y;
+  float a = 0.f;
+  if (n < N)
+    for (int k = rl; k < nchunk; k += 4) a += ws[((long)z * nchunk + k) * N + n];
+  red[rl][cl] = a;
+  __syncthreads();
+  if (rl == 0 && n < N) {
+    const float t = ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
+    float* o = out + (long)z * ld_out + n;
+    *o = accumulate ? *o + t : t;
+  }
+}
+long colsum_fixed_ws_floats(int nz, long rows_per_z, int N) { return (long)nz * cdiv_l(rows_per_z, 256) * N; }
+int launch_colsum_fixed(const float* dy, int nz, long rows_per_z, int N, long ld, float* out, long ld_out, int accumulate, float* ws,
+                        hipStream_t s) {
+  T2P_REQUIRE(dy && out && ws && nz > 0 && nz <= 65535 && rows_per_z > 0 && N > 0 && ld >= N && ld_out >= N, "colsum arguments");
+  const int rpb = 256, nchunk = cdiv_l(rows_per_z, rpb);
+  T2P_REQUIRE(nchunk <= 65535, "colsum rows");
+  hipLaunchKernelGGL(colsum_partial_kernel, dim3(cdiv_l(N, 64), nchunk, nz), dim3(256), 0, s, dy, rows_per_z, N, ld, ws, rpb);
+  hipLaunchKernelGGL(colsum_finish_kernel, dim3(cdiv_l(N, 64), nz), dim3(256), 0, s, (const float*)ws, nchunk, N, out, ld_out, accumulate);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
 }
 int launch_colsum(const float* dy, long rows, int N, long ld, float* out, hipStream_t s) {
   T2P_REQUIRE(dy && out && rows > 0 && N > 0 && ld >= N, "colsum arguments");
@@ -791,6 +1230,30 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
   a = block_sum_256_d(a, sh);
   if (threadIdx.x == 0) unsafeAtomicAdd(out, a);
 }
+// fixed order: one partial per block (SUMSQ_BLOCKS of them), then one block adds the partials
+constexpr int SUMSQ_BLOCKS = 1024;
+__global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ g, const long n, double* __restrict__ partial) {
+  __shared__ double sh[4];
+  double a = 0.0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) { const float v = g[i]; a += (double)v * v; }
+  a = block_sum_256_d(a, sh);
+  if (threadIdx.x == 0) partial[blockIdx.x] = a;
+}
+__global__ __launch_bounds__(256) void sumsq_finish_kernel(const double* __restrict__ partial, const int np, double* __restrict__ out) {
+  __shared__ double sh[4];
+  double a = 0.0;
+  for (int i = threadIdx.x; i < np; i += 256) a += partial[i];
+  a = block_sum_256_d(a, sh);
+  if (threadIdx.x == 0) *out = a;
+}
+int launch_sumsq_fixed(const float* g, long n, double* partial, double* out, hipStream_t s) {
+  T2P_REQUIRE(g && partial && out && n > 0, "sumsq arguments");
+  const int nb = grid_for(n, 256, SUMSQ_BLOCKS);
+  hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nb), dim3(256), 0, s, g, n, partial);
+  hipLaunchKernelGGL(sumsq_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, nb, out);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
 int launch_sumsq(const float* g, long n, double* out, hipStream_t s) {
   T2P_REQUIRE(g && out && n > 0, "sumsq arguments");
   hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for(n, 256, 1024)), dim3(256), 0, s, g, n, out);
@@ -825,6 +1288,16 @@ __global__ __launch_bounds__(256) void ema_kernel(float* __restrict__ shadow, co
 int launch_ema(float* shadow, const float* p, float one_minus_decay, long n, hipStream_t s) {
   T2P_REQUIRE(shadow && p && n > 0, "ema arguments");
   hipLaunchKernelGGL(ema_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, s, shadow, p, one_minus_decay, n);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+
+__global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ x, const float a, const long n) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) x[i] *= a;
+}
+int launch_scale(float* x, float a, long n, hipStream_t s) {
+  T2P_REQUIRE(x && n > 0, "scale arguments");
+  hipLaunchKernelGGL(scale_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, s, x, a, n);
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }

@@ -1,5 +1,6 @@
 """Training step on MI355X: Python mirror of the reference's ``score_sde_pytorch/losses.py`` over the C ABI
-(``t2p_train_*``, include/t2p.h).  First slice of SURVEY.md 8(f)4: fp32 arithmetic, VE SDE.
+(``t2p_train_*``, include/t2p.h).  SURVEY.md 8(f)4, VE SDE: exact-f32 products, or (``dtype="f16"`` / ``"bf16"``) 16-bit
+products with fp32 accumulation and fp32 parameters, gradients, optimizer state, EMA and loss.
 
 The reference keeps four objects in ``state`` -- ``model`` (DataParallel(UNetModel)), ``optimizer`` (torch Adam),
 ``ema`` (ExponentialMovingAverage) and ``step`` (train.py:118-124) -- and ``step_fn`` (losses.py:165-176) drives them:
@@ -45,16 +46,23 @@ def condition_flags(condition) -> int:
 
 
 class HipTrainModel:
-    """The score network in training form: ``UNetModel`` + its optimizer state + its EMA, resident on one GPU."""
+    """The score network in training form: ``UNetModel`` + its optimizer state + its EMA, resident on one GPU.
 
-    def __init__(self, config, device="cuda:0", seed=0):
+    ``dtype`` ("f32" | "f16" | "bf16", the names of ``HipScoreModel``) is the compute dtype of the products.  Whatever it is, the
+    parameters, gradients, Adam moments, EMA and checkpoints are fp32 and laid out identically.  In the 16-bit modes a step whose
+    loss or gradient norm is not finite raises ``T2PError`` and changes nothing (mixed-precision training's skipped step)."""
+
+    def __init__(self, config, device="cuda:0", seed=0, dtype="f32"):
+        if not isinstance(dtype, str) or dtype not in _lib.DTYPE_NAMES:
+            raise ValueError(f"unknown compute dtype {dtype!r}: one of {sorted(_lib.DTYPE_NAMES)}")
         self.config = config
+        self.dtype = dtype
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise T2PError("HipTrainModel needs a GPU device (there is no CPU fallback)")
         self.lib = _lib.load()
         torch.cuda.set_device(self.device)
-        self._mc = _model_config(config, "f32")
+        self._mc = _model_config(config, dtype)
         o, m = config.optim, config.model
         if o.optimizer != "Adam":
             raise NotImplementedError(f"Optimizer {o.optimizer} not supported yet!")          # losses.py:32-34
@@ -229,9 +237,9 @@ class _ParamHandle:
         self.model = model
 
 
-def get_train_model(config, seed=0):
+def get_train_model(config, seed=0, dtype="f32"):
     """``utils.get_model(config)`` (score_sde_pytorch/utils.py:4-9) for training: no DataParallel, one process per GPU."""
-    return HipTrainModel(config, device=config.device if str(config.device) != "cuda" else "cuda:0", seed=seed)
+    return HipTrainModel(config, device=config.device if str(config.device) != "cuda" else "cuda:0", seed=seed, dtype=dtype)
 
 
 class AdamView:
@@ -373,15 +381,24 @@ def get_step_fn(sde, train, optimize_fn=None, dist=None):
         if train:
             if optimize_fn is not None:
                 optimize_fn(state["optimizer"], model.parameters(), step=state["step"])
+            prev = model.get_step()
             model.set_step(state["step"])
             if world == 1:
-                loss = model.step(batch, t=t, z=z)                # zero_grad, loss, backward, optimize_fn, ema.update
+                try:
+                    loss = model.step(batch, t=t, z=z)            # zero_grad, loss, backward, optimize_fn, ema.update
+                except T2PError:
+                    model.set_step(*prev)                         # a refused 16-bit step leaves the counters as they were
+                    raise
             else:
                 from . import distributed as D
                 loss = model.loss(batch, t=t, z=z, backward=True)
                 D.allreduce_mean_(model.grad_view(), dist)        # one collective over the whole gradient
                 loss = D.mean_over_ranks(loss, dist, model.device)
-                model.apply()
+                try:
+                    model.apply()
+                except T2PError:
+                    model.set_step(*prev)                         # as above: a refused 16-bit step leaves the counters as they were
+                    raise
             state["step"] += 1
             return loss
         return model.eval_loss(batch, t=t, z=z)                  # ema.store / copy_to / loss / restore (losses.py:177-183)

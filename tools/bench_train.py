@@ -1,9 +1,9 @@
-"""Time the training step (t2p_train_step: loss + backward + Adam + EMA, fp32) at a BASELINE model size.
+"""Time the training step (t2p_train_step: loss + backward + Adam + EMA) at a BASELINE model size.
 
-    python tools/bench_train.py --config cond_length.yml --batch 8 --steps 5 [--tokens 64] [--dropout 0.1]
+    python tools/bench_train.py --config cond_length.yml --batch 8 --steps 5 [--tokens 64] [--dropout 0.1] [--dtype f32|f16|bf16]
 
-Prints one JSON line: ms per step, samples/s, the loss sequence, device memory, and the achieved fp32 matrix rate against the
-157.3 TFLOP/s f32 MFMA peak, counting a step as 3 x the forward pass AS EXECUTED (the text K / V projections are inside a training
+Prints one JSON line: ms per step, samples/s, the loss sequence, device memory, and the achieved matrix rate against the peak of the
+compute dtype's MFMA (157.3 TFLOP/s f32, 2500 TFLOP/s f16 / bf16), counting a step as 3 x the forward pass AS EXECUTED (the text K / V projections are inside a training
 step: the context changes with every batch).  Measurement tool, not part of the product path or of bench.py's headline."""
 import argparse
 import json
@@ -17,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+PEAK_TFLOPS = {"f32": 157.3, "f16": 2500.0, "bf16": 2500.0}
 FWD_GFLOP = {"test_config.yml": 714.0, "cond_length.yml": 151.2, "cond_length_inpainting.yml": 151.4, "test_config_large.yml": 3099.6}   # SURVEY 8(d), L = 128 / 256, T = 512
 
 
@@ -29,6 +30,7 @@ def main():
     ap.add_argument("--tokens", type=int, default=512)
     ap.add_argument("--L", type=int, default=0)
     ap.add_argument("--dropout", type=float, default=-1.0)
+    ap.add_argument("--dtype", default="f32", choices=sorted(PEAK_TFLOPS))
     a = ap.parse_args()
     from text2protein_amd import losses, sde_lib, synth
     from text2protein_amd.config import load_config
@@ -41,7 +43,7 @@ def main():
         cfg.optim = dict(optimizer="Adam", lr=1e-4, beta1=0.9, eps=1e-8, weight_decay=0, warmup=5000, grad_clip=1.0)
     cfg.model.setdefault("ema_rate", 0.999)
     cfg.model.setdefault("dropout", 0.1)
-    model = losses.HipTrainModel(cfg, device="cuda:0", seed=1)
+    model = losses.HipTrainModel(cfg, device="cuda:0", seed=1, dtype=a.dtype)
     model.load_state_dict(synth.synth_state_dict(cfg, 0))
     B, C, L = a.batch, cfg.data.num_channels, cfg.data.max_res_num
     x = torch.from_numpy(synth.uniform_pm1(1, "bench_train_x", B * C * L * L).reshape(B, C, L, L))
@@ -66,9 +68,14 @@ def main():
     torch.cuda.synchronize()
     dt = (time.time() - t0) / a.steps
     gf = FWD_GFLOP.get(a.config, 0.0) * 3 * B
-    print(json.dumps({"metric": "training step (fp32)", "config": a.config, "batch": B, "L": L, "tokens": a.tokens, "ms_per_step": dt * 1e3,
-                      "samples_per_s": B / dt, "losses": [round(v, 5) for v in seq], "device_GiB": model.device_bytes() / 2 ** 30,
-                      "tflops_f32": gf / dt / 1e3, "frac_of_f32_peak": gf / dt / 1e3 / 157.3, "dropout": float(cfg.model.dropout)}))
+    out = {"metric": f"training step ({'fp32' if a.dtype == 'f32' else a.dtype})", "dtype": a.dtype, "config": a.config, "batch": B, "L": L,
+           "tokens": a.tokens, "ms_per_step": dt * 1e3, "samples_per_s": B / dt, "losses": [round(v, 5) for v in seq],
+           "device_GiB": model.device_bytes() / 2 ** 30}
+    tf = gf / dt / 1e3
+    if a.dtype == "f32":
+        out.update(tflops_f32=tf, frac_of_f32_peak=tf / PEAK_TFLOPS["f32"])
+    out.update(tflops=tf, peak_tflops=PEAK_TFLOPS[a.dtype], frac_of_peak=tf / PEAK_TFLOPS[a.dtype], dropout=float(cfg.model.dropout))
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":
