@@ -23,6 +23,7 @@ extern "C" {
 
 #define T2P_SDE_VE 0
 #define T2P_SDE_VP 1
+#define T2P_SDE_SUBVP 2   /* training step only (t2p_train_set_sde) */
 
 /* Flat view of the YAML keys the score network reads
  * (reference score_sde_pytorch/models/ncsnpp.py:74-217, configs/test_config.yml). */
@@ -153,7 +154,7 @@ int t2p_sampler_run(t2p_sampler* s, float* x, float* out, int prior_given, int n
  * on `stream` (not the default stream) and discarded, nothing executes; call after at least one eager step */
 int t2p_sampler_count_dispatches(t2p_sampler* s, float* x, float* x_mean, void* stream, int* n_out);
 
-/* ---- training step (VE SDE) ------------------------------------------------------
+/* ---- training step ---------------------------------------------------------------
  * model->compute_dtype selects the products: T2P_DTYPE_F32 exact f32; T2P_DTYPE_F16 / T2P_DTYPE_BF16 16-bit operands with fp32
  * accumulation (residual-block 3x3 convolutions on the 16-bit implicit GEMM, every other product on t2p_op_tgemm16; input / head
  * convolutions, norms, softmax and elementwise work stay fp32).  Parameters, gradients, Adam moments, EMA and loss are fp32 in every
@@ -164,6 +165,7 @@ int t2p_sampler_count_dispatches(t2p_sampler* s, float* x, float* x_mean, void* 
  * gradient norm is not finite.
  * t2p_train_create      <- get_model + get_optimizer + ExponentialMovingAverage(model.parameters(), decay)
  *                          (score_sde_pytorch/utils.py:4-9, losses.py:26-36, models/ema.py:13-30; train.py builds `state` from them)
+ * t2p_train_set_sde     <- the `sde` of get_sde_loss_fn / get_step_fn (losses.py:66,140): VE (the default), VP or sub-VP
  * t2p_train_load_param  <- load_state_dict of one tensor; the EMA shadow starts as a copy (ema.py:28-29)
  * t2p_train_loss        <- loss_fn(model, batch, condition)      (losses.py:105-134), optionally with loss.backward()
  * t2p_train_step        <- step_fn(state, batch, condition), train=True (losses.py:165-176): zero_grad, loss, backward,
@@ -205,6 +207,15 @@ int t2p_train_write(t2p_trainer* t, int which, const char* name, const float* ho
 /* state['step'] (drives the warm-up), the optimizer's own update count (Adam bias correction) and ema.num_updates */
 int t2p_train_set_step(t2p_trainer* t, int64_t step, int64_t adam_updates, int64_t ema_updates);
 int t2p_train_get_step(const t2p_trainer* t, int64_t out3[3]);
+/* SDE of the loss (get_sde_loss_fn's `sde`, losses.py:66): T2P_SDE_VE (the default after create), T2P_SDE_VP or T2P_SDE_SUBVP.
+ * Call after t2p_train_create and before the first loss.  VE: std = sigma_min (sigma_max / sigma_min)^t, mean = x, integer label
+ * round((1 - t)(N - 1)).  VP / sub-VP (sde_lib.py:134-138, 184-188; models/utils.py:138-157): mean = exp(lmc) x, std = sqrt(1 - exp(2 lmc))
+ * resp. 1 - exp(2 lmc), the network receives the float label t (N - 1) resp. 999 t and its output o becomes the score
+ * -o / sqrt_1m_alphas_cumprod[trunc(label)] resp. -o / std.  beta_min / beta_max: ignored for VE but checked.
+ * std_table: VP only, host float[num_scales] = sde.sqrt_1m_alphas_cumprod as the reference builds it in float32 (sde_lib.py:118-122);
+ * NULL otherwise.  Refused with nothing changed: an unknown sde; beta_max <= beta_min or beta_min <= 0; VP without a table; sub-VP with
+ * scale_by_sigma and num_scales < 1000 (the reference would index sigmas[trunc(999 t)] out of range). */
+int t2p_train_set_sde(t2p_trainer* t, int sde, double beta_min, double beta_max, const float* std_table);
 /* parity runs: keep-masks of Dropout_0 for the next pass, one device uint8 [batch][H][W][C] (NHWC, the block's own resolution and
  * width) per residual block in forward order; n = 0 returns to on-device Philox masks */
 int t2p_train_set_dropout_masks(t2p_trainer* t, const uint8_t* const* device_masks, int n);

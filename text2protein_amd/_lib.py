@@ -11,7 +11,7 @@ from . import build as _build
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 DTYPE_NAMES = {"f32": DT_F32, "fp32": DT_F32, "float32": DT_F32, "bf16": DT_BF16, "bfloat16": DT_BF16,
                "f16": DT_F16, "fp16": DT_F16, "float16": DT_F16}
-SDE_VE, SDE_VP = 0, 1
+SDE_VE, SDE_VP, SDE_SUBVP = 0, 1, 2
 
 
 class T2PError(RuntimeError):
@@ -126,6 +126,7 @@ SIGNATURES = {
     "t2p_train_write": (_i, [_vp, _i, C.c_char_p, _vp]),
     "t2p_train_set_step": (_i, [_vp, _i64, _i64, _i64]),
     "t2p_train_get_step": (_i, [_vp, C.POINTER(_i64)]),
+    "t2p_train_set_sde": (_i, [_vp, _i, C.c_double, C.c_double, _vp]),
     "t2p_train_set_dropout_masks": (_i, [_vp, C.POINTER(_vp), _i]),
     "t2p_train_loss": (_i, [_vp, C.POINTER(TrainBatch), _i, C.POINTER(_f), _vp, _vp]),
     "t2p_train_step": (_i, [_vp, C.POINTER(TrainBatch), C.POINTER(_f), _vp]),

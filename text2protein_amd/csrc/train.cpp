@@ -1,4 +1,4 @@
-// Training step of the score network on MI355X, fp32 (first slice).
+// Training step of the score network on MI355X, under the VE, VP or sub-VP SDE (set_sde).
 //
 // What the reference does in one step (score_sde_pytorch/losses.py:165-176): optimizer.zero_grad(); loss = loss_fn(...) (:105-134);
 // loss.backward(); optimize_fn (:41-49: warm-up on state['step'], clip_grad_norm_, Adam); state['step'] += 1; ema.update
@@ -15,7 +15,7 @@
 // implicit GEMM (fp32 activations rounded once into a pass-local 16-bit copy, 16-bit weight copies made by prep_weights), every strided product on
 // launch_tgemm16; the input and head convolutions (5 or 8 channels) keep the exact-f32 kernel for their forward and data gradient.
 // The backward pass is seeded with S dL/do, S = 2^round(log2(B C L L)) (the fp32 seed is ~1e-5 at full size, at the bottom of
-// f16's normal range), and S is divided out of the flat gradient buffer once at the end.  Every reduction that feeds a gradient, the
+// f16's normal range; under the VP / sub-VP SDE S is chosen on the device from max|dL/do|), and S is divided out of the flat gradient buffer once at the end.  Every reduction that feeds a gradient, the
 // gradient norm or an update runs in a fixed order, so the gradients and the state after a 16-bit step are bitwise reproducible (the
 // scalar loss itself is still summed with double atomics, shared with the fp32 step).  apply() refuses (and changes nothing) when the
 // loss or the gradient norm is not finite.
@@ -233,6 +233,22 @@ int Trainer::set_step(int64_t step, int64_t adam_updates, int64_t ema_updates) {
   return T2P_OK;
 }
 int Trainer::get_step(int64_t out[3]) const { out[0] = step_; out[1] = adam_k_; out[2] = ema_k_; return T2P_OK; }
+int Trainer::set_sde(int sde, double beta_min, double beta_max, const float* std_table) {
+  T2P_REQUIRE(sde == T2P_SDE_VE || sde == T2P_SDE_VP || sde == T2P_SDE_SUBVP, "set_sde: unknown SDE (T2P_SDE_VE, T2P_SDE_VP or T2P_SDE_SUBVP)");
+  T2P_REQUIRE(beta_min > 0.0 && beta_max > beta_min, "set_sde: 0 < beta_min < beta_max");
+  T2P_REQUIRE(sde != T2P_SDE_VP || std_table, "set_sde: the VP SDE needs sqrt_1m_alphas_cumprod (float[num_scales])");
+  T2P_REQUIRE(!(sde == T2P_SDE_SUBVP && mc_.scale_by_sigma && mc_.num_scales < 1000),
+              "set_sde: the sub-VP time label is 999 t: with scale_by_sigma it indexes the sigma table, which needs num_scales >= 1000");
+  if (sde == T2P_SDE_VP) {
+    float* tab = vp_std_ ? vp_std_ : (float*)pool_.persistent((size_t)mc_.num_scales * 4);
+    if (!tab) return T2P_ERR_HIP;
+    T2P_HIP_CHECK(hipDeviceSynchronize());
+    T2P_HIP_CHECK(hipMemcpy(tab, std_table, (size_t)mc_.num_scales * 4, hipMemcpyHostToDevice));
+    vp_std_ = tab;
+  }
+  sde_ = sde; beta_min_ = beta_min; beta_max_ = beta_max;
+  return T2P_OK;
+}
 int Trainer::set_dropout_masks(const uint8_t* const* masks, int n) {
   T2P_REQUIRE(n == 0 || masks, "dropout masks");
   drop_masks_.assign(masks, masks + n);
@@ -678,8 +694,19 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool bac
   float* perturbed = tmp(nx * 4);
   uint8_t* mask = (uint8_t*)tmp(nx);
   if (!t_dev || !stdv || !scale || !num_elem || !labels || !loss_sum || !perturbed || !mask) return T2P_ERR_HIP;
-  T2P_TRY(launch_dsm_prepare(b.t, B, (float)tc_.t_eps, (float)mc_.sigma_min, (float)mc_.sigma_max, mc_.num_scales,
-                             mc_.scale_by_sigma ? inv_sigma_ : nullptr, tc_.seed, (unsigned long long)loss_calls_, t_dev, stdv, labels, scale, s_));
+  // per sample: the std of the loss, the mean coefficient (VP / sub-VP), the time label and the signed scale that turns the network's
+  // output into the score (VE: 1 or 1 / sigma; VP: -1 / std_table[label]; sub-VP: -1 / std; models/utils.py:138-171)
+  float* mean_coef = nullptr; float* labels_f = nullptr;
+  if (sde_ == T2P_SDE_VE) {
+    T2P_TRY(launch_dsm_prepare(b.t, B, (float)tc_.t_eps, (float)mc_.sigma_min, (float)mc_.sigma_max, mc_.num_scales,
+                               mc_.scale_by_sigma ? inv_sigma_ : nullptr, tc_.seed, (unsigned long long)loss_calls_, t_dev, stdv, labels, scale, s_));
+  } else {
+    mean_coef = tmp(B * 4); labels_f = tmp(B * 4);
+    if (!mean_coef || !labels_f) return T2P_ERR_HIP;
+    T2P_TRY(launch_dsm_prepare_vp(b.t, B, (float)tc_.t_eps, beta_min_, beta_max_, sde_ == T2P_SDE_SUBVP, mc_.num_scales, vp_std_,
+                                  mc_.scale_by_sigma ? inv_sigma_ : nullptr, tc_.seed, (unsigned long long)loss_calls_, t_dev, mean_coef, stdv,
+                                  labels, labels_f, scale, s_));
+  }
   const float* z = b.z;
   if (!z) {
     float* zb = tmp(nx * 4);
@@ -687,13 +714,13 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool bac
     T2P_TRY(launch_philox_normal(zb, nx, tc_.seed, (unsigned long long)(loss_calls_ * 4096 + 1), nullptr, s_));
     z = zb;
   }
-  T2P_TRY(launch_dsm_perturb(b.coords_6d, z, stdv, b.mask_pair, b.mask_inpaint, tc_.cond_flags, B, Cx, L, perturbed, mask, num_elem, s_));
+  T2P_TRY(launch_dsm_perturb(b.coords_6d, z, stdv, mean_coef, b.mask_pair, b.mask_inpaint, tc_.cond_flags, B, Cx, L, perturbed, mask, num_elem, s_));
 
   // UNetModel.forward (ncsnpp.py:220-263)
   T2P_ACT(x0, B, L, L, 8, false);
   T2P_TRY(launch_nchw_to_nhwc(perturbed, x0->p, B, Cx, HW, 8, s_));
   T2P_ACT(emb, B, 1, 1, nf, false);
-  T2P_TRY(launch_timestep_embedding(labels, nullptr, nullptr, emb->p, B, nf, s_));
+  T2P_TRY(launch_timestep_embedding(labels, labels_f, nullptr, emb->p, B, nf, s_));   // VP / sub-VP: the fractional label
   TT *te1 = nullptr, *temb = nullptr;
   T2P_TRY(linear(emb, pre0_, &te1));
   T2P_TRY(linear(te1, pre1_, &temb));
@@ -775,12 +802,27 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool bac
   }
   T2P_TRY(launch_dsm_loss(o->p, 8, z, stdv, scale, mask, num_elem, B, Cx, L, loss_sum, d_o, 8, score_out, s_));
   T2P_TRY(launch_dsm_finish(loss_sum, num_elem, B, loss_dev, s_));
-  // 16-bit modes: seed the backward pass with S dL/do (S a power of two: exact in fp32) and divide S out of the flat gradient buffer
+  // 16-bit modes: seed the backward pass with S dL/do (S a power of two: exact in fp32) and divide S out of the flat gradient buffer.
+  // VE: S = 2^round(log2(B C L L)), known on the host (std / sigma[label] is about 1, so the seed is about 2 r / (num_elem B)).
+  // VP / sub-VP: the seed carries std |scale| = up to 1 / sigma_min with scale_by_sigma (the sigma table is indexed by a label that
+  // grows with t) and a residual r of that size, so a fixed S overflows f16 at large t: S is chosen on the device as the largest
+  // power of two with S max|dL/do| <= 64, the magnitude the VE seed has.
+  const bool dev_scale = backward && dt_ != DT_F32 && sde_ != T2P_SDE_VE;
   const float S = dt_ == DT_F32 ? 1.f : std::ldexp(1.f, (int)std::lround(std::log2((double)B * Cx * HW)));
-  if (backward && S != 1.f) T2P_TRY(launch_scale(d_o, S, o->numel(), s_));
+  float* s2 = nullptr;                            // device pair {S, 1 / S} of the VP / sub-VP 16-bit step
+  if (dev_scale) {
+    s2 = tmp(8);
+    unsigned int* amax = (unsigned int*)tmp(4);
+    if (!s2 || !amax) return T2P_ERR_HIP;
+    T2P_TRY(launch_seed_scale(d_o, o->numel(), 64.f, amax, s2, s_));
+    T2P_TRY(launch_scale_dev(d_o, s2, o->numel(), s_));
+  } else if (backward && S != 1.f) {
+    T2P_TRY(launch_scale(d_o, S, o->numel(), s_));
+  }
   if (backward)
     for (auto it = tape_.rbegin(); it != tape_.rend(); ++it) T2P_TRY((*it)());
-  if (backward && S != 1.f) T2P_TRY(launch_scale(Gr_, 1.f / S, total_, s_));
+  if (dev_scale) T2P_TRY(launch_scale_dev(Gr_, s2 + 1, total_, s_));
+  else if (backward && S != 1.f) T2P_TRY(launch_scale(Gr_, 1.f / S, total_, s_));
   return T2P_OK;
 }
 

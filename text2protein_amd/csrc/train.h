@@ -43,6 +43,8 @@ class Trainer {
   int set_step(int64_t step, int64_t adam_updates, int64_t ema_updates);
   int get_step(int64_t out[3]) const;
   int set_dropout_masks(const uint8_t* const* masks, int n);
+  // the SDE of the loss (get_sde_loss_fn's `sde`): T2P_SDE_VE (after build), T2P_SDE_VP (std_table: host float[num_scales]) or T2P_SDE_SUBVP
+  int set_sde(int sde, double beta_min, double beta_max, const float* std_table);
   // loss_fn (losses.py:105-134); with `backward` also d loss / d parameters into the gradient buffer (zeroed first: optimizer.zero_grad())
   int loss(const t2p_train_batch& b, bool backward, bool use_ema, float* loss_host, float* score_out, hipStream_t s);
   // step_fn with train=True (losses.py:165-176) = loss(backward) + apply()
@@ -99,6 +101,9 @@ class Trainer {
   double* sumsq_ = nullptr;
   float* loss_dev_ = nullptr;
   float* inv_sigma_ = nullptr;
+  int sde_ = T2P_SDE_VE;            // the SDE of the loss (set_sde)
+  double beta_min_ = 0.0, beta_max_ = 0.0;
+  float* vp_std_ = nullptr;         // VP: sqrt_1m_alphas_cumprod, float[num_scales] (the divisor of the score, models/utils.py:154)
   int64_t step_ = 0, adam_k_ = 0, ema_k_ = 0, loss_calls_ = 0;
   int dt_ = DT_F32;                 // compute dtype of the products
   double* sumsq_part_ = nullptr;    // 16-bit modes: fixed-order gradient norm (launch_sumsq_fixed)

@@ -88,6 +88,13 @@ int t2p_train_get_step(const t2p_trainer* t, int64_t out3[3]) {
   API_END
 }
 
+int t2p_train_set_sde(t2p_trainer* t, int sde, double beta_min, double beta_max, const float* std_table) {
+  API_BEGIN
+  T2P_REQUIRE(t, "null trainer");
+  return t->impl.set_sde(sde, beta_min, beta_max, std_table);
+  API_END
+}
+
 int t2p_train_set_dropout_masks(t2p_trainer* t, const uint8_t* const* device_masks, int n) {
   API_BEGIN
   T2P_REQUIRE(t && n >= 0, "set_dropout_masks arguments");

@@ -85,19 +85,30 @@ int launch_conv_w_prep(const float* w, float* wf, float* wd, int Co, int Ci, int
 // gw [Co][Ci][3][3] += dwc [Co][9][Cip]
 int launch_conv_w_grad_fold(const float* dwc, float* gw, int Co, int Ci, int Cip, hipStream_t s);
 
-// ---- denoising score matching, VE SDE (losses.py:105-131) --------------------------------------------------------------------------------
-// per sample: t[b] (given, or drawn here: t = eps + (T - eps) u, u from Philox keyed by (seed, step) -- losses.py:106 with T = 1),
+// ---- denoising score matching (losses.py:105-131) under the VE, VP and sub-VP SDEs -----------------------------------------------------
+// VE, per sample: t[b] (given, or drawn here: t = eps + (T - eps) u, u from Philox keyed by (seed, step) -- losses.py:106 with T = 1),
 // std[b] = sigma_min (sigma_max / sigma_min)^t (VESDE.marginal_prob, sde_lib.py:225-228), label[b] = round((1 - t) (N - 1)) (half to even:
 // get_score_fn's VE branch, models/utils.py:165-168) and scale[b] = scale_by_sigma ? 1 / sigmas[label] : 1 (ncsnpp.py:256-261)
 int launch_dsm_prepare(const float* t_in, int B, float t_eps, float sigma_min, float sigma_max, int N, const float* inv_sigma_table,
                        unsigned long long seed, unsigned long long step, float* t_out, float* std, int* labels, float* scale, hipStream_t s);
+// VP (subvp = 0) / sub-VP (subvp = 1), per sample, t as above (the same Philox stream): lmc = -t^2 (beta_max - beta_min) / 4 - t beta_min / 2,
+// mean_coef[b] = exp(lmc), std[b] = sqrt(1 - exp(2 lmc)) (VP, sde_lib.py:134-138) / 1 - exp(2 lmc) (sub-VP, sde_lib.py:184-188) with
+// 1 - exp(2 lmc) = -expm1(2 lmc) in double; labels_f[b] = t (N - 1) (VP) / 999 t (sub-VP), the float the network embeds
+// (models/utils.py:147,152); labels[b] = trunc(labels_f) (the sigma index, ncsnpp.py:223); scale[b] = -1 / std_table[labels[b]] (VP: the
+// DISCRETE sqrt_1m_alphas_cumprod entry, models/utils.py:154) / -1 / std[b] (sub-VP, :149), times inv_sigma_table[labels[b]] when given.
+// std_table: device float[N], VP only.  sub-VP with inv_sigma_table needs N >= 1000
+int launch_dsm_prepare_vp(const float* t_in, int B, float t_eps, double beta_min, double beta_max, int subvp, int N, const float* std_table,
+                          const float* inv_sigma_table, unsigned long long seed, unsigned long long step, float* t_out, float* mean_coef,
+                          float* std, int* labels, float* labels_f, float* scale, hipStream_t s);
 // mask[b][c][y][x] = mask_pair[b][y][x] && conditional_mask (length: c != C - 1; ss: c not in 4..6; inpainting: mask_inpaint[b][y][x]);
-// perturbed = mask ? x + std[b] z : x;  num_elem[b] = #mask   (all NCHW; cond_flags: 1 length, 2 ss, 4 inpainting)
-int launch_dsm_perturb(const float* x, const float* z, const float* std, const unsigned char* mask_pair, const unsigned char* mask_inpaint,
-                       int cond_flags, int B, int C, int L, float* perturbed, unsigned char* mask, float* num_elem, hipStream_t s);
-// o: the head convolution's output NHWC [B][L L][ldo] (before the division by sigma); score = o inv_sigma[b];
-// r = score std[b] + z; loss_sum[b] += sum mask r^2 (double);  d_o [B][L L][ld_do] = 2 r mask std inv_sigma / ((num_elem + 1e-8) B), pad columns zero
-int launch_dsm_loss(const float* o, long ldo, const float* z, const float* std, const float* inv_sigma, const unsigned char* mask,
+// perturbed = mask ? mean_coef[b] x + std[b] z : x (mean_coef == nullptr: the VE form x + std[b] z);  num_elem[b] = #mask
+// (all NCHW; cond_flags: 1 length, 2 ss, 4 inpainting)
+int launch_dsm_perturb(const float* x, const float* z, const float* std, const float* mean_coef, const unsigned char* mask_pair,
+                       const unsigned char* mask_inpaint, int cond_flags, int B, int C, int L, float* perturbed, unsigned char* mask,
+                       float* num_elem, hipStream_t s);
+// o: the head convolution's output NHWC [B][L L][ldo]; scale[b]: the signed per-sample output scale of dsm_prepare; score = scale[b] o;
+// r = score std[b] + z; loss_sum[b] += sum mask r^2 (double);  d_o [B][L L][ld_do] = 2 r mask std scale / ((num_elem + 1e-8) B), pad columns zero
+int launch_dsm_loss(const float* o, long ldo, const float* z, const float* std, const float* scale, const unsigned char* mask,
                     const float* num_elem, int B, int C, int L, double* loss_sum, float* d_o, long ld_do, float* score_nchw, hipStream_t s);
 // loss = mean_b loss_sum[b] / (num_elem[b] + 1e-8)
 int launch_dsm_finish(const double* loss_sum, const float* num_elem, int B, float* loss, hipStream_t s);
@@ -115,5 +126,9 @@ struct AdamArgs {
 int launch_adam(const AdamArgs& a, hipStream_t s);
 int launch_ema(float* shadow, const float* p, float one_minus_decay, long n, hipStream_t s);   // shadow -= (1 - d) (shadow - p)
 int launch_scale(float* x, float a, long n, hipStream_t s);                                   // x *= a
+// s2[0] = S = the largest power of two with S max|x| <= target (1 when x is all zero or not finite), s2[1] = 1 / S; absmax: one
+// device word of scratch.  The maximum is taken with integer atomics on the bit patterns: the same S whatever the order of arrival
+int launch_seed_scale(const float* x, long n, float target, unsigned int* absmax, float* s2, hipStream_t s);
+int launch_scale_dev(float* x, const float* a, long n, hipStream_t s);                        // x *= *a (a on the device)
 
 }  // namespace t2p

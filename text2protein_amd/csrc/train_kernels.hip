@@ -1083,7 +1083,7 @@ int launch_conv_w_grad_fold(const float* dwc, float* gw, int Co, int Ci, int Cip
 }
 
 // =====================================================================================================================================
-// denoising score matching (VE SDE)
+// denoising score matching (VE, VP and sub-VP SDEs)
 // =====================================================================================================================================
 __device__ inline float block_sum_256(float v, float* sh) {
   v = wave_sum(v);
@@ -1103,20 +1103,21 @@ __device__ inline double block_sum_256_d(double v, double* sh) {
 }
 
 __device__ inline void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, const uint32_t k0, const uint32_t k1);
+// t[b]: given, or t = eps + (1 - eps) u with u from Philox keyed by (seed, step), counter = the sample (the same stream for every SDE)
+__device__ inline float dsm_time(const float* __restrict__ t_in, const int b, const float t_eps, const unsigned long long seed,
+                                 const unsigned long long step) {
+  if (t_in) return t_in[b];
+  uint32_t c0 = (uint32_t)b, c1 = 0, c2 = (uint32_t)step, c3 = (uint32_t)(step >> 32), k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  for (int r = 0; r < 10; ++r) { philox_round(c0, c1, c2, c3, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+  return (c0 >> 8) * (1.0f / 16777216.0f) * (1.f - t_eps) + t_eps;
+}
 __global__ void dsm_prepare_kernel(const float* __restrict__ t_in, const int B, const float t_eps, const float sigma_min, const float sigma_max,
                                    const int N, const float* __restrict__ inv_sigma_table, const unsigned long long seed,
                                    const unsigned long long step, float* __restrict__ t_out, float* __restrict__ stdv, int* __restrict__ labels,
                                    float* __restrict__ scale) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  float t;
-  if (t_in) {
-    t = t_in[b];
-  } else {
-    uint32_t c0 = (uint32_t)b, c1 = 0, c2 = (uint32_t)step, c3 = (uint32_t)(step >> 32), k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    for (int r = 0; r < 10; ++r) { philox_round(c0, c1, c2, c3, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-    t = (c0 >> 8) * (1.0f / 16777216.0f) * (1.f - t_eps) + t_eps;
-  }
+  const float t = dsm_time(t_in, b, t_eps, seed, step);
   t_out[b] = t;
   stdv[b] = sigma_min * powf(sigma_max / sigma_min, t);
   int lab = (int)rintf((1.f - t) * (float)(N - 1));
@@ -1133,15 +1134,57 @@ int launch_dsm_prepare(const float* t_in, int B, float t_eps, float sigma_min, f
   return T2P_OK;
 }
 
+// VP (subvp == 0) and sub-VP (subvp == 1).  The exponent lmc is evaluated in double from the fp32 t and 1 - exp(2 lmc) as -expm1(2 lmc):
+// the reference's fp32 1 - exp(.) cancels (quantised to 6e-8 / (1 - exp(2 lmc)) relative), this form does not, so the result is the more
+// accurate one and never differs through a cancellation of its own.  The time label stays the reference's fp32 product (its integer part
+// is a table index).
+__global__ void dsm_prepare_vp_kernel(const float* __restrict__ t_in, const int B, const float t_eps, const double beta_min, const double beta_max,
+                                      const int subvp, const int N, const float* __restrict__ std_table, const float* __restrict__ inv_sigma_table,
+                                      const unsigned long long seed, const unsigned long long step, float* __restrict__ t_out,
+                                      float* __restrict__ mean_coef, float* __restrict__ stdv, int* __restrict__ labels, float* __restrict__ labels_f,
+                                      float* __restrict__ scale) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const float t = dsm_time(t_in, b, t_eps, seed, step);
+  t_out[b] = t;
+  const double td = (double)t;
+  const double lmc = -0.25 * td * td * (beta_max - beta_min) - 0.5 * td * beta_min;
+  const double var = -expm1(2.0 * lmc);                        // 1 - exp(2 lmc)
+  mean_coef[b] = (float)exp(lmc);
+  stdv[b] = (float)(subvp ? var : sqrt(var));
+  const float lf = t * (subvp ? 999.f : (float)(N - 1));
+  int idx = (int)lf;                                            // labels.long(): truncation
+  idx = min(max(idx, 0), N - 1);                              // clamped: labels[] is a safe TABLE index, not always trunc(labels_f) -- sub-VP
+  labels_f[b] = lf;                                             // without a sigma table and N < 1000 has 999 t >= N (the index is unused there)
+  labels[b] = idx;
+  const double div = subvp ? var : (double)std_table[idx];      // the score's divisor: continuous (sub-VP) / the discrete table entry (VP)
+  scale[b] = (float)(-(inv_sigma_table ? (double)inv_sigma_table[idx] : 1.0) / div);
+}
+int launch_dsm_prepare_vp(const float* t_in, int B, float t_eps, double beta_min, double beta_max, int subvp, int N, const float* std_table,
+                          const float* inv_sigma_table, unsigned long long seed, unsigned long long step, float* t_out, float* mean_coef,
+                          float* std, int* labels, float* labels_f, float* scale, hipStream_t s) {
+  T2P_REQUIRE(B > 0 && N >= 2 && t_out && mean_coef && std && labels && labels_f && scale && beta_min > 0.0 && beta_max > beta_min,
+              "dsm_prepare_vp arguments");
+  T2P_REQUIRE(subvp ? (!inv_sigma_table || N >= 1000) : std_table != nullptr,
+              "dsm_prepare_vp: VP needs the discrete std table; sub-VP with a sigma table needs N >= 1000 (its label is 999 t)");
+  hipLaunchKernelGGL(dsm_prepare_vp_kernel, dim3(cdiv_l(B, 64)), dim3(64), 0, s, t_in, B, t_eps, beta_min, beta_max, subvp, N, std_table,
+                     inv_sigma_table, seed, step, t_out, mean_coef, std, labels, labels_f, scale);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+
 // grid (chunks, B)
+template <bool MEAN>
 __global__ __launch_bounds__(256) void dsm_perturb_kernel(const float* __restrict__ x, const float* __restrict__ z, const float* __restrict__ stdv,
-                                                          const unsigned char* __restrict__ mask_pair, const unsigned char* __restrict__ mask_inpaint,
-                                                          const int flags, const int C, const int HW, float* __restrict__ perturbed,
-                                                          unsigned char* __restrict__ mask, float* __restrict__ num_elem) {
+                                                          const float* __restrict__ mean_coef, const unsigned char* __restrict__ mask_pair,
+                                                          const unsigned char* __restrict__ mask_inpaint, const int flags, const int C,
+                                                          const int HW, float* __restrict__ perturbed, unsigned char* __restrict__ mask,
+                                                          float* __restrict__ num_elem) {
   __shared__ float sh[4];
   const int b = blockIdx.y;
   const long per = (long)C * HW;
   const float sd = stdv[b];
+  const float mc = MEAN ? mean_coef[b] : 1.f;
   float cnt = 0.f;
   for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < per; j += (long)gridDim.x * 256) {
     const int c = (int)(j / HW), p = (int)(j - (long)c * HW);
@@ -1151,34 +1194,41 @@ __global__ __launch_bounds__(256) void dsm_perturb_kernel(const float* __restric
     if ((flags & 4) && !mask_inpaint[(long)b * HW + p]) m = false;
     const long i = (long)b * per + j;
     const float xv = x[i];
-    perturbed[i] = m ? xv + sd * z[i] : xv;
+    if (MEAN) perturbed[i] = m ? mc * xv + sd * z[i] : xv;
+    else perturbed[i] = m ? xv + sd * z[i] : xv;
     mask[i] = m ? 1 : 0;
     cnt += m ? 1.f : 0.f;
   }
   cnt = block_sum_256(cnt, sh);
   if (threadIdx.x == 0 && cnt != 0.f) unsafeAtomicAdd(num_elem + b, cnt);
 }
-int launch_dsm_perturb(const float* x, const float* z, const float* std, const unsigned char* mask_pair, const unsigned char* mask_inpaint,
-                       int cond_flags, int B, int C, int L, float* perturbed, unsigned char* mask, float* num_elem, hipStream_t s) {
+int launch_dsm_perturb(const float* x, const float* z, const float* std, const float* mean_coef, const unsigned char* mask_pair,
+                       const unsigned char* mask_inpaint, int cond_flags, int B, int C, int L, float* perturbed, unsigned char* mask,
+                       float* num_elem, hipStream_t s) {
   T2P_REQUIRE(x && z && std && mask_pair && perturbed && mask && num_elem && B > 0 && B <= 65535 && C > 0 && L > 0, "dsm_perturb arguments");
   T2P_REQUIRE(!(cond_flags & 4) || mask_inpaint, "dsm_perturb: the inpainting condition needs mask_inpaint");
   T2P_HIP_CHECK(hipMemsetAsync(num_elem, 0, B * sizeof(float), s));
   const long per = (long)C * L * L;
-  hipLaunchKernelGGL(dsm_perturb_kernel, dim3(std::min(64, cdiv_l(per, 256)), B), dim3(256), 0, s, x, z, std, mask_pair, mask_inpaint, cond_flags, C,
-                     L * L, perturbed, mask, num_elem);
+  const dim3 grid(std::min(64, cdiv_l(per, 256)), B);
+  if (mean_coef)
+    hipLaunchKernelGGL(dsm_perturb_kernel<true>, grid, dim3(256), 0, s, x, z, std, mean_coef, mask_pair, mask_inpaint, cond_flags, C, L * L, perturbed,
+                       mask, num_elem);
+  else
+    hipLaunchKernelGGL(dsm_perturb_kernel<false>, grid, dim3(256), 0, s, x, z, std, mean_coef, mask_pair, mask_inpaint, cond_flags, C, L * L, perturbed,
+                       mask, num_elem);
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }
 
 __global__ __launch_bounds__(256) void dsm_loss_kernel(const float* __restrict__ o, const long ldo, const float* __restrict__ z,
-                                                       const float* __restrict__ stdv, const float* __restrict__ inv_sigma,
+                                                       const float* __restrict__ stdv, const float* __restrict__ scale,
                                                        const unsigned char* __restrict__ mask, const float* __restrict__ num_elem, const int B,
                                                        const int C, const int HW, double* __restrict__ loss_sum, float* __restrict__ d_o,
                                                        const long ld_do, float* __restrict__ score_nchw) {
   __shared__ double sh[4];
   const int b = blockIdx.y;
   const long per = (long)C * HW;
-  const float sd = stdv[b], is = inv_sigma[b];
+  const float sd = stdv[b], is = scale[b];
   const float gscale = 2.f * sd * is / ((num_elem[b] + 1e-8f) * (float)B);
   double acc = 0.0;
   for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < per; j += (long)gridDim.x * 256) {
@@ -1194,14 +1244,14 @@ __global__ __launch_bounds__(256) void dsm_loss_kernel(const float* __restrict__
   acc = block_sum_256_d(acc, sh);
   if (threadIdx.x == 0) unsafeAtomicAdd(loss_sum + b, acc);
 }
-int launch_dsm_loss(const float* o, long ldo, const float* z, const float* std, const float* inv_sigma, const unsigned char* mask,
+int launch_dsm_loss(const float* o, long ldo, const float* z, const float* std, const float* scale, const unsigned char* mask,
                     const float* num_elem, int B, int C, int L, double* loss_sum, float* d_o, long ld_do, float* score_nchw, hipStream_t s) {
-  T2P_REQUIRE(o && z && std && inv_sigma && mask && num_elem && loss_sum && B > 0 && B <= 65535 && C > 0 && L > 0 && ldo >= C, "dsm_loss arguments");
+  T2P_REQUIRE(o && z && std && scale && mask && num_elem && loss_sum && B > 0 && B <= 65535 && C > 0 && L > 0 && ldo >= C, "dsm_loss arguments");
   T2P_REQUIRE(!d_o || ld_do >= C, "dsm_loss: ld_do");
   T2P_HIP_CHECK(hipMemsetAsync(loss_sum, 0, B * sizeof(double), s));
   if (d_o && ld_do > C) T2P_HIP_CHECK(hipMemsetAsync(d_o, 0, (size_t)B * L * L * ld_do * sizeof(float), s));
   const long per = (long)C * L * L;
-  hipLaunchKernelGGL(dsm_loss_kernel, dim3(std::min(64, cdiv_l(per, 256)), B), dim3(256), 0, s, o, ldo, z, std, inv_sigma, mask, num_elem, B, C, L * L,
+  hipLaunchKernelGGL(dsm_loss_kernel, dim3(std::min(64, cdiv_l(per, 256)), B), dim3(256), 0, s, o, ldo, z, std, scale, mask, num_elem, B, C, L * L,
                      loss_sum, d_o, ld_do, score_nchw);
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
@@ -1298,6 +1348,45 @@ __global__ __launch_bounds__(256) void scale_kernel(float* __restrict__ x, const
 int launch_scale(float* x, float a, long n, hipStream_t s) {
   T2P_REQUIRE(x && n > 0, "scale arguments");
   hipLaunchKernelGGL(scale_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, s, x, a, n);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+
+// ---- power-of-two seed scale chosen from the seed itself (16-bit VP / sub-VP step) --------------------------------------------------------
+// |x| of a finite non-negative float orders as its bit pattern, so an integer atomicMax gives max |x| independent of the order of arrival
+__global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x, const long n, unsigned int* __restrict__ out) {
+  unsigned int m = 0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) m = max(m, __float_as_uint(fabsf(x[i])));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned int)__shfl_xor((int)m, o));
+  if ((threadIdx.x & 63) == 0 && m != 0) atomicMax(out, m);
+}
+__global__ void seed_scale_kernel(const unsigned int* __restrict__ absmax, const float target, float* __restrict__ s2) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const float m = __uint_as_float(*absmax);
+  float S = 1.f;
+  if (m > 0.f && m < INFINITY) {                 // (a NaN or infinite seed keeps S = 1: the loss is not finite and apply() refuses)
+    int e = 0;
+    frexpf(target / m, &e);                      // target / m = f 2^e, f in [0.5, 1): 2^(e - 1) <= target / m
+    S = ldexpf(1.f, min(max(e - 1, -60), 60));
+  }
+  s2[0] = S; s2[1] = 1.f / S;
+}
+__global__ __launch_bounds__(256) void scale_dev_kernel(float* __restrict__ x, const float* __restrict__ a, const long n) {
+  const float av = *a;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) x[i] *= av;
+}
+int launch_seed_scale(const float* x, long n, float target, unsigned int* absmax, float* s2, hipStream_t s) {
+  T2P_REQUIRE(x && n > 0 && absmax && s2 && target > 0.f, "seed_scale arguments");
+  T2P_HIP_CHECK(hipMemsetAsync(absmax, 0, sizeof(unsigned int), s));
+  hipLaunchKernelGGL(absmax_kernel, dim3(grid_for(n, 256, 1024)), dim3(256), 0, s, x, n, absmax);
+  hipLaunchKernelGGL(seed_scale_kernel, dim3(1), dim3(64), 0, s, absmax, target, s2);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+int launch_scale_dev(float* x, const float* a, long n, hipStream_t s) {
+  T2P_REQUIRE(x && a && n > 0, "scale_dev arguments");
+  hipLaunchKernelGGL(scale_dev_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, s, x, a, n);
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }

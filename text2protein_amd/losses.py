@@ -1,5 +1,5 @@
 """Training step on MI355X: Python mirror of the reference's ``score_sde_pytorch/losses.py`` over the C ABI
-(``t2p_train_*``, include/t2p.h).  SURVEY.md 8(f)4, VE SDE: exact-f32 products, or (``dtype="f16"`` / ``"bf16"``) 16-bit
+(``t2p_train_*``, include/t2p.h).  SURVEY.md 8(f)4, under the VE, VP or sub-VP SDE: exact-f32 products, or (``dtype="f16"`` / ``"bf16"``) 16-bit
 products with fp32 accumulation and fp32 parameters, gradients, optimizer state, EMA and loss.
 
 The reference keeps four objects in ``state`` -- ``model`` (DataParallel(UNetModel)), ``optimizer`` (torch Adam),
@@ -30,7 +30,7 @@ from . import _lib
 from ._lib import T2PError, TrainBatch, TrainConfig, check, ptr, stream_ptr
 from .arch import param_specs
 from .model import _model_config
-from .sde_lib import VESDE
+from .sde_lib import VESDE, VPSDE, subVPSDE
 
 _COND_FLAGS = {"length": 1, "ss": 2, "inpainting": 4}
 PARAM, GRAD, EMA, EXP_AVG, EXP_AVG_SQ = 0, 1, 2, 3, 4
@@ -82,6 +82,7 @@ class HipTrainModel:
         self._loaded = False
         self.training = True
         self._keep = []
+        self._sde = None          # (kind, parameters) once set_sde ran; the native default is VE with the model's sigmas
 
     # -- nn.Module-like surface ----------------------------------------------------------------------------------------
     def train(self, mode=True):
@@ -150,6 +151,28 @@ class HipTrainModel:
         out = (C.c_int64 * 3)()
         check(self.lib.t2p_train_get_step(self._h, out))
         return tuple(int(v) for v in out)
+
+    def set_sde(self, sde):
+        """The SDE of the loss (``get_sde_loss_fn``'s ``sde``): an ``sde_lib.VESDE``, ``VPSDE`` or ``subVPSDE`` whose ``N`` is
+        ``model.num_scales``.  ``get_sde_loss_fn`` / ``get_step_fn`` call this on first use; a model stays with the SDE it was given."""
+        key = _sde_key(sde)
+        if int(sde.N) != int(self.config.model.num_scales):
+            raise T2PError(f"sde.N = {sde.N} differs from model.num_scales = {self.config.model.num_scales}")
+        if self._sde is not None:
+            if self._sde != key:
+                raise T2PError(f"this model trains under {self._sde[0]}{self._sde[1:]}; it cannot switch to {key[0]}{key[1:]}")
+            return
+        m = self.config.model
+        if key[0] == "VESDE":
+            if (float(m.sigma_min), float(m.sigma_max)) != key[1:3]:
+                raise T2PError("the VESDE's sigma_min / sigma_max differ from model.sigma_min / sigma_max")
+            check(self.lib.t2p_train_set_sde(self._h, _lib.SDE_VE, 0.1, 20.0, None))       # (the betas are unused under VE)
+        elif key[0] == "VPSDE":
+            table = sde.sqrt_1m_alphas_cumprod.detach().to("cpu", torch.float32).contiguous()     # the reference's float32 table
+            check(self.lib.t2p_train_set_sde(self._h, _lib.SDE_VP, key[1], key[2], C.c_void_p(table.data_ptr())))
+        else:
+            check(self.lib.t2p_train_set_sde(self._h, _lib.SDE_SUBVP, key[1], key[2], None))
+        self._sde = key
 
     def set_dropout_masks(self, masks):
         """Parity runs: NHWC uint8 keep-masks (device tensors), one per residual block in forward order; None / [] = Philox."""
@@ -228,6 +251,17 @@ class HipTrainModel:
                 self._h = None
         except Exception:  # noqa: BLE001
             pass
+
+
+def _sde_key(sde):
+    """(class name, parameters, N) of a supported SDE; any other class raises the reference's error (models/utils.py:173-174)."""
+    if isinstance(sde, VESDE):
+        return ("VESDE", float(sde.sigma_min), float(sde.sigma_max), int(sde.N))
+    if isinstance(sde, VPSDE):
+        return ("VPSDE", float(sde.beta_0), float(sde.beta_1), int(sde.N))
+    if isinstance(sde, subVPSDE):
+        return ("subVPSDE", float(sde.beta_0), float(sde.beta_1), int(sde.N))
+    raise NotImplementedError(f"SDE class {sde.__class__.__name__} not yet supported.")
 
 
 class _ParamHandle:
@@ -340,12 +374,12 @@ class ExponentialMovingAverage:
 
 
 def get_sde_loss_fn(sde, train, eps=1e-5):
-    """losses.py:66-136.  ``batch["context"]`` holds the caption embedding (B, T, context_dim); with raw captions pass
+    """losses.py:66-136 for ``sde`` = VESDE, VPSDE or subVPSDE (the model takes the SDE on first use and keeps it).  ``batch["context"]`` holds the caption embedding (B, T, context_dim); with raw captions pass
     ``llm_components`` = a callable ``captions -> embedding`` (text2protein_amd.text_context.TextContextProducer)."""
-    if not isinstance(sde, VESDE):
-        raise NotImplementedError(f"SDE class {sde.__class__.__name__} not yet supported.")
+    _sde_key(sde)
 
     def loss_fn(model, batch, condition=None, llm_components=None, t=None, z=None):
+        model.set_sde(sde)
         if condition_flags(condition) != model._tc.cond_flags:
             raise T2PError("`condition` differs from the model.condition the model was created with")
         if "context" not in batch:
@@ -365,12 +399,12 @@ def get_step_fn(sde, train, optimize_fn=None, dist=None):
     the ranks with ONE all-reduce (RCCL over xGMI) and every rank applies the same update; the returned loss is the mean over the
     ranks.  With equal shards this is the reference's DataParallel step on the concatenated batch (the loss is a mean of per-sample
     terms, losses.py:128-131)."""
-    if not isinstance(sde, VESDE):
-        raise NotImplementedError(f"SDE class {sde.__class__.__name__} not yet supported.")
+    _sde_key(sde)
     world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
 
     def step_fn(state, batch, condition=None, t=None, z=None):
         model = state["model"]
+        model.set_sde(sde)
         if condition_flags(condition) != model._tc.cond_flags:
             raise T2PError("`condition` differs from the model.condition the model was created with")
         if "context" not in batch:

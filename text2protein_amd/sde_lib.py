@@ -1,4 +1,4 @@
-"""SDE definitions of the sampling path (mirror of reference ``score_sde_pytorch/sde_lib.py``).
+"""SDE definitions of the sampling path and of the training loss (mirror of reference ``score_sde_pytorch/sde_lib.py``).
 
 Scalars and (B,)-shaped schedule values are computed with torch exactly as the reference does
 (they are a few floats per step); everything that touches the (B, C, L, L) state runs in the HIP
@@ -36,6 +36,12 @@ class SDE(abc.ABC):
     def prior_sampling(self, shape):
         return torch.randn(*shape) * self.prior_scale()
 
+    def marginal_prob(self, x, t):
+        """(mean, std) of p_t(x | x_0 = x) for a (B, C, L, L) tensor and a (B,) tensor of times, in the reference's arithmetic.  The
+        training step evaluates the same quantities per sample on the device (text2protein_amd.losses).  VESDE, VPSDE and subVPSDE
+        define it; it is not required of other subclasses."""
+        raise NotImplementedError(f"{type(self).__name__} has no marginal_prob")
+
 
 class VESDE(SDE):
     def __init__(self, sigma_min=0.01, sigma_max=50, N=1000):
@@ -54,6 +60,10 @@ class VESDE(SDE):
 
     def prior_scale(self):
         return self.sigma_max
+
+    def marginal_prob(self, x, t):
+        """sde_lib.py:224-227."""
+        return x, self.marginal_prob_std(t)
 
     def discretize_coeffs(self, t):
         """(drift scale a, G) such that f = a * x; VE: f = 0, G = sqrt(sigma_k^2 - sigma_{k-1}^2)
@@ -96,6 +106,13 @@ class VPSDE(SDE):
         log_mean_coeff = -0.25 * t ** 2 * (self.beta_1 - self.beta_0) - 0.5 * t * self.beta_0
         return torch.sqrt(1.0 - torch.exp(2.0 * log_mean_coeff))
 
+    def marginal_prob(self, x, t):
+        """sde_lib.py:134-138."""
+        log_mean_coeff = -0.25 * t ** 2 * (self.beta_1 - self.beta_0) - 0.5 * t * self.beta_0
+        mean = torch.exp(log_mean_coeff[:, None, None, None]) * x
+        std = torch.sqrt(1. - torch.exp(2. * log_mean_coeff))
+        return mean, std
+
     def prior_scale(self):
         return 1.0
 
@@ -135,7 +152,7 @@ class VPSDE(SDE):
 
 
 class subVPSDE(SDE):
-    """Present for the config surface only: the reference's ``subVPSDE.sde`` does not accept the
+    """Training loss only (``marginal_prob``, losses.get_sde_loss_fn): the reference's ``subVPSDE.sde`` does not accept the
     ``context`` argument its callers pass (sde_lib.py:177 vs :89), so it cannot be sampled there
     either, and the driver never selects it (sampling_6d.py:76-82)."""
 
@@ -151,6 +168,13 @@ class subVPSDE(SDE):
     def marginal_prob_std(self, t):
         log_mean_coeff = -0.25 * t ** 2 * (self.beta_1 - self.beta_0) - 0.5 * t * self.beta_0
         return 1 - torch.exp(2.0 * log_mean_coeff)
+
+    def marginal_prob(self, x, t):
+        """sde_lib.py:184-188 (the "std" is the variance of the VP SDE: no square root, as the reference has it)."""
+        log_mean_coeff = -0.25 * t ** 2 * (self.beta_1 - self.beta_0) - 0.5 * t * self.beta_0
+        mean = torch.exp(log_mean_coeff)[:, None, None, None] * x
+        std = 1 - torch.exp(2. * log_mean_coeff)
+        return mean, std
 
     def prior_scale(self):
         return 1.0

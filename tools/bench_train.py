@@ -1,6 +1,6 @@
 """Time the training step (t2p_train_step: loss + backward + Adam + EMA) at a BASELINE model size.
 
-    python tools/bench_train.py --config cond_length.yml --batch 8 --steps 5 [--tokens 64] [--dropout 0.1] [--dtype f32|f16|bf16]
+    python tools/bench_train.py --config cond_length.yml --batch 8 --steps 5 [--tokens 64] [--dropout 0.1] [--dtype f32|f16|bf16] [--sde ve|vp|subvp]
 
 Prints one JSON line: ms per step, samples/s, the loss sequence, device memory, and the achieved matrix rate against the peak of the
 compute dtype's MFMA (157.3 TFLOP/s f32, 2500 TFLOP/s f16 / bf16), counting a step as 3 x the forward pass AS EXECUTED (the text K / V projections are inside a training
@@ -31,6 +31,7 @@ def main():
     ap.add_argument("--L", type=int, default=0)
     ap.add_argument("--dropout", type=float, default=-1.0)
     ap.add_argument("--dtype", default="f32", choices=sorted(PEAK_TFLOPS))
+    ap.add_argument("--sde", default="ve", choices=["ve", "vp", "subvp"], help="the SDE of the loss")
     a = ap.parse_args()
     from text2protein_amd import losses, sde_lib, synth
     from text2protein_amd.config import load_config
@@ -54,7 +55,10 @@ def main():
     batch = dict(coords_6d=x.cuda(), mask_pair=mp.cuda(), context=synth.synth_context(B, a.tokens, cfg.model.context_dim, 3).cuda())
     if "inpainting" in (cfg.model.condition or []):
         batch["mask_inpaint"] = mp.cuda()
-    sde = sde_lib.VESDE(sigma_min=cfg.model.sigma_min, sigma_max=cfg.model.sigma_max, N=cfg.model.num_scales)
+    if a.sde == "ve":
+        sde = sde_lib.VESDE(sigma_min=cfg.model.sigma_min, sigma_max=cfg.model.sigma_max, N=cfg.model.num_scales)
+    else:
+        sde = (sde_lib.VPSDE if a.sde == "vp" else sde_lib.subVPSDE)(beta_min=cfg.model.beta_min, beta_max=cfg.model.beta_max, N=cfg.model.num_scales)
     step_fn = losses.get_step_fn(sde, train=True, optimize_fn=losses.optimization_manager(cfg))
     state = dict(model=model, optimizer=losses.get_optimizer(cfg, model.parameters()),
                  ema=losses.ExponentialMovingAverage(model.parameters(), decay=cfg.model.ema_rate), step=5000)
@@ -68,7 +72,7 @@ def main():
     torch.cuda.synchronize()
     dt = (time.time() - t0) / a.steps
     gf = FWD_GFLOP.get(a.config, 0.0) * 3 * B
-    out = {"metric": f"training step ({'fp32' if a.dtype == 'f32' else a.dtype})", "dtype": a.dtype, "config": a.config, "batch": B, "L": L,
+    out = {"metric": f"training step ({'fp32' if a.dtype == 'f32' else a.dtype})", "dtype": a.dtype, "sde": a.sde, "config": a.config, "batch": B, "L": L,
            "tokens": a.tokens, "ms_per_step": dt * 1e3, "samples_per_s": B / dt, "losses": [round(v, 5) for v in seq],
            "device_GiB": model.device_bytes() / 2 ** 30}
     tf = gf / dt / 1e3
