@@ -209,8 +209,7 @@ static void st_params(std::vector<ParamInfo>& v, const Layer& l, int64_t ctx) {
   add(v, p + ".proj_out.weight", {c, c, 1, 1}); add(v, p + ".proj_out.bias", {c});
 }
 
-int Engine::build() {
-  const t2p_model_config& c = cfg_;
+int NetArch::build(const t2p_model_config& c) {
   T2P_REQUIRE(c.n_ch_mult >= 1 && c.n_ch_mult <= 8, "ch_mult length");
   T2P_REQUIRE(c.n_attn_resolutions >= 0 && c.n_attn_resolutions <= 8, "attn_resolutions length");
   T2P_REQUIRE(c.nf >= 8 && c.nf % 8 == 0, "nf must be a multiple of 8");
@@ -219,9 +218,8 @@ int Engine::build() {
   T2P_REQUIRE(c.n_heads >= 1 && c.context_dim >= 8 && c.context_dim % 8 == 0, "n_heads / context_dim");
   T2P_REQUIRE(c.num_scales >= 2 && c.sigma_min > 0 && c.sigma_max > c.sigma_min, "sigma schedule");
   T2P_REQUIRE(c.compute_dtype >= 0 && c.compute_dtype <= 2, "compute_dtype");
-  nf_ = c.nf;
-  temb_dim_ = 4 * nf_;
-  cpad_ = 8;
+  nf = c.nf;
+  temb_dim = 4 * nf;
   const int nres = c.n_ch_mult, nrb = c.num_res_blocks, L = c.max_res_num;
   auto in_attn = [&](int res) {
     for (int i = 0; i < c.n_attn_resolutions; ++i)
@@ -232,7 +230,7 @@ int Engine::build() {
     Layer l;
     l.kind = kind; l.prefix = prefix; l.in_ch = ci; l.out_ch = co; l.up = up; l.down = down;
     l.has_conv2 = (kind == 0) && (ci != co || up || down);
-    if (kind == 0) { l.temb_off = temb_total_; temb_total_ += co; }
+    if (kind == 0) { l.temb_off = temb_total; temb_total += co; }
     return l;
   };
   auto attn_pair = [&](Stage& st, const std::string& prefix, int idx0, int ch) -> int {
@@ -242,38 +240,38 @@ int Engine::build() {
     st.layers.push_back(mk(2, prefix + "." + std::to_string(idx0 + 1), ch, ch, 0, 0));
     return T2P_OK;
   };
-  std::vector<int> skip_ch{nf_};
-  int in_ch = nf_;
+  std::vector<int> skip_ch{nf};
+  int in_ch = nf;
   for (int lvl = 0; lvl < nres; ++lvl) {
     const int res = L >> lvl;
     for (int b = 0; b < nrb; ++b) {
-      const int out_ch = nf_ * c.ch_mult[lvl];
-      const std::string prefix = "input_blocks." + std::to_string(input_stages_.size());
+      const int out_ch = nf * c.ch_mult[lvl];
+      const std::string prefix = "input_blocks." + std::to_string(input_stages.size());
       Stage st;
       st.layers.push_back(mk(0, prefix + ".0", in_ch, out_ch, 0, 0));
       in_ch = out_ch;
       if (in_attn(res)) T2P_TRY(attn_pair(st, prefix, 1, in_ch));
-      input_stages_.push_back(std::move(st));
+      input_stages.push_back(std::move(st));
       skip_ch.push_back(in_ch);
     }
     if (lvl != nres - 1) {
-      const std::string prefix = "input_blocks." + std::to_string(input_stages_.size());
+      const std::string prefix = "input_blocks." + std::to_string(input_stages.size());
       Stage st;
       st.layers.push_back(mk(0, prefix + ".0", in_ch, in_ch, 0, 1));
-      input_stages_.push_back(std::move(st));
+      input_stages.push_back(std::move(st));
       skip_ch.push_back(in_ch);
     }
   }
   const int mid = skip_ch.back();
-  mid_stage_.layers.push_back(mk(0, "mid_blocks.0", mid, mid, 0, 0));
-  T2P_TRY(attn_pair(mid_stage_, "mid_blocks", 1, mid));
-  mid_stage_.layers.push_back(mk(0, "mid_blocks.3", mid, mid, 0, 0));
+  mid_stage.layers.push_back(mk(0, "mid_blocks.0", mid, mid, 0, 0));
+  T2P_TRY(attn_pair(mid_stage, "mid_blocks", 1, mid));
+  mid_stage.layers.push_back(mk(0, "mid_blocks.3", mid, mid, 0, 0));
   in_ch = mid;
   for (int lvl = nres - 1; lvl >= 0; --lvl) {
     const int res = L >> lvl;
     for (int b = 0; b <= nrb; ++b) {
-      const int out_ch = nf_ * c.ch_mult[lvl];
-      const std::string prefix = "out_blocks." + std::to_string(out_stages_.size());
+      const int out_ch = nf * c.ch_mult[lvl];
+      const std::string prefix = "out_blocks." + std::to_string(out_stages.size());
       Stage st;
       st.skip_ch = skip_ch.back();
       skip_ch.pop_back();
@@ -282,31 +280,33 @@ int Engine::build() {
       if (in_attn(res)) T2P_TRY(attn_pair(st, prefix, 1, in_ch));
       if (lvl != 0 && b == nrb)
         st.layers.push_back(mk(0, prefix + "." + std::to_string(st.layers.size()), in_ch, in_ch, 1, 0));
-      out_stages_.push_back(std::move(st));
+      out_stages.push_back(std::move(st));
     }
   }
   T2P_REQUIRE(skip_ch.empty(), "skip stack not consumed");
-  final_ch_ = in_ch;
+  final_ch = in_ch;
 
   // parameter table in reference parameters() order
-  const int64_t td = temb_dim_, nf = nf_, ch = c.num_channels;
-  add(params_, "pre_blocks.0.weight", {td, nf}); add(params_, "pre_blocks.0.bias", {td});
-  add(params_, "pre_blocks.1.weight", {td, td}); add(params_, "pre_blocks.1.bias", {td});
-  add(params_, "pre_conv.weight", {nf, ch, 3, 3}); add(params_, "pre_conv.bias", {nf});
+  const int64_t td = temb_dim, ch = c.num_channels;
+  add(params, "pre_blocks.0.weight", {td, nf}); add(params, "pre_blocks.0.bias", {td});
+  add(params, "pre_blocks.1.weight", {td, td}); add(params, "pre_blocks.1.bias", {td});
+  add(params, "pre_conv.weight", {nf, ch, 3, 3}); add(params, "pre_conv.bias", {nf});
   auto walk = [&](Stage& st) {
     for (Layer& l : st.layers) {
-      if (l.kind == 0) res_params(params_, l, temb_dim_);
-      else if (l.kind == 1) attn_params(params_, l);
-      else st_params(params_, l, c.context_dim);
+      if (l.kind == 0) res_params(params, l, temb_dim);
+      else if (l.kind == 1) attn_params(params, l);
+      else st_params(params, l, c.context_dim);
     }
   };
-  for (Stage& st : input_stages_) walk(st);
-  walk(mid_stage_);
-  for (Stage& st : out_stages_) walk(st);
-  add(params_, "out.0.weight", {final_ch_}); add(params_, "out.0.bias", {final_ch_});
-  add(params_, "out.2.weight", {ch, final_ch_, 3, 3}); add(params_, "out.2.bias", {ch});
+  for (Stage& st : input_stages) walk(st);
+  walk(mid_stage);
+  for (Stage& st : out_stages) walk(st);
+  add(params, "out.0.weight", {final_ch}); add(params, "out.0.bias", {final_ch});
+  add(params, "out.2.weight", {ch, final_ch, 3, 3}); add(params, "out.2.bias", {ch});
   return T2P_OK;
 }
+
+int Engine::build() { return arch_.build(cfg_); }
 
 int Engine::load_param(const char* name, const float* data, const int64_t* shape, int ndim) {
   T2P_REQUIRE(name && data && shape && ndim >= 1 && ndim <= 4, "load_param arguments");
@@ -315,7 +315,7 @@ int Engine::load_param(const char* name, const float* data, const int64_t* shape
   if (n.rfind("module.", 0) == 0) n = n.substr(7);   // DataParallel state dict (score_sde_pytorch/utils.py:8)
   if (n == "sigmas") return T2P_OK;                   // float64 buffer: derived from the config here
   const ParamInfo* info = nullptr;
-  for (const ParamInfo& p : params_)
+  for (const ParamInfo& p : arch_.params)
     if (p.name == n) { info = &p; break; }
   if (!info) {   // load_state_dict(strict=False) ignores unknown keys (score_sde_pytorch/utils.py:14)
     return T2P_OK;
@@ -487,40 +487,40 @@ int Engine::upload_norm(const std::string& prefix, int C, int G, DevNorm* out) {
 
 int Engine::finalize() {
   T2P_REQUIRE(!finalized_, "engine already finalized");
-  for (const ParamInfo& p : params_) {
+  for (const ParamInfo& p : arch_.params) {
     if (!host_.count(p.name)) {
       set_last_error("parameter not loaded: " + p.name);
       return T2P_ERR_STATE;
     }
   }
-  const int td = temb_dim_;
-  T2P_TRY(upload_linear("pre_blocks.0.weight", "pre_blocks.0.bias", td, nf_, &pre0_, false, false, DT_F32));
+  const int td = arch_.temb_dim;
+  T2P_TRY(upload_linear("pre_blocks.0.weight", "pre_blocks.0.bias", td, arch_.nf, &pre0_, false, false, DT_F32));
   T2P_TRY(upload_linear("pre_blocks.1.weight", "pre_blocks.1.bias", td, td, &pre1_, false, false, DT_F32));
-  T2P_TRY(upload_linear("pre_conv.weight", "pre_conv.bias", nf_, 9 * cfg_.num_channels, &pre_conv_, true, false, DT_F32));
+  T2P_TRY(upload_linear("pre_conv.weight", "pre_conv.bias", arch_.nf, 9 * cfg_.num_channels, &pre_conv_, true, false, DT_F32));
   {
-    const HostTensor* w = host("pre_conv.weight", {nf_, cfg_.num_channels, 3, 3});
+    const HostTensor* w = host("pre_conv.weight", {arch_.nf, cfg_.num_channels, 3, 3});
     if (!w) return T2P_ERR_STATE;
     std::vector<float> m = to_nk(*w, true, false, 0);      // [nf][tap][C], unpadded
     const int K9 = 9 * cfg_.num_channels;
-    std::vector<float> mt((size_t)K9 * nf_);                // [tap][C][nf]: lanes (= output channels) read contiguously
-    for (int n = 0; n < nf_; ++n)
-      for (int k = 0; k < K9; ++k) mt[(size_t)k * nf_ + n] = m[(size_t)n * K9 + k];
+    std::vector<float> mt((size_t)K9 * arch_.nf);                // [tap][C][nf]: lanes (= output channels) read contiguously
+    for (int n = 0; n < arch_.nf; ++n)
+      for (int k = 0; k < K9; ++k) mt[(size_t)k * arch_.nf + n] = m[(size_t)n * K9 + k];
     T2P_TRY(upload_f32(mt, &pre_conv_direct_));
     // the same weights split into two f16 terms each, for the input convolution on the 16-bit matrix pipe (pre_conv_split_kernel).
     // The split form needs |x| inside the f16 range: the state of a VE run stays within a few sigma_max
     const int C = cfg_.num_channels;
     if (dtype() != DT_F32 && (C == 5 || C == 8) && cfg_.sigma_max <= 4096.0) {
-      pre_conv_split_ = pool_.persistent(pre_conv_split_weight_bytes(C, nf_));
+      pre_conv_split_ = pool_.persistent(pre_conv_split_weight_bytes(C, arch_.nf));
       if (!pre_conv_split_) return T2P_ERR_HIP;
-      T2P_TRY(launch_pre_conv_split_weights(pre_conv_direct_, pre_conv_split_, C, nf_, nullptr));
+      T2P_TRY(launch_pre_conv_split_weights(pre_conv_direct_, pre_conv_split_, C, arch_.nf, nullptr));
       T2P_HIP_CHECK(hipStreamSynchronize(nullptr));
     }
   }
-  std::vector<float> dw((size_t)temb_total_ * td), db(temb_total_);
+  std::vector<float> dw((size_t)arch_.temb_total * td), db(arch_.temb_total);
   auto each_layer = [&](auto&& fn) -> int {
-    for (Stage& st : input_stages_) for (Layer& l : st.layers) T2P_TRY(fn(l));
-    for (Layer& l : mid_stage_.layers) T2P_TRY(fn(l));
-    for (Stage& st : out_stages_) for (Layer& l : st.layers) T2P_TRY(fn(l));
+    for (Stage& st : arch_.input_stages) for (Layer& l : st.layers) T2P_TRY(fn(l));
+    for (Layer& l : arch_.mid_stage.layers) T2P_TRY(fn(l));
+    for (Stage& st : arch_.out_stages) for (Layer& l : st.layers) T2P_TRY(fn(l));
     return T2P_OK;
   };
   T2P_TRY(each_layer([&](Layer& l) -> int {
@@ -700,11 +700,11 @@ int Engine::finalize() {
   void* dwp = nullptr;
   T2P_TRY(upload_matrix(pool_, dw, DT_F32, &dwp));
   dense_all_.w = dwp;
-  dense_all_.N = temb_total_;
+  dense_all_.N = arch_.temb_total;
   dense_all_.K = td;
   T2P_TRY(upload_f32(db, &dense_all_.b));
-  T2P_TRY(upload_norm("out.0", final_ch_, gn_groups(final_ch_), &head_norm_));
-  T2P_TRY(upload_linear("out.2.weight", "out.2.bias", cfg_.num_channels, 9 * final_ch_, &head_conv_, true));
+  T2P_TRY(upload_norm("out.0", arch_.final_ch, gn_groups(arch_.final_ch), &head_norm_));
+  T2P_TRY(upload_linear("out.2.weight", "out.2.bias", cfg_.num_channels, 9 * arch_.final_ch, &head_conv_, true));
 
   // 1 / sigmas[label]: sigmas = exp(linspace(log sigma_max, log sigma_min, N)) in float64
   // (models/utils.py:50-60); the reference divides by the float64 value (ncsnpp.py:259-261).
@@ -1511,9 +1511,9 @@ int Engine::set_context(const float* ctx, int B, int T, hipStream_t s) {
     T2P_TRY(project_vt(dt, l.a2_v, cx, D, B, T, Tpad, l.ctx_vt, s));
     return T2P_OK;
   };
-  for (Stage& st : input_stages_) for (Layer& l : st.layers) T2P_TRY(each(l));
-  for (Layer& l : mid_stage_.layers) T2P_TRY(each(l));
-  for (Stage& st : out_stages_) for (Layer& l : st.layers) T2P_TRY(each(l));
+  for (Stage& st : arch_.input_stages) for (Layer& l : st.layers) T2P_TRY(each(l));
+  for (Layer& l : arch_.mid_stage.layers) T2P_TRY(each(l));
+  for (Stage& st : arch_.out_stages) for (Layer& l : st.layers) T2P_TRY(each(l));
   pool_.put(conv);
   ctx_B_ = B; ctx_T_ = T; ctx_Tpad_ = (int)Tpad;
   return T2P_OK;
@@ -1528,20 +1528,20 @@ int Engine::score(const float* x, const int* labels, const int* step_counter, fl
   const int R = labels ? B : 1;
   PoolLease lease(pool_);                              // whatever an early return below leaves checked out goes back to the pool
   g_tap_counter = 0;
-  std::unique_ptr<LayerScope> pre_scope(new LayerScope("pre,pre," + std::to_string(L) + "," + std::to_string(Cx) + "," + std::to_string(nf_), s));
-  POOL_GET(emb, float*, (size_t)R * nf_ * 4);
-  POOL_GET(t1, float*, (size_t)R * temb_dim_ * 4);
-  POOL_GET(t2, float*, (size_t)R * temb_dim_ * 4);
-  POOL_GET(tb, float*, (size_t)R * temb_total_ * 4);
+  std::unique_ptr<LayerScope> pre_scope(new LayerScope("pre,pre," + std::to_string(L) + "," + std::to_string(Cx) + "," + std::to_string(arch_.nf), s));
+  POOL_GET(emb, float*, (size_t)R * arch_.nf * 4);
+  POOL_GET(t1, float*, (size_t)R * arch_.temb_dim * 4);
+  POOL_GET(t2, float*, (size_t)R * arch_.temb_dim * 4);
+  POOL_GET(tb, float*, (size_t)R * arch_.temb_total * 4);
   T2P_REQUIRE(!labels_f || labels, "fractional labels come with integer labels (sigma index)");
   T2P_REQUIRE(!label_table || (!labels && step_counter), "a label table goes with the device step counter");
   T2P_REQUIRE(!label_f_table || label_table, "the fractional label table goes with the integer one (sigma index)");
-  T2P_TRY(launch_timestep_embedding(labels, labels_f, step_counter, emb, R, nf_, s, label_table, N, label_f_table));
-  T2P_TRY(launch_small_linear(emb, (const float*)pre0_.w, pre0_.b, t1, R, nf_, temb_dim_, 0, s));
-  T2P_TRY(launch_small_linear(t1, (const float*)pre1_.w, pre1_.b, t2, R, temb_dim_, temb_dim_, 0, s));
-  T2P_TRY(launch_small_linear(t2, (const float*)dense_all_.w, dense_all_.b, tb, R, temb_dim_, temb_total_, 1, s));
+  T2P_TRY(launch_timestep_embedding(labels, labels_f, step_counter, emb, R, arch_.nf, s, label_table, N, label_f_table));
+  T2P_TRY(launch_small_linear(emb, (const float*)pre0_.w, pre0_.b, t1, R, arch_.nf, arch_.temb_dim, 0, s));
+  T2P_TRY(launch_small_linear(t1, (const float*)pre1_.w, pre1_.b, t2, R, arch_.temb_dim, arch_.temb_dim, 0, s));
+  T2P_TRY(launch_small_linear(t2, (const float*)dense_all_.w, dense_all_.b, tb, R, arch_.temb_dim, arch_.temb_total, 1, s));
   tb_ = tb;
-  tb_ld_ = labels ? temb_total_ : 0;
+  tb_ld_ = labels ? arch_.temb_total : 0;
   POOL_GET(scale, float*, (size_t)B * 4);
   if (cfg_.scale_by_sigma) {
     T2P_TRY(launch_gather_label(labels, step_counter, inv_sigma_, scale, B, N, s, label_table));
@@ -1551,35 +1551,35 @@ int Engine::score(const float* x, const int* labels, const int* step_counter, fl
     T2P_HIP_CHECK(hipStreamSynchronize(s));
   }
   const bool hlp = res_lowp() && (Cx == 5 || Cx == 8) && pre_conv_direct_;   // the residual stream starts here
-  POOL_GET(h0, float*, (size_t)B * HW * nf_ * (hlp ? dtype_size(dtype()) : 4));
+  POOL_GET(h0, float*, (size_t)B * HW * arch_.nf * (hlp ? dtype_size(dtype()) : 4));
   float* h0_stats = nullptr;
   if ((Cx == 5 || Cx == 8) && pre_conv_direct_) {
     // 16-bit modes: the GroupNorm column statistics of h0 (read by the first block and, through the skip stack, by the last
     // stage) come out of the input convolution instead of two passes over the tensor
-    if (hlp && g_fuse_gn_stats && pre_conv_fuses_col_stats(L, nf_) && !(g_gn_small && HW <= 64)) {
-      h0_stats = (float*)pool_.get((size_t)B * (HW / 64) * nf_ * 2 * 4);
+    if (hlp && g_fuse_gn_stats && pre_conv_fuses_col_stats(L, arch_.nf) && !(g_gn_small && HW <= 64)) {
+      h0_stats = (float*)pool_.get((size_t)B * (HW / 64) * arch_.nf * 2 * 4);
       if (!h0_stats) return T2P_ERR_HIP;
     }
-    if (hlp && pre_conv_split_ && pre_conv_split_ok(dtype(), Cx, L, L, nf_))
-      T2P_TRY(launch_pre_conv_split(x, pre_conv_split_, pre_conv_.b, h0, dtype(), B, Cx, L, L, nf_, s, h0_stats));
+    if (hlp && pre_conv_split_ && pre_conv_split_ok(dtype(), Cx, L, L, arch_.nf))
+      T2P_TRY(launch_pre_conv_split(x, pre_conv_split_, pre_conv_.b, h0, dtype(), B, Cx, L, L, arch_.nf, s, h0_stats));
     else
-      T2P_TRY(launch_pre_conv(x, pre_conv_direct_, pre_conv_.b, h0, hlp ? dtype() : DT_F32, B, Cx, L, L, nf_, s, h0_stats));
+      T2P_TRY(launch_pre_conv(x, pre_conv_direct_, pre_conv_.b, h0, hlp ? dtype() : DT_F32, B, Cx, L, L, arch_.nf, s, h0_stats));
   } else {
     POOL_GET(xin, float*, (size_t)B * HW * cpad_ * 4);
     T2P_TRY(launch_nchw_to_nhwc(x, xin, B, Cx, HW, cpad_, s));
     GemmParams p;   // pre_conv always in exact fp32: the input has the dynamic range of sigma_max
     p.dtype = DT_F32; p.a_f32 = 1; p.A0 = xin; p.C0 = cpad_; p.lda0 = cpad_;
     p.taps = 9; p.H = L; p.W = L;
-    p.Bw = pre_conv_.w; p.ldb = pre_conv_.K; p.M = B * HW; p.N = nf_; p.bias_n = pre_conv_.b;
+    p.Bw = pre_conv_.w; p.ldb = pre_conv_.K; p.M = B * HW; p.N = arch_.nf; p.bias_n = pre_conv_.b;
     p.rows_per_batch = HW;
-    p.C = h0; p.c_f32 = 1; p.ldc = nf_;
+    p.C = h0; p.c_f32 = 1; p.ldc = arch_.nf;
     T2P_TRY(gemm(p, s));
     pool_.put(xin);
   }
   bool h0_lowp = hlp;
   if (res_lowp() && !hlp) {              // generic input-conv path: bring the stream to its storage type
-    POOL_GET(h0c, float*, (size_t)B * HW * nf_ * dtype_size(dtype()));
-    T2P_TRY(launch_convert(h0, h0c, dtype(), (long)B * HW * nf_, s));
+    POOL_GET(h0c, float*, (size_t)B * HW * arch_.nf * dtype_size(dtype()));
+    T2P_TRY(launch_convert(h0, h0c, dtype(), (long)B * HW * arch_.nf, s));
     pool_.put(h0);
     h0 = h0c;
     h0_lowp = true;
@@ -1588,19 +1588,19 @@ int Engine::score(const float* x, const int* labels, const int* step_counter, fl
   pre_scope.reset();
 
   std::vector<Act> hs;
-  Act h{h0, nf_, L, L, h0_stats, h0_lowp};
+  Act h{h0, arch_.nf, L, L, h0_stats, h0_lowp};
   hs.push_back(h);
-  for (size_t i = 0; i < input_stages_.size(); ++i) {
+  for (size_t i = 0; i < arch_.input_stages.size(); ++i) {
     // the stage's last block may apply the first norm of the block that follows it (next input stage, or the mid stage)
     // (run_stage owns the pre-applied norm its input carries: the first block takes it, or it is dropped there)
-    const Layer* next = i + 1 < input_stages_.size() ? &input_stages_[i + 1].layers[0] : &mid_stage_.layers[0];
-    T2P_TRY(run_stage(input_stages_[i], h, nullptr, B, s, next));
+    const Layer* next = i + 1 < arch_.input_stages.size() ? &arch_.input_stages[i + 1].layers[0] : &arch_.mid_stage.layers[0];
+    T2P_TRY(run_stage(arch_.input_stages[i], h, nullptr, B, s, next));
     hs.push_back(h);
     hs.back().pre_norm = nullptr;      // the skip-stack copy does not own the pre-applied norm
   }
   // mid stage: its input stays on the skip stack
-  T2P_TRY(run_stage(mid_stage_, h, nullptr, B, s));
-  for (Stage& st : out_stages_) {
+  T2P_TRY(run_stage(arch_.mid_stage, h, nullptr, B, s));
+  for (Stage& st : arch_.out_stages) {
     Act skip = hs.back();
     hs.pop_back();
     T2P_REQUIRE(skip.C == st.skip_ch && skip.H == h.H, "skip stack mismatch");
@@ -1612,11 +1612,11 @@ int Engine::score(const float* x, const int* labels, const int* step_counter, fl
   }
   T2P_REQUIRE(hs.empty(), "skip stack not consumed");
   // head: GroupNorm -> SiLU -> conv3x3 (nf -> C), stored NCHW and divided by sigma[label]
-  LayerScope head_scope("head,head," + std::to_string(L) + "," + std::to_string(final_ch_) + "," + std::to_string(Cx), s);
+  LayerScope head_scope("head,head," + std::to_string(L) + "," + std::to_string(arch_.final_ch) + "," + std::to_string(Cx), s);
   void* a = nullptr;
   {
     GemmParams p;
-    p.dtype = dtype(); p.a_f32 = p.dtype == DT_F32; p.C0 = final_ch_; p.lda0 = final_ch_;
+    p.dtype = dtype(); p.a_f32 = p.dtype == DT_F32; p.C0 = arch_.final_ch; p.lda0 = arch_.final_ch;
     p.taps = 9; p.H = L; p.W = L;
     p.Bw = head_conv_.w; p.ldb = head_conv_.K; p.M = B * HW; p.N = Cx; p.bias_n = head_conv_.b;
     p.rows_per_batch = HW;

@@ -105,6 +105,16 @@ struct Stage {
   int skip_ch = 0;
 };
 
+// The network's structure: the block list in execution order, the slots of the per-block time-embedding biases and the parameter
+// table in the reference's parameters() order.  Shared by the sampling engine and the training step (train.cpp).
+struct NetArch {
+  std::vector<Stage> input_stages, out_stages;
+  Stage mid_stage;
+  std::vector<ParamInfo> params;
+  int nf = 0, temb_dim = 0, temb_total = 0, final_ch = 0;
+  int build(const t2p_model_config& c);   // checks the config
+};
+
 struct Act {  // an NHWC activation: fp32, or the compute dtype when `lowp`
   float* p = nullptr;
   int C = 0, H = 0, W = 0;
@@ -125,8 +135,8 @@ class Engine {
  public:
   explicit Engine(const t2p_model_config& cfg);
   ~Engine();
-  int build();  // structure + parameter table
-  const std::vector<ParamInfo>& params() const { return params_; }
+  int build();  // structure + parameter table (NetArch::build)
+  const std::vector<ParamInfo>& params() const { return arch_.params; }
   int load_param(const char* name, const float* data, const int64_t* shape, int ndim);
   int finalize();
   int set_context(const float* ctx, int B, int T, hipStream_t s);
@@ -171,27 +181,23 @@ class Engine {
   bool res_lowp() const { return g_lowp_residual && cfg_.compute_dtype == DT_F16; }
 
   t2p_model_config cfg_;
-  std::vector<ParamInfo> params_;
+  NetArch arch_;
   std::unordered_map<std::string, HostTensor> host_;
   bool finalized_ = false;
   DevPool pool_;
 
-  int nf_ = 0, temb_dim_ = 0, cpad_ = 0, final_ch_ = 0;
-  std::vector<Stage> input_stages_, out_stages_;
-  Stage mid_stage_;
+  int cpad_ = 8;                // channel padding of the network input
   DevLinear pre0_, pre1_, pre_conv_, head_conv_, dense_all_;
   DevNorm head_norm_;
-  int temb_total_ = 0;
   float* pre_conv_direct_ = nullptr;   // [nf][9][C] fp32 weights of the direct input convolution
   void* pre_conv_split_ = nullptr;     // the same, each weight as two f16 terms (pre_conv_split_kernel; 16-bit modes)
   float* inv_sigma_ = nullptr;  // [N] fp32, 1 / sigmas[label] (descending sigmas)
   int ctx_B_ = 0, ctx_T_ = 0, ctx_Tpad_ = 0;
   void* splitk_ws_ = nullptr;
   size_t splitk_ws_bytes_ = 0;
-  const float* tb_ = nullptr;   // per-eval temb biases [R][temb_total_]
+  const float* tb_ = nullptr;   // per-eval temb biases [R][arch_.temb_total]
   long tb_ld_ = 0;
   friend class Sampler;
-  friend class Trainer;     // train.cpp: reads the block list and the parameter table (Engine::build), nothing else
 };
 
 class Sampler {

@@ -4,19 +4,22 @@
 // loss.backward(); optimize_fn (:41-49: warm-up on state['step'], clip_grad_norm_, Adam); state['step'] += 1; ema.update
 // (models/ema.py:32-49).  Here: the parameters, their gradients, both Adam moments and the EMA shadow are five flat device buffers
 // in the reference's parameters() order (what the checkpoint loader and the optimizer kernels want); the forward pass walks the
-// same block list as the sampling engine (Engine::build), keeps the activations the backward pass needs and records one
-// closure per operator; the backward pass runs the closures in reverse.  Products: 3x3 convolutions forward and input-gradient on
-// the engine's exact-f32 implicit-GEMM kernel (the input gradient is the same convolution on dY with flipped, transposed taps),
-// everything else -- linear layers both ways, weight gradients, the attention products -- on the strided GEMM of
+// same block list as the sampling engine (NetArch::build), keeps the activations the backward pass needs and records one
+// closure per operator; the backward pass runs the closures in reverse.  Every operator is one member (linear, conv3x3, group_norm,
+// layer_norm, attention, add_scale) that runs its forward and pushes its backward.  Products: 3x3 convolutions forward and
+// input-gradient on the engine's exact-f32 implicit-GEMM kernel (the input gradient is the same convolution on dY with flipped,
+// transposed taps), everything else -- linear layers both ways, weight gradients, the attention products -- on the strided GEMM of
 // train_kernels.hip.  Every gradient buffer is zero-initialised at first use and accumulated into, so fan-out (residual
 // connections, U-Net skips, the shared time embedding) needs no special cases.
 //
 // Mixed precision (compute_dtype F16 / BF16): the residual-block convolutions run forward and data-gradient on the engine's 16-bit
 // implicit GEMM (fp32 activations rounded once into a pass-local 16-bit copy, 16-bit weight copies made by prep_weights), every strided product on
 // launch_tgemm16; the input and head convolutions (5 or 8 channels) keep the exact-f32 kernel for their forward and data gradient.
+// The dtype is looked at in three places only: tg (which strided GEMM), conv3x3 (a convolution that has 16-bit weight copies runs on
+// them) and fixed_order_ (set in build(): which form of the reduction launchers; reduce_ws hands out their workspace, or null).
 // The backward pass is seeded with S dL/do, S = 2^round(log2(B C L L)) (the fp32 seed is ~1e-5 at full size, at the bottom of
 // f16's normal range; under the VP / sub-VP SDE S is chosen on the device from max|dL/do|), and S is divided out of the flat gradient buffer once at the end.  Every reduction that feeds a gradient, the
-// gradient norm or an update runs in a fixed order, so the gradients and the state after a 16-bit step are bitwise reproducible (the
+// gradient norm or an update runs in a fixed order (fixed_order_), so the gradients and the state after a 16-bit step are bitwise reproducible (the
 // scalar loss itself is still summed with double atomics, shared with the fp32 step).  apply() refuses (and changes nothing) when the
 // loss or the gradient norm is not finite.
 #include "train.h"
@@ -29,7 +32,7 @@ namespace t2p {
 
 static int gn_groups_of(int c) { return std::min(c / 4, 32); }   // layers.py:282
 
-Trainer::Trainer(const t2p_model_config& mc, const t2p_train_config& tc) : mc_(mc), tc_(tc), arch_(mc) {}
+Trainer::Trainer(const t2p_model_config& mc, const t2p_train_config& tc) : mc_(mc), tc_(tc) {}
 Trainer::~Trainer() {}
 
 long Trainer::poff(const std::string& name, std::vector<int64_t> shape) {
@@ -104,12 +107,13 @@ int Trainer::build() {
   T2P_REQUIRE(mc_.compute_dtype == DT_F32 || mc_.compute_dtype == DT_F16 || mc_.compute_dtype == DT_BF16,
               "the training step computes in f32, f16 or bf16");
   dt_ = mc_.compute_dtype;
+  fixed_order_ = dt_ != DT_F32;            // the 16-bit step is bitwise reproducible; the f32 step keeps its atomic reductions
   T2P_REQUIRE(tc_.dropout >= 0.0 && tc_.dropout < 1.0 && tc_.ema_rate >= 0.0 && tc_.ema_rate <= 1.0, "dropout / ema_rate");
   int dev = 0;
   T2P_HIP_CHECK(hipGetDevice(&dev));       // fails without a HIP device: there is no CPU fallback
-  T2P_TRY(arch_.build());
+  T2P_TRY(arch_.build(mc_));
   long off = 0;
-  for (const ParamInfo& p : arch_.params()) {
+  for (const ParamInfo& p : arch_.params) {
     TParam t;
     t.name = p.name; t.shape = p.shape; t.off = off; t.n = 1;
     for (int64_t d : p.shape) t.n *= d;
@@ -143,10 +147,10 @@ int Trainer::build() {
     }
     return T2P_OK;
   };
-  for (const Stage& st : arch_.input_stages_) { in_stages_.emplace_back(); T2P_TRY(map_stage(st, &in_stages_.back())); }
-  T2P_TRY(map_stage(arch_.mid_stage_, &mid_));
-  for (const Stage& st : arch_.out_stages_) { out_stages_.emplace_back(); T2P_TRY(map_stage(st, &out_stages_.back())); }
-  const int fc = arch_.final_ch_;
+  for (const Stage& st : arch_.input_stages) { in_stages_.emplace_back(); T2P_TRY(map_stage(st, &in_stages_.back())); }
+  T2P_TRY(map_stage(arch_.mid_stage, &mid_));
+  for (const Stage& st : arch_.out_stages) { out_stages_.emplace_back(); T2P_TRY(map_stage(st, &out_stages_.back())); }
+  const int fc = arch_.final_ch;
   T2P_OFF(head_norm_.g, "out.0.weight", fc); T2P_OFF(head_norm_.b, "out.0.bias", fc);
   head_norm_.C = fc; head_norm_.G = gn_groups_of(fc);
   T2P_OFF(head_conv_.w, "out.2.weight", ch, fc, 3, 3); T2P_OFF(head_conv_.b, "out.2.bias", ch);
@@ -177,7 +181,7 @@ int Trainer::build() {
       if (!c->wf16 || !c->wd16) return T2P_ERR_HIP;
     }
   }
-  if (dt_ != DT_F32) {
+  if (fixed_order_) {
     sumsq_part_ = (double*)pool_.persistent(1024 * 8);
     if (!sumsq_part_) return T2P_ERR_HIP;
   }
@@ -299,15 +303,16 @@ int Trainer::prep_weights(const float* P, hipStream_t s) {
   return T2P_OK;
 }
 
-// out += column sums of dy (bias gradients): ld_out == 0 -> over all `rows` (launch_colsum); else per sample, nz samples of `rows` rows
-// each, into out [nz][ld_out] (launch_colsum_per_sample)
-int Trainer::colsum(const float* dy, int nz, long rows, int N, long ld, float* out, long ld_out) {
-  if (dt_ == DT_F32) return ld_out == 0 ? launch_colsum(dy, rows, N, ld, out, s_) : launch_colsum_per_sample(dy, nz, (int)rows, N, out, ld_out, 1, s_);
-  float* ws = (float*)pool_.get((size_t)colsum_fixed_ws_floats(nz, rows, N) * 4);
-  if (!ws) return T2P_ERR_HIP;
-  const int rc = launch_colsum_fixed(dy, nz, rows, N, ld, out, ld_out == 0 ? N : ld_out, 1, ws, s_);
-  pool_.put(ws);
-  return rc;
+int Trainer::reduce_ws(long floats, float** ws) {
+  *ws = fixed_order_ ? tmp((size_t)floats * 4) : nullptr;
+  return fixed_order_ && !*ws ? T2P_ERR_HIP : T2P_OK;
+}
+
+// out [nz][N] += the column sums of the nz blocks of `rows` rows of dy: nz = 1 a bias gradient, nz = B the per-sample time-embedding bias
+int Trainer::colsum(const float* dy, int nz, long rows, int N, long ld, float* out) {
+  float* ws = nullptr;
+  T2P_TRY(reduce_ws(colsum_ws_floats(nz, rows, N), &ws));
+  return launch_colsum(dy, nz, rows, N, ld, out, N, 1, ws, s_);
 }
 
 int Trainer::tg(const TGemmArgs& a) {
@@ -324,32 +329,58 @@ int Trainer::tg(const TGemmArgs& a) {
 }
 
 // ---- operators -----------------------------------------------------------------------------------------------------------------------------
-// y [B][H W][ldc] = conv3x3(x) + bias (+ bias_bn[b][:]: Dense_0(act(temb)) of the block, layers.py:316) (+ residual_inplace, which may be y:
-// the register-staged kernel reads and writes an output element in the same thread) on the engine's exact-f32 implicit-GEMM kernel, or
-// with dtype F16 / BF16 on its 16-bit kernels: x16 = x rounded to dtype (the layout x has), w16 = the 16-bit copy of w
-static int conv_forward(const float* x, int B, int H, int W, int Cin, const float* w, long ldb, const float* bias, const float* bias_bn, int N,
-                        float* y, long ldc, const float* residual_inplace, hipStream_t s, int dtype = DT_F32, const void* w16 = nullptr,
-                        const void* x16 = nullptr) {
+// y [B][H W][ldc] = conv3x3(x) + bias (+ bias_bn[b][:]) (+ residual_inplace, which may be y: the register-staged kernel reads and writes
+// an output element in the same thread), N columns written.  w16 == nullptr: the engine's exact-f32 implicit-GEMM kernel on w; else its
+// 16-bit kernels on w16 (the LDS-DMA implicit GEMM takes 16-bit A only: x is rounded once into a pass-local 16-bit copy)
+int Trainer::conv_gemm(const float* x, int B, int H, int W, int Cin, const float* w, const void* w16, long ldb, const float* bias,
+                       const float* bias_bn, int N, float* y, long ldc, const float* residual_inplace) {
   GemmParams p;
-  p.dtype = dtype; p.a_f32 = 1; p.A0 = x; p.C0 = Cin; p.lda0 = Cin; p.taps = 9; p.H = H; p.W = W;
-  if (dtype != DT_F32) { p.a_f32 = 0; p.A0 = x16; }
-  p.Bw = dtype == DT_F32 ? (const void*)w : w16; p.ldb = ldb; p.M = B * H * W; p.N = N; p.bias_n = bias; p.bias_bn = bias_bn; p.rows_per_batch = H * W; p.ld_bn = N;
+  p.dtype = DT_F32; p.a_f32 = 1; p.A0 = x; p.C0 = Cin; p.lda0 = Cin; p.taps = 9; p.H = H; p.W = W;
+  p.Bw = w; p.ldb = ldb; p.M = B * H * W; p.N = N; p.bias_n = bias; p.bias_bn = bias_bn; p.rows_per_batch = H * W; p.ld_bn = N;
   p.R = residual_inplace; p.ldr = ldc;
   p.C = y; p.c_f32 = 1; p.ldc = ldc;
-  return launch_gemm(p, s);
-}
-
-// a residual-block 3x3 convolution in 16-bit modes: the fp32 input is rounded once into a pass-local 16-bit copy, so the engine's
-// LDS-DMA implicit GEMM (16-bit A only) takes the layers it covers
-int Trainer::conv16(const float* x, int B, int H, int W, int Cin, const void* w16, long ldb, const float* bias, const float* bias_bn, int N,
-                    float* y, long ldc, const float* residual_inplace) {
+  if (!w16) return launch_gemm(p, s_);
   const long n = (long)B * H * W * Cin;
   void* x16 = pool_.get((size_t)n * 2);
   if (!x16) return T2P_ERR_HIP;
+  p.dtype = dt_; p.a_f32 = 0; p.A0 = x16; p.Bw = w16;
   int rc = launch_convert(x, x16, dt_, n, s_);
-  if (rc == T2P_OK) rc = conv_forward(x, B, H, W, Cin, nullptr, ldb, bias, bias_bn, N, y, ldc, residual_inplace, s_, dt_, w16, x16);
+  if (rc == T2P_OK) rc = launch_gemm(p, s_);
   pool_.put(x16);                  // stream-ordered: the next user of the block runs after this convolution
   return rc;
+}
+
+// y [B][H W][Cop] = conv3x3(x [B][H W][Cip]) + bias (+ tbias[b][:]: Dense_0(act(temb)) of the block, layers.py:316); Co of the Cop
+// columns are written (the head convolution: Cop = 8 > Co, the rest zero).  c.wf16 (the residual-block convolutions in 16-bit
+// modes) selects the 16-bit implicit GEMM for the forward and the data gradient; the input and head convolutions keep the exact-f32 kernel
+int Trainer::conv3x3(TT* x, const Conv& c, TT* tbias, TT** out) {
+  T2P_REQUIRE(x->C == c.Cip && (!tbias || (tbias->C == c.Co && c.Cop == c.Co)), "conv3x3 channels");
+  T2P_ACT(y, x->B, x->H, x->W, c.Cop);
+  if (c.Cop != c.Co) T2P_HIP_CHECK(hipMemsetAsync(y->p, 0, (size_t)y->numel() * 4, s_));
+  T2P_TRY(conv_gemm(x->p, x->B, x->H, x->W, c.Cip, c.wf, c.wf16, 9L * c.Cip, Pc_ + c.b, tbias ? tbias->p : nullptr, c.Co, y->p, c.Cop, nullptr));
+  *out = y;
+  const Conv C = c;
+  tape_.push_back([this, x, y, C, tbias]() -> int {
+    if (!y->g) return T2P_OK;
+    const long rows = x->rows();
+    if (x->needs_grad) {                           // dX = conv3x3(dY, flipped transposed taps), accumulated in place through the residual operand
+      T2P_GRAD(gx, x);
+      T2P_TRY(conv_gemm(y->g, x->B, x->H, x->W, C.Cop, C.wd, C.wd16, 9L * C.Cop, nullptr, nullptr, C.Ci, gx, C.Cip, gx));
+    }
+    T2P_HIP_CHECK(hipMemsetAsync(dwc_, 0, (size_t)C.Co * 9 * C.Cip * 4, s_));
+    TGemmArgs w;                                   // dW[co][tap][ci] = sum_pixels dY[pixel][co] X[pixel + tap][ci]
+    w.A = y->g; w.sAm = 1; w.sAk = C.Cop; w.B = x->p; w.conv_b = 1; w.H = x->H; w.W = x->W; w.conv_C = C.Cip; w.ldx = C.Cip;
+    w.C = dwc_; w.ldc = 9L * C.Cip; w.M = C.Co; w.N = 9 * C.Cip; w.K = (int)rows; w.beta = 1.f; w.ksplit = 0;
+    T2P_TRY(tg(w));
+    T2P_TRY(launch_conv_w_grad_fold(dwc_, Gr_ + C.w, C.Co, C.Ci, C.Cip, s_));
+    T2P_TRY(colsum(y->g, 1, rows, C.Co, C.Cop, Gr_ + C.b));
+    if (tbias) {
+      T2P_GRAD(gt, tbias);
+      T2P_TRY(colsum(y->g, x->B, (long)x->H * x->W, C.Co, C.Cop, gt));
+    }
+    return T2P_OK;
+  });
+  return T2P_OK;
 }
 
 int Trainer::linear(TT* x, const Lin& l, TT** out) {
@@ -380,7 +411,7 @@ int Trainer::linear(TT* x, const Lin& l, TT** out) {
     else        { w.A = x->p; w.sAm = 1; w.sAk = L.K; w.B = y->g; w.sBk = L.N; w.sBn = 1; w.M = L.K; w.N = L.N; }
     w.C = Gr_ + L.w; w.ldc = w.N; w.K = (int)rows; w.beta = 1.f; w.ksplit = 0;
     T2P_TRY(tg(w));
-    if (L.b >= 0) T2P_TRY(colsum(y->g, 1, rows, L.N, L.N, Gr_ + L.b, 0));
+    if (L.b >= 0) T2P_TRY(colsum(y->g, 1, rows, L.N, L.N, Gr_ + L.b));
     return T2P_OK;
   });
   return T2P_OK;
@@ -408,8 +439,7 @@ int Trainer::group_norm(TT* x, const Norm& n, int silu, TT** out) {
     T2P_GRAD(gx, x);
     float* ws = tmp((size_t)gn_bwd_ws_floats(B, HW, N.C, N.G) * 4);
     if (!ws) return T2P_ERR_HIP;
-    if (dt_ != DT_F32) return launch_gn_backward_fixed(x->p, y->g, stats, Pc_ + N.g, Pc_ + N.b, silu, B, HW, N.C, N.G, gx, Gr_ + N.g, Gr_ + N.b, ws, s_);
-    return launch_gn_backward(x->p, y->g, stats, Pc_ + N.g, Pc_ + N.b, silu, B, HW, N.C, N.G, gx, Gr_ + N.g, Gr_ + N.b, ws, s_);
+    return launch_gn_backward(x->p, y->g, stats, Pc_ + N.g, Pc_ + N.b, silu, B, HW, N.C, N.G, gx, Gr_ + N.g, Gr_ + N.b, ws, fixed_order_, s_);
   });
   return T2P_OK;
 }
@@ -423,15 +453,18 @@ int Trainer::layer_norm(TT* x, const Norm& n, TT** out) {
   tape_.push_back([this, x, y, N]() -> int {
     if (!y->g) return T2P_OK;
     T2P_GRAD(gx, x);
-    if (dt_ != DT_F32) {
-      float* ws = tmp((size_t)ln_bwd_fixed_ws_floats(x->rows(), N.C) * 4);
-      if (!ws) return T2P_ERR_HIP;
-      return launch_ln_backward_fixed(x->p, y->g, Pc_ + N.g, x->rows(), N.C, 1e-5f, gx, Gr_ + N.g, Gr_ + N.b, ws, s_);
-    }
-    return launch_ln_backward(x->p, y->g, Pc_ + N.g, x->rows(), N.C, 1e-5f, gx, Gr_ + N.g, Gr_ + N.b, s_);
+    float* ws = nullptr;
+    T2P_TRY(reduce_ws(ln_bwd_ws_floats(x->rows(), N.C), &ws));
+    return launch_ln_backward(x->p, y->g, Pc_ + N.g, x->rows(), N.C, 1e-5f, gx, Gr_ + N.g, Gr_ + N.b, ws, s_);
   });
   return T2P_OK;
 }
+
+// one operand of a product batched over (sample b, head h): element (row, col) at p[b z0 + h z1 + row s_row + col s_col]
+struct HeadOp {
+  float* p; long s_row, s_col, z0, z1;
+  HeadOp t() const { return {p, s_col, s_row, z0, z1}; }      // the transposed view
+};
 
 // softmax(scale q k^T) v per (sample, head): q [B][nq][C], k, v [B][nk][C], head h = columns [h d, (h + 1) d)
 // (CrossAttention.forward, attention.py:170-191; AttnBlockpp with one head of width C, layers.py:168-172)
@@ -443,54 +476,37 @@ int Trainer::attention(TT* q, TT* k, TT* v, int heads, float scale, TT** out) {
   float* S = tmp(pbytes);
   float* P = tmp(pbytes);
   if (!S || !P) return T2P_ERR_HIP;
-  auto heads_of = [&](TGemmArgs& a) { a.nz0 = B; a.nz1 = heads; };
-  TGemmArgs a;                                   // S = q k^T
-  a.A = q->p; a.sAm = C; a.sAk = 1; a.sAz0 = (long)nq * C; a.sAz1 = d;
-  a.B = k->p; a.sBk = 1; a.sBn = C; a.sBz0 = (long)nk * C; a.sBz1 = d;
-  a.C = S; a.ldc = nk; a.sCz0 = (long)heads * nq * nk; a.sCz1 = (long)nq * nk; a.M = nq; a.N = nk; a.K = d;
-  heads_of(a);
-  T2P_TRY(tg(a));
+  // the two kinds of operand: an activation [B][n][C] seen per head as [n][d], and a score buffer [B][heads][nq][nk]
+  auto act_op = [C, d](float* p, int n) { return HeadOp{p, C, 1, (long)n * C, d}; };
+  auto score_op = [heads, nq, nk](float* p) { return HeadOp{p, nk, 1, (long)heads * nq * nk, (long)nq * nk}; };
+  auto prod = [this, B, heads](const HeadOp& a, const HeadOp& b, const HeadOp& c, int M, int N, int K, float beta) -> int {   // c = a b + beta c
+    TGemmArgs g;
+    g.A = a.p; g.sAm = a.s_row; g.sAk = a.s_col; g.sAz0 = a.z0; g.sAz1 = a.z1;
+    g.B = b.p; g.sBk = b.s_row; g.sBn = b.s_col; g.sBz0 = b.z0; g.sBz1 = b.z1;
+    g.C = c.p; g.ldc = c.s_row; g.sCz0 = c.z0; g.sCz1 = c.z1;
+    g.M = M; g.N = N; g.K = K; g.nz0 = B; g.nz1 = heads; g.beta = beta;
+    return tg(g);
+  };
+  T2P_TRY(prod(act_op(q->p, nq), act_op(k->p, nk).t(), score_op(S), nq, nk, d, 0.f));           // S = q k^T
   T2P_TRY(launch_softmax(S, nk, P, nk, DT_F32, (long)B * heads * nq, nk, scale, s_));
-  TGemmArgs b;                                   // o = P v
-  b.A = P; b.sAm = nk; b.sAk = 1; b.sAz0 = (long)heads * nq * nk; b.sAz1 = (long)nq * nk;
-  b.B = v->p; b.sBk = C; b.sBn = 1; b.sBz0 = (long)nk * C; b.sBz1 = d;
-  b.C = o->p; b.ldc = C; b.sCz0 = (long)nq * C; b.sCz1 = d; b.M = nq; b.N = d; b.K = nk;
-  heads_of(b);
-  T2P_TRY(tg(b));
+  T2P_TRY(prod(score_op(P), act_op(v->p, nk), act_op(o->p, nq), nq, d, nk, 0.f));               // o = P v
   *out = o;
-  tape_.push_back([this, q, k, v, o, P, S, B, heads, nq, nk, C, d, scale]() -> int {
+  tape_.push_back([this, q, k, v, o, P, S, B, heads, nq, nk, d, scale, act_op, score_op, prod]() -> int {
     if (!o->g) return T2P_OK;
-    const long sP0 = (long)heads * nq * nk, sP1 = (long)nq * nk;
     float* dP = S;                               // the raw scores are dead: their buffer takes dP, then dS
-    TGemmArgs e;                                 // dP = dO v^T
-    e.A = o->g; e.sAm = C; e.sAk = 1; e.sAz0 = (long)nq * C; e.sAz1 = d;
-    e.B = v->p; e.sBk = 1; e.sBn = C; e.sBz0 = (long)nk * C; e.sBz1 = d;
-    e.C = dP; e.ldc = nk; e.sCz0 = sP0; e.sCz1 = sP1; e.M = nq; e.N = nk; e.K = d; e.nz0 = B; e.nz1 = heads;
-    T2P_TRY(tg(e));
+    T2P_TRY(prod(act_op(o->g, nq), act_op(v->p, nk).t(), score_op(dP), nq, nk, d, 0.f));        // dP = dO v^T
     if (v->needs_grad) {                         // dv += P^T dO
       T2P_GRAD(gv, v);
-      TGemmArgs f;
-      f.A = P; f.sAm = 1; f.sAk = nk; f.sAz0 = sP0; f.sAz1 = sP1;
-      f.B = o->g; f.sBk = C; f.sBn = 1; f.sBz0 = (long)nq * C; f.sBz1 = d;
-      f.C = gv; f.ldc = C; f.sCz0 = (long)nk * C; f.sCz1 = d; f.M = nk; f.N = d; f.K = nq; f.nz0 = B; f.nz1 = heads; f.beta = 1.f;
-      T2P_TRY(tg(f));
+      T2P_TRY(prod(score_op(P).t(), act_op(o->g, nq), act_op(gv, nk), nk, d, nq, 1.f));
     }
     T2P_TRY(launch_softmax_backward(P, dP, (long)B * heads * nq, nk, scale, s_));     // dS (w.r.t. the raw scores q k^T)
     if (q->needs_grad) {                         // dq += dS k
       T2P_GRAD(gq, q);
-      TGemmArgs f;
-      f.A = dP; f.sAm = nk; f.sAk = 1; f.sAz0 = sP0; f.sAz1 = sP1;
-      f.B = k->p; f.sBk = C; f.sBn = 1; f.sBz0 = (long)nk * C; f.sBz1 = d;
-      f.C = gq; f.ldc = C; f.sCz0 = (long)nq * C; f.sCz1 = d; f.M = nq; f.N = d; f.K = nk; f.nz0 = B; f.nz1 = heads; f.beta = 1.f;
-      T2P_TRY(tg(f));
+      T2P_TRY(prod(score_op(dP), act_op(k->p, nk), act_op(gq, nq), nq, d, nk, 1.f));
     }
     if (k->needs_grad) {                         // dk += dS^T q
       T2P_GRAD(gk, k);
-      TGemmArgs f;
-      f.A = dP; f.sAm = 1; f.sAk = nk; f.sAz0 = sP0; f.sAz1 = sP1;
-      f.B = q->p; f.sBk = C; f.sBn = 1; f.sBz0 = (long)nq * C; f.sBz1 = d;
-      f.C = gk; f.ldc = C; f.sCz0 = (long)nk * C; f.sCz1 = d; f.M = nk; f.N = d; f.K = nq; f.nz0 = B; f.nz1 = heads; f.beta = 1.f;
-      T2P_TRY(tg(f));
+      T2P_TRY(prod(score_op(dP).t(), act_op(q->p, nq), act_op(gk, nk), nk, d, nq, 1.f));
     }
     return T2P_OK;
   });
@@ -514,8 +530,8 @@ int Trainer::add_scale(TT* a, TT* b, float alpha, TT** out) {
   return T2P_OK;
 }
 
-// ResnetBlockBigGANpp.forward in train mode (layers.py:303-327)
-int Trainer::res_block(const LayerT& L, TT* x, TT* stemb, TT** out) {
+// ResnetBlockBigGANpp.forward (layers.py:303-327); Dropout_0 is active in train mode only
+int Trainer::res_block(const LayerT& L, TT* x, TT* stemb, bool train, TT** out) {
   const ResL& r = L.r;
   const int B = x->B;
   const float alpha = mc_.skip_rescale ? (float)(1.0 / std::sqrt(2.0)) : 1.f;
@@ -541,43 +557,14 @@ int Trainer::res_block(const LayerT& L, TT* x, TT* stemb, TT** out) {
     }
     a0 = dst[0]; xs = dst[1];
   }
-  const int H = a0->H, W = a0->W, HW = H * W;
-  TT* tb = nullptr;                                // Dense_0(act(temb)) [B][Cout]
+  T2P_REQUIRE(r.c0.Cop == r.c0.Co && r.c1.Cop == r.c1.Co && r.c1.Cip == r.c1.Ci, "residual block channels are multiples of 8");
+  TT *tb = nullptr, *h = nullptr;                  // h = Conv_0(a0) + bias + Dense_0(act(temb)) [B][Cout]
   T2P_TRY(linear(stemb, r.dense, &tb));
-  // h = Conv_0(a0) + bias + tb
-  T2P_REQUIRE(a0->C == r.c0.Cip && r.c0.Cop == r.c0.Co && r.c1.Cop == r.c1.Co && r.c1.Cip == r.c1.Ci, "residual block channels are multiples of 8");
-  T2P_ACT(h, B, H, W, r.c0.Co);
-  if (dt_ == DT_F32) T2P_TRY(conv_forward(a0->p, B, H, W, a0->C, r.c0.wf, 9L * r.c0.Cip, Pc_ + r.c0.b, tb->p, r.c0.Co, h->p, r.c0.Co, nullptr, s_));
-  else T2P_TRY(conv16(a0->p, B, H, W, a0->C, r.c0.wf16, 9L * r.c0.Cip, Pc_ + r.c0.b, tb->p, r.c0.Co, h->p, r.c0.Co, nullptr));
-  auto conv_backward = [this](TT* in, TT* y, const Conv c, TT* tbias) -> int {
-    if (!y->g) return T2P_OK;
-    const int Bq = in->B, Hq = in->H, Wq = in->W;
-    const long rows = in->rows();
-    if (in->needs_grad) {                          // dX = conv3x3(dY, flipped transposed taps), accumulated in place through the residual operand
-      T2P_GRAD(gi, in);
-      if (dt_ == DT_F32) T2P_TRY(conv_forward(y->g, Bq, Hq, Wq, c.Cop, c.wd, 9L * c.Cop, nullptr, nullptr, c.Ci, gi, in->C, gi, s_));
-      else T2P_TRY(conv16(y->g, Bq, Hq, Wq, c.Cop, c.wd16, 9L * c.Cop, nullptr, nullptr, c.Ci, gi, in->C, gi));
-    }
-    T2P_HIP_CHECK(hipMemsetAsync(dwc_, 0, (size_t)c.Co * 9 * c.Cip * 4, s_));
-    TGemmArgs w;                                   // dW[co][tap][ci] = sum_pixels dY[pixel][co] X[pixel + tap][ci]
-    w.A = y->g; w.sAm = 1; w.sAk = y->C; w.B = in->p; w.conv_b = 1; w.H = Hq; w.W = Wq; w.conv_C = c.Cip; w.ldx = in->C;
-    w.C = dwc_; w.ldc = 9L * c.Cip; w.M = c.Co; w.N = 9 * c.Cip; w.K = (int)rows; w.beta = 1.f; w.ksplit = 0;
-    T2P_TRY(tg(w));
-    T2P_TRY(launch_conv_w_grad_fold(dwc_, Gr_ + c.w, c.Co, c.Ci, c.Cip, s_));
-    T2P_TRY(colsum(y->g, 1, rows, c.Co, y->C, Gr_ + c.b, 0));
-    if (tbias) {
-      T2P_GRAD(gt, tbias);
-      T2P_TRY(colsum(y->g, Bq, (long)Hq * Wq, c.Co, c.Co, gt, c.Co));
-    }
-    return T2P_OK;
-  };
-  {
-    const Conv c = r.c0;
-    tape_.push_back([conv_backward, a0, h, c, tb]() -> int { return conv_backward(a0, h, c, tb); });
-  }
+  T2P_TRY(conv3x3(a0, r.c0, tb, &h));
   TT* a1 = nullptr;
   T2P_TRY(group_norm(h, r.gn1, 1, &a1));
-  if (tc_.dropout > 0.0) {                         // Dropout_0 (layers.py:318)
+  const double drop_p = train ? tc_.dropout : 0.0; // eval mode: models/utils.py:113-115
+  if (drop_p > 0.0) {                              // Dropout_0 (layers.py:318)
     const long n = a1->numel();
     const uint8_t* keep = nullptr;
     if (!drop_masks_.empty()) {
@@ -586,11 +573,11 @@ int Trainer::res_block(const LayerT& L, TT* x, TT* stemb, TT** out) {
     } else {
       uint8_t* m = (uint8_t*)tmp((size_t)n);
       if (!m) return T2P_ERR_HIP;
-      T2P_TRY(launch_dropout_mask(m, n, (float)tc_.dropout, tc_.seed, (unsigned long long)(loss_calls_ * 4096 + 16 + drop_index_), s_));
+      T2P_TRY(launch_dropout_mask(m, n, (float)drop_p, tc_.seed, rng_dropout(drop_index_), s_));
       keep = m;
     }
     ++drop_index_;
-    const float inv_keep = (float)(1.0 / (1.0 - tc_.dropout));
+    const float inv_keep = (float)(1.0 / (1.0 - drop_p));
     T2P_ACT(y, a1->B, a1->H, a1->W, a1->C);
     T2P_TRY(launch_dropout(a1->p, keep, inv_keep, y->p, n, 0, s_));
     TT* in = a1;
@@ -601,16 +588,10 @@ int Trainer::res_block(const LayerT& L, TT* x, TT* stemb, TT** out) {
     });
     a1 = y;
   }
-  T2P_ACT(h2, B, H, W, r.c1.Co);
-  if (dt_ == DT_F32) T2P_TRY(conv_forward(a1->p, B, H, W, a1->C, r.c1.wf, 9L * r.c1.Cip, Pc_ + r.c1.b, nullptr, r.c1.Co, h2->p, r.c1.Co, nullptr, s_));
-  else T2P_TRY(conv16(a1->p, B, H, W, a1->C, r.c1.wf16, 9L * r.c1.Cip, Pc_ + r.c1.b, nullptr, r.c1.Co, h2->p, r.c1.Co, nullptr));
-  {
-    const Conv c = r.c1;
-    tape_.push_back([conv_backward, a1, h2, c]() -> int { return conv_backward(a1, h2, c, nullptr); });
-  }
+  TT* h2 = nullptr;
+  T2P_TRY(conv3x3(a1, r.c1, nullptr, &h2));
   TT* sc = xs;
   if (r.has_sc) T2P_TRY(linear(xs, r.sc, &sc));
-  (void)HW;
   return add_scale(sc, h2, alpha, out);
 }
 
@@ -666,10 +647,10 @@ int Trainer::st_block(const LayerT& L, TT* x, TT* ctx, TT** out) {
   return add_scale(po, x, 1.f, out);
 }
 
-int Trainer::run_layers(const std::vector<LayerT>& ls, TT* h, TT* stemb, TT* ctx, TT** out) {
+int Trainer::run_layers(const std::vector<LayerT>& ls, TT* h, TT* stemb, TT* ctx, bool train, TT** out) {
   for (const LayerT& l : ls) {
     TT* y = nullptr;
-    if (l.kind == 0) T2P_TRY(res_block(l, h, stemb, &y));
+    if (l.kind == 0) T2P_TRY(res_block(l, h, stemb, train, &y));
     else if (l.kind == 1) T2P_TRY(attn_block(l, h, &y));
     else T2P_TRY(st_block(l, h, ctx, &y));
     h = y;
@@ -679,7 +660,7 @@ int Trainer::run_layers(const std::vector<LayerT>& ls, TT* h, TT* stemb, TT* ctx
 }
 
 // loss_fn (losses.py:105-134) on the parameters P; with `backward`, d loss / d P accumulates into Gr_
-int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool backward, float* loss_dev, float* score_out) {
+int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool train, bool backward, float* loss_dev, float* score_out) {
   const int B = b.batch, L = mc_.max_res_num, HW = L * L, Cx = mc_.num_channels, nf = mc_.nf;
   T2P_REQUIRE(b.coords_6d && b.mask_pair && b.context && B > 0 && b.tokens > 0, "training batch");
   T2P_REQUIRE(!(tc_.cond_flags & 4) || b.mask_inpaint, "the inpainting condition needs batch.mask_inpaint");
@@ -699,19 +680,19 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool bac
   float* mean_coef = nullptr; float* labels_f = nullptr;
   if (sde_ == T2P_SDE_VE) {
     T2P_TRY(launch_dsm_prepare(b.t, B, (float)tc_.t_eps, (float)mc_.sigma_min, (float)mc_.sigma_max, mc_.num_scales,
-                               mc_.scale_by_sigma ? inv_sigma_ : nullptr, tc_.seed, (unsigned long long)loss_calls_, t_dev, stdv, labels, scale, s_));
+                               mc_.scale_by_sigma ? inv_sigma_ : nullptr, tc_.seed, rng_t(), t_dev, stdv, labels, scale, s_));
   } else {
     mean_coef = tmp(B * 4); labels_f = tmp(B * 4);
     if (!mean_coef || !labels_f) return T2P_ERR_HIP;
     T2P_TRY(launch_dsm_prepare_vp(b.t, B, (float)tc_.t_eps, beta_min_, beta_max_, sde_ == T2P_SDE_SUBVP, mc_.num_scales, vp_std_,
-                                  mc_.scale_by_sigma ? inv_sigma_ : nullptr, tc_.seed, (unsigned long long)loss_calls_, t_dev, mean_coef, stdv,
+                                  mc_.scale_by_sigma ? inv_sigma_ : nullptr, tc_.seed, rng_t(), t_dev, mean_coef, stdv,
                                   labels, labels_f, scale, s_));
   }
   const float* z = b.z;
   if (!z) {
     float* zb = tmp(nx * 4);
     if (!zb) return T2P_ERR_HIP;
-    T2P_TRY(launch_philox_normal(zb, nx, tc_.seed, (unsigned long long)(loss_calls_ * 4096 + 1), nullptr, s_));
+    T2P_TRY(launch_philox_normal(zb, nx, tc_.seed, rng_z(), nullptr, s_));
     z = zb;
   }
   T2P_TRY(launch_dsm_perturb(b.coords_6d, z, stdv, mean_coef, b.mask_pair, b.mask_inpaint, tc_.cond_flags, B, Cx, L, perturbed, mask, num_elem, s_));
@@ -735,28 +716,15 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool bac
   TT* ctx = &acts_.back();
   ctx->p = const_cast<float*>(b.context); ctx->B = B; ctx->H = b.tokens; ctx->W = 1; ctx->C = mc_.context_dim; ctx->needs_grad = false;
 
-  T2P_ACT(h0, B, L, L, nf);
-  T2P_TRY(conv_forward(x0->p, B, L, L, 8, pre_conv_.wf, 9L * 8, P + pre_conv_.b, nullptr, nf, h0->p, nf, nullptr, s_));
-  {
-    const Conv c = pre_conv_;
-    tape_.push_back([this, x0, h0, c]() -> int {
-      if (!h0->g) return T2P_OK;
-      T2P_HIP_CHECK(hipMemsetAsync(dwc_, 0, (size_t)c.Co * 9 * c.Cip * 4, s_));
-      TGemmArgs w;
-      w.A = h0->g; w.sAm = 1; w.sAk = h0->C; w.B = x0->p; w.conv_b = 1; w.H = x0->H; w.W = x0->W; w.conv_C = c.Cip; w.ldx = x0->C;
-      w.C = dwc_; w.ldc = 9L * c.Cip; w.M = c.Co; w.N = 9 * c.Cip; w.K = (int)x0->rows(); w.beta = 1.f; w.ksplit = 0;
-      T2P_TRY(tg(w));
-      T2P_TRY(launch_conv_w_grad_fold(dwc_, Gr_ + c.w, c.Co, c.Ci, c.Cip, s_));
-      return colsum(h0->g, 1, h0->rows(), c.Co, h0->C, Gr_ + c.b, 0);
-    });
-  }
+  TT* h0 = nullptr;
+  T2P_TRY(conv3x3(x0, pre_conv_, nullptr, &h0));   // x0 needs no gradient: weight and bias gradients only
   std::vector<TT*> hs{h0};
   TT* h = h0;
   for (const auto& st : in_stages_) {
-    T2P_TRY(run_layers(st, h, stemb, ctx, &h));
+    T2P_TRY(run_layers(st, h, stemb, ctx, train, &h));
     hs.push_back(h);
   }
-  T2P_TRY(run_layers(mid_, h, stemb, ctx, &h));
+  T2P_TRY(run_layers(mid_, h, stemb, ctx, train, &h));
   for (const auto& st : out_stages_) {
     TT* skip = hs.back();
     hs.pop_back();
@@ -772,29 +740,13 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool bac
       T2P_TRY(launch_copy_cols(cat->g, cat->C, 0, g0, hin->C, 0, hin->rows(), hin->C, 1, s_));
       return launch_copy_cols(cat->g, cat->C, hin->C, g1, skip->C, 0, hin->rows(), skip->C, 1, s_);
     });
-    T2P_TRY(run_layers(st, cat, stemb, ctx, &h));
+    T2P_TRY(run_layers(st, cat, stemb, ctx, train, &h));
   }
   T2P_REQUIRE(hs.empty(), "skip stack not consumed");
   TT* a = nullptr;
   T2P_TRY(group_norm(h, head_norm_, 1, &a));
-  T2P_ACT(o, B, L, L, 8);                          // head convolution: Cx of 8 columns used
-  T2P_HIP_CHECK(hipMemsetAsync(o->p, 0, (size_t)o->numel() * 4, s_));
-  T2P_TRY(conv_forward(a->p, B, L, L, a->C, head_conv_.wf, 9L * head_conv_.Cip, P + head_conv_.b, nullptr, Cx, o->p, 8, nullptr, s_));
-  {
-    const Conv c = head_conv_;
-    tape_.push_back([this, a, o, c]() -> int {
-      if (!o->g) return T2P_OK;
-      T2P_GRAD(ga, a);
-      T2P_TRY(conv_forward(o->g, a->B, a->H, a->W, 8, c.wd, 9L * 8, nullptr, nullptr, c.Ci, ga, a->C, ga, s_));
-      T2P_HIP_CHECK(hipMemsetAsync(dwc_, 0, (size_t)c.Co * 9 * c.Cip * 4, s_));
-      TGemmArgs w;
-      w.A = o->g; w.sAm = 1; w.sAk = 8; w.B = a->p; w.conv_b = 1; w.H = a->H; w.W = a->W; w.conv_C = c.Cip; w.ldx = a->C;
-      w.C = dwc_; w.ldc = 9L * c.Cip; w.M = c.Co; w.N = 9 * c.Cip; w.K = (int)a->rows(); w.beta = 1.f; w.ksplit = 0;
-      T2P_TRY(tg(w));
-      T2P_TRY(launch_conv_w_grad_fold(dwc_, Gr_ + c.w, c.Co, c.Ci, c.Cip, s_));
-      return colsum(o->g, 1, a->rows(), c.Co, 8, Gr_ + c.b, 0);
-    });
-  }
+  TT* o = nullptr;                                 // head convolution: Cx of its 8 columns used, the rest zero
+  T2P_TRY(conv3x3(a, head_conv_, nullptr, &o));
   float* d_o = nullptr;
   if (backward) {
     d_o = grad(o);
@@ -831,10 +783,7 @@ int Trainer::loss(const t2p_train_batch& b, bool backward, bool use_ema, float* 
   s_ = s;
   if (backward) last_loss_finite_ = false;        // the overflow guard trusts only a completed backward pass
   if (backward) T2P_HIP_CHECK(hipMemsetAsync(Gr_, 0, (size_t)total_ * 4, s));      // optimizer.zero_grad()
-  const double keep_dropout = tc_.dropout;
-  if (use_ema) tc_.dropout = 0.0;                 // eval mode (models/utils.py:113-115)
-  const int rc = forward_backward(b, use_ema ? E_ : P_, backward, loss_dev_, score_out);
-  tc_.dropout = keep_dropout;
+  const int rc = forward_backward(b, use_ema ? E_ : P_, !use_ema, backward, loss_dev_, score_out);   // the EMA weights: eval mode
   ++loss_calls_;
   const hipError_t e = hipStreamSynchronize(s);
   release();
@@ -860,10 +809,14 @@ int Trainer::apply(hipStream_t s) {
   a.bias1 = (float)(1.0 - std::pow(tc_.beta1, (double)k));
   a.bias2_sqrt = (float)std::sqrt(1.0 - std::pow(0.999, (double)k));
   a.grad_clip = (float)tc_.grad_clip;
-  if (dt_ != DT_F32) {
-    // overflow guard (AMP's skipped step, reported): a loss or gradient norm that is not finite changes nothing
+  const bool guard = dt_ != DT_F32;               // overflow guard (AMP's skipped step, reported): a loss or gradient norm that is not finite changes nothing
+  if (guard || tc_.grad_clip >= 0) {
+    if (!sumsq_part_) T2P_HIP_CHECK(hipMemsetAsync(sumsq_, 0, 8, s));     // the atomic form accumulates
+    T2P_TRY(launch_sumsq(Gr_, total_, sumsq_part_, sumsq_, s));
+    if (tc_.grad_clip >= 0) a.sumsq = sumsq_;
+  }
+  if (guard) {
     double sumsq = 0.0;
-    T2P_TRY(launch_sumsq_fixed(Gr_, total_, sumsq_part_, sumsq_, s));
     T2P_HIP_CHECK(hipMemcpyAsync(&sumsq, sumsq_, 8, hipMemcpyDeviceToHost, s));
     T2P_HIP_CHECK(hipStreamSynchronize(s));
     T2P_REQUIRE(last_loss_finite_ && std::isfinite(sumsq),
@@ -871,11 +824,6 @@ int Trainer::apply(hipStream_t s) {
                     (last_loss_finite_ ? "the gradient norm is not finite (f16 / bf16 overflow)"
                                        : "the loss of the last backward pass is not finite (f16 / bf16 overflow), or that pass did not complete") +
                     "; parameters, optimizer state, EMA and step counters are unchanged");
-    if (tc_.grad_clip >= 0) a.sumsq = sumsq_;
-  } else if (tc_.grad_clip >= 0) {
-    T2P_HIP_CHECK(hipMemsetAsync(sumsq_, 0, 8, s));
-    T2P_TRY(launch_sumsq(Gr_, total_, sumsq_, s));
-    a.sumsq = sumsq_;
   }
   T2P_TRY(launch_adam(a, s));
   adam_k_ = k;

@@ -1,7 +1,9 @@
 // Training step of the score network: forward pass that keeps what the backward pass needs, backward pass,
 // denoising score-matching loss, Adam / warm-up / clipping and the EMA update (reference score_sde_pytorch/losses.py:26-186,
 // score_sde_pytorch/models/ema.py:32-49).  compute_dtype F32: exact-f32 products; F16 / BF16: 16-bit products with fp32 accumulation,
-// everything the optimizer sees (parameters, gradients, moments, EMA, loss) fp32.
+// everything the optimizer sees (parameters, gradients, moments, EMA, loss) fp32.  Every operator of the network (linear, conv3x3,
+// group_norm, layer_norm, attention, add_scale) is one member that runs its forward and appends its backward to the tape; the
+// dtypes differ inside tg (which strided GEMM), conv3x3 (which implicit GEMM) and in fixed_order_ (which form of the reductions).
 #pragma once
 #include <deque>
 #include <functional>
@@ -69,29 +71,39 @@ class Trainer {
   int map_layer(const Layer& l, LayerT* out);
   int prep_weights(const float* P, hipStream_t s);
   int tg(const TGemmArgs& a);               // one strided product: launch_tgemm (F32) or launch_tgemm16 (F16 / BF16)
-  int conv16(const float* x, int B, int H, int W, int Cin, const void* w16, long ldb, const float* bias, const float* bias_bn, int N,
-             float* y, long ldc, const float* residual_inplace);   // residual-block 3x3 convolution, 16-bit modes
-  int colsum(const float* dy, int nz, long rows, int N, long ld, float* out, long ld_out);   // bias gradients (fixed order in 16-bit modes)
+  int reduce_ws(long floats, float** ws);   // pass-local workspace of a fixed-order reduction; null in the f32 step (atomic form)
+  int colsum(const float* dy, int nz, long rows, int N, long ld, float* out);   // out [nz][N] += column sums of dy (bias gradients)
+  // one launch of the engine's implicit-GEMM 3x3 convolution (forward and data gradient of conv3x3)
+  int conv_gemm(const float* x, int B, int H, int W, int Cin, const float* w, const void* w16, long ldb, const float* bias,
+                const float* bias_bn, int N, float* y, long ldc, const float* residual_inplace);
+  // Philox stream ids of the running loss call, all under the key tc_.seed: the diffusion times t, the noise z and the dropout mask of
+  // residual block k.  Known defect, kept as it is here (the RNG stream bookkeeping of the training step): the three families overlap -- t of
+  // call 4096 n + 1 is z's stream of call n, t of call 4096 n + 16 + k is block k's mask stream of call n -- and z's id wraps at
+  // 2^20 calls in the 32-bit stream word of the normal generator.
+  unsigned long long rng_t() const { return (unsigned long long)loss_calls_; }
+  unsigned long long rng_z() const { return (unsigned long long)(loss_calls_ * 4096 + 1); }
+  unsigned long long rng_dropout(int k) const { return (unsigned long long)(loss_calls_ * 4096 + 16 + k); }
 
   // forward ops: each appends its backward to tape_
   TT* act(int B, int H, int W, int C, bool needs_grad = true);
   float* grad(TT* t);                       // gradient buffer of t, zero-initialised on first use
   float* tmp(size_t bytes);                 // released at the end of the call
   int linear(TT* x, const Lin& l, TT** out);
+  int conv3x3(TT* x, const Conv& c, TT* tbias, TT** out);   // + bias (+ tbias [B][Co] per sample)
   int group_norm(TT* x, const Norm& n, int silu, TT** out);
   int layer_norm(TT* x, const Norm& n, TT** out);
   int attention(TT* q, TT* k, TT* v, int heads, float scale, TT** out);
   int add_scale(TT* a, TT* b, float alpha, TT** out);
-  int res_block(const LayerT& L, TT* x, TT* stemb, TT** out);
+  int res_block(const LayerT& L, TT* x, TT* stemb, bool train, TT** out);   // train: Dropout_0 active (eval: models/utils.py:113-115)
   int attn_block(const LayerT& L, TT* x, TT** out);
   int st_block(const LayerT& L, TT* x, TT* ctx, TT** out);
-  int run_layers(const std::vector<LayerT>& ls, TT* h, TT* stemb, TT* ctx, TT** out);
-  int forward_backward(const t2p_train_batch& b, const float* P, bool backward, float* loss_dev, float* score_out);
+  int run_layers(const std::vector<LayerT>& ls, TT* h, TT* stemb, TT* ctx, bool train, TT** out);
+  int forward_backward(const t2p_train_batch& b, const float* P, bool train, bool backward, float* loss_dev, float* score_out);
   void release();
 
   t2p_model_config mc_;
   t2p_train_config tc_;
-  Engine arch_;                     // structure and parameter table only (Engine::build); never finalized, holds no weights
+  NetArch arch_;                    // the block list and the parameter table the sampling engine uses
   std::vector<TParam> params_;
   std::unordered_map<std::string, int> index_;
   long total_ = 0;
@@ -106,9 +118,9 @@ class Trainer {
   float* vp_std_ = nullptr;         // VP: sqrt_1m_alphas_cumprod, float[num_scales] (the divisor of the score, models/utils.py:154)
   int64_t step_ = 0, adam_k_ = 0, ema_k_ = 0, loss_calls_ = 0;
   int dt_ = DT_F32;                 // compute dtype of the products
-  double* sumsq_part_ = nullptr;    // 16-bit modes: fixed-order gradient norm (launch_sumsq_fixed)
+  bool fixed_order_ = false;        // 16-bit modes: every reduction that feeds a gradient or an update runs in a fixed order
+  double* sumsq_part_ = nullptr;    // fixed_order_: the partial sums of the gradient norm (launch_sumsq)
   bool last_loss_finite_ = false;   // 16-bit modes: the last backward pass completed with a finite loss (the overflow guard of apply)
-  std::vector<LayerT> in_layers_;
   std::vector<std::vector<LayerT>> in_stages_, out_stages_;
   std::vector<LayerT> mid_;
   Lin pre0_, pre1_;

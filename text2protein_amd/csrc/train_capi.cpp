@@ -17,6 +17,19 @@ using namespace t2p;
     return T2P_ERR_STATE;                              \
   }
 
+// the arguments of t2p_op_tgemm / t2p_op_tgemm16 (include/t2p.h) as the launchers take them
+static TGemmArgs op_tgemm_args(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBk, int64_t sBn, float* C, int64_t ldc, int M,
+                               int N, int K, int nz, int64_t sAz, int64_t sBz, int64_t sCz, float alpha, float beta, const float* bias_n,
+                               int ksplit, int conv, int H, int W, int conv_C) {
+  TGemmArgs a;
+  a.A = A; a.sAm = sAm; a.sAk = sAk; a.sAz0 = sAz;
+  a.B = B; a.sBk = sBk; a.sBn = sBn; a.sBz0 = sBz;
+  a.C = C; a.ldc = ldc; a.sCz0 = sCz; a.M = M; a.N = N; a.K = K; a.nz0 = nz; a.nz1 = 1;
+  a.alpha = alpha; a.beta = beta; a.bias_n = bias_n; a.ksplit = ksplit;
+  if (conv) { a.conv_b = 1; a.H = H; a.W = W; a.conv_C = conv_C; a.ldx = sBz; a.sBz0 = 0; }
+  return a;
+}
+
 extern "C" {
 
 int t2p_train_create(const t2p_model_config* model, const t2p_train_config* train, t2p_trainer** out) {
@@ -145,13 +158,8 @@ int t2p_op_tgemm(const float* A, int64_t sAm, int64_t sAk, const float* B, int64
                  int K, int nz, int64_t sAz, int64_t sBz, int64_t sCz, float alpha, float beta, const float* bias_n, int ksplit, int conv,
                  int H, int W, int conv_C, void* stream) {
   API_BEGIN
-  TGemmArgs a;
-  a.A = A; a.sAm = sAm; a.sAk = sAk; a.sAz0 = sAz;
-  a.B = B; a.sBk = sBk; a.sBn = sBn; a.sBz0 = sBz;
-  a.C = C; a.ldc = ldc; a.sCz0 = sCz; a.M = M; a.N = N; a.K = K; a.nz0 = nz; a.nz1 = 1;
-  a.alpha = alpha; a.beta = beta; a.bias_n = bias_n; a.ksplit = ksplit;
-  if (conv) { a.conv_b = 1; a.H = H; a.W = W; a.conv_C = conv_C; a.ldx = sBz; a.sBz0 = 0; }
-  return launch_tgemm(a, (hipStream_t)stream);
+  return launch_tgemm(op_tgemm_args(A, sAm, sAk, B, sBk, sBn, C, ldc, M, N, K, nz, sAz, sBz, sCz, alpha, beta, bias_n, ksplit, conv, H, W, conv_C),
+                      (hipStream_t)stream);
   API_END
 }
 
@@ -159,12 +167,7 @@ int t2p_op_tgemm16(int dtype, const float* A, int64_t sAm, int64_t sAk, const fl
                    int M, int N, int K, int nz, int64_t sAz, int64_t sBz, int64_t sCz, float alpha, float beta, const float* bias_n, int ksplit,
                    int conv, int H, int W, int conv_C, void* stream) {
   API_BEGIN
-  TGemmArgs a;
-  a.A = A; a.sAm = sAm; a.sAk = sAk; a.sAz0 = sAz;
-  a.B = B; a.sBk = sBk; a.sBn = sBn; a.sBz0 = sBz;
-  a.C = C; a.ldc = ldc; a.sCz0 = sCz; a.M = M; a.N = N; a.K = K; a.nz0 = nz; a.nz1 = 1;
-  a.alpha = alpha; a.beta = beta; a.bias_n = bias_n; a.ksplit = ksplit;
-  if (conv) { a.conv_b = 1; a.H = H; a.W = W; a.conv_C = conv_C; a.ldx = sBz; a.sBz0 = 0; }
+  const TGemmArgs a = op_tgemm_args(A, sAm, sAk, B, sBk, sBn, C, ldc, M, N, K, nz, sAz, sBz, sCz, alpha, beta, bias_n, ksplit, conv, H, W, conv_C);
   T2P_REQUIRE(M > 0 && N > 0 && K > 0 && nz >= 1 && ksplit >= 0, "tgemm16 shapes");
   hipStream_t s = (hipStream_t)stream;
   const long n = tgemm16_ws_floats(a);
@@ -187,15 +190,20 @@ int t2p_op_groupnorm_backward(const float* x, const float* dy, const float* gamm
   hipStream_t s = (hipStream_t)stream;
   float *stats = nullptr, *partial = nullptr, *ws = nullptr;
   const int nparts = gn_num_chunks(HW) * ((C + 1023) / 1024);
-  T2P_HIP_CHECK(hipMalloc(&stats, (size_t)batch * groups * 2 * 4));
-  T2P_HIP_CHECK(hipMalloc(&partial, (size_t)batch * nparts * groups * 2 * 4));
-  T2P_HIP_CHECK(hipMalloc(&ws, (size_t)gn_bwd_ws_floats(batch, HW, C, groups) * 4));
+  int rc = T2P_OK;
+  hipError_t e = hipMalloc(&stats, (size_t)batch * groups * 2 * 4);
+  if (e == hipSuccess) e = hipMalloc(&partial, (size_t)batch * nparts * groups * 2 * 4);
+  if (e == hipSuccess) e = hipMalloc(&ws, (size_t)gn_bwd_ws_floats(batch, HW, C, groups) * 4);
+  if (e != hipSuccess) {
+    set_last_error(std::string("groupnorm_backward: hipMalloc: ") + hipGetErrorString(e));
+    rc = T2P_ERR_HIP;
+  }
   GroupNormArgs a;
   a.x0 = x; a.C0 = C; a.B = batch; a.HW = HW; a.G = groups; a.eps = eps; a.partial = partial; a.stats = stats;
-  int rc = launch_gn_stats(a, s);
-  if (rc == T2P_OK) rc = launch_gn_backward(x, dy, stats, gamma, beta, silu, batch, HW, C, groups, dx, dgamma, dbeta, ws, s);
+  if (rc == T2P_OK) rc = launch_gn_stats(a, s);
+  if (rc == T2P_OK) rc = launch_gn_backward(x, dy, stats, gamma, beta, silu, batch, HW, C, groups, dx, dgamma, dbeta, ws, false, s);
   (void)hipStreamSynchronize(s);
-  (void)hipFree(stats); (void)hipFree(partial); (void)hipFree(ws);
+  (void)hipFree(stats); (void)hipFree(partial); (void)hipFree(ws);   // hipFree(nullptr) is a no-op: one cleanup path, whichever step failed
   return rc;
   API_END
 }
@@ -203,7 +211,7 @@ int t2p_op_groupnorm_backward(const float* x, const float* dy, const float* gamm
 int t2p_op_layernorm_backward(const float* x, const float* dy, const float* gamma, int64_t rows, int C, float eps, float* dx, float* dgamma,
                               float* dbeta, void* stream) {
   API_BEGIN
-  return launch_ln_backward(x, dy, gamma, rows, C, eps, dx, dgamma, dbeta, (hipStream_t)stream);
+  return launch_ln_backward(x, dy, gamma, rows, C, eps, dx, dgamma, dbeta, nullptr, (hipStream_t)stream);
   API_END
 }
 

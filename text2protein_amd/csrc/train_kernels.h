@@ -1,7 +1,11 @@
 // Launchers of the TRAINING step's kernels (train_kernels.hip): the backward halves of the score network's operators, the
 // denoising score-matching loss and the optimizer / EMA updates (reference score_sde_pytorch/losses.py:26-186,
-// score_sde_pytorch/models/ema.py:32-49).  fp32 throughout (exact-f32 MFMA, v_mfma_f32_32x32x2_f32): first slice of
-// SURVEY.md 8(f)4.  Every gradient output ACCUMULATES (+=) into its destination unless stated.
+// score_sde_pytorch/models/ema.py:32-49).  Everything in memory is fp32; the products run on the exact-f32 MFMA
+// (v_mfma_f32_32x32x2_f32, launch_tgemm) or on the 16-bit matrix pipe (launch_tgemm16): SURVEY.md 8(f)4.  Every gradient output
+// ACCUMULATES (+=) into its destination unless stated.
+// Each reduction over rows or over the batch (GroupNorm / LayerNorm parameter gradients, column sums, the gradient norm) has one
+// launcher and two forms: float / double atomics (the f32 step), or a fixed summation order through a workspace (the 16-bit step,
+// which is bitwise reproducible).  The workspace argument selects the form: null = atomics.
 #pragma once
 #include "t2p_common.h"
 
@@ -34,20 +38,16 @@ int launch_tgemm16(const TGemmArgs& a, int dtype, float* ws, hipStream_t s);
 
 // ---- GroupNorm backward (nn.GroupNorm + optional SiLU, layers.py:282,304,317; attention.py:77) -------------------------------------
 // y = act(gamma (x - mean) rstd + beta); x, dy, dx: NHWC [B][HW][C] fp32; stats [B][G][2] = (mean, rstd) of the forward pass.
-// dx += ..., dgamma += ..., dbeta += ...;  ws: gn_bwd_ws_floats(B, HW, C) floats
+// dx += ..., dgamma += ..., dbeta += ...;  ws: gn_bwd_ws_floats(B, HW, C, G) floats (both forms).  fixed_order: d gamma / d beta are
+// summed over the batch in sample order instead of with atomics
 long gn_bwd_ws_floats(int B, int HW, int C, int G);
 int launch_gn_backward(const float* x, const float* dy, const float* stats, const float* gamma, const float* beta, int silu,
-                       int B, int HW, int C, int G, float* dx, float* dgamma, float* dbeta, float* ws, hipStream_t s);
-// the same with d gamma / d beta summed over the batch in a fixed order (bitwise reproducible)
-int launch_gn_backward_fixed(const float* x, const float* dy, const float* stats, const float* gamma, const float* beta, int silu,
-                             int B, int HW, int C, int G, float* dx, float* dgamma, float* dbeta, float* ws, hipStream_t s);
+                       int B, int HW, int C, int G, float* dx, float* dgamma, float* dbeta, float* ws, bool fixed_order, hipStream_t s);
 // ---- LayerNorm backward (attention.py:203-205), rows x C, eps as the forward -----------------------------------------------------
+// ws == nullptr: d gamma / d beta with atomics (C <= 8192); else fixed order, ws: ln_bwd_ws_floats(rows, C) floats
+long ln_bwd_ws_floats(long rows, int C);
 int launch_ln_backward(const float* x, const float* dy, const float* gamma, long rows, int C, float eps, float* dx, float* dgamma,
-                       float* dbeta, hipStream_t s);
-// the same with a fixed summation order for d gamma / d beta (bitwise reproducible); ws: ln_bwd_fixed_ws_floats(rows, C) floats
-long ln_bwd_fixed_ws_floats(long rows, int C);
-int launch_ln_backward_fixed(const float* x, const float* dy, const float* gamma, long rows, int C, float eps, float* dx, float* dgamma,
-                             float* dbeta, float* ws, hipStream_t s);
+                       float* dbeta, float* ws, hipStream_t s);
 // ---- softmax backward, in place: dP[r][j] <- scale P[r][j] (dP[r][j] - sum_j dP[r][j] P[r][j])  (P = softmax(scale S)) ------------------
 int launch_softmax_backward(const float* P, float* dP, long rows, int n, float scale, hipStream_t s);
 // ---- GEGLU backward (attention.py:37-44): u = [a | g], out = a gelu(g);  du += [dy gelu(g) | dy a gelu'(g)] ----------------------------
@@ -60,14 +60,11 @@ int launch_add_scale(const float* a, const float* b, float alpha, float* out, lo
 // dst[r][dst_off + c] (+)= src[r][src_off + c], c < C  (channel concat of the U-Net skips, ncsnpp.py:250, and its backward)
 int launch_copy_cols(const float* src, long ld_src, long src_off, float* dst, long ld_dst, long dst_off, long rows, int C, int accumulate,
                      hipStream_t s);
-// out[n] += sum_r dy[r][n]                      (bias gradients)
-int launch_colsum(const float* dy, long rows, int N, long ld, float* out, hipStream_t s);
-// out[b][n] (+)= sum_p dy[b][p][n]              (gradient of the per-sample time-embedding bias, layers.py:316)
-int launch_colsum_per_sample(const float* dy, int B, int HW, int N, float* out, long ld_out, int accumulate, hipStream_t s);
-// fixed-order column sums (bitwise reproducible): out[z][n] (+)= sum_r dy[z rows_per_z + r][n]; ws: colsum_fixed_ws_floats floats
-long colsum_fixed_ws_floats(int nz, long rows_per_z, int N);
-int launch_colsum_fixed(const float* dy, int nz, long rows_per_z, int N, long ld, float* out, long ld_out, int accumulate, float* ws,
-                        hipStream_t s);
+// column sums: out[z][n] (+)= sum_r dy[z rows_per_z + r][n], dy rows of ld floats, out rows of ld_out.  nz = 1: bias gradients; nz = B:
+// the gradient of the per-sample time-embedding bias (layers.py:316).  ws == nullptr: atomics; else fixed order, ws:
+// colsum_ws_floats(nz, rows_per_z, N) floats
+long colsum_ws_floats(int nz, long rows_per_z, int N);
+int launch_colsum(const float* dy, int nz, long rows_per_z, int N, long ld, float* out, long ld_out, int accumulate, float* ws, hipStream_t s);
 // nearest 2x up-sampling / 2x2 mean down-sampling of NHWC maps (layers.py:179-188) and their backward (+=)
 int launch_up2(const float* x, float* y, int B, int H, int W, int C, hipStream_t s);               // x [B][H][W][C] -> y [B][2H][2W][C]
 int launch_up2_backward(const float* dy, float* dx, int B, int H, int W, int C, hipStream_t s);
@@ -114,8 +111,8 @@ int launch_dsm_loss(const float* o, long ldo, const float* z, const float* std, 
 int launch_dsm_finish(const double* loss_sum, const float* num_elem, int B, float* loss, hipStream_t s);
 
 // ---- optimizer (losses.py:26-51: Adam, warm-up, clip_grad_norm_) and EMA (ema.py:32-49) over flat parameter buffers ------------------------
-int launch_sumsq(const float* g, long n, double* out, hipStream_t s);      // *out += sum g^2   (zero it first)
-int launch_sumsq_fixed(const float* g, long n, double* partial, double* out, hipStream_t s);   // *out = sum g^2, fixed order; partial: 1024 doubles
+// partial == nullptr: *out += sum g^2 with atomics (zero it first); else *out = sum g^2 in a fixed order, partial: 1024 doubles
+int launch_sumsq(const float* g, long n, double* partial, double* out, hipStream_t s);
 struct AdamArgs {
   float* p = nullptr; float* g = nullptr; float* m = nullptr; float* v = nullptr; long n = 0;
   float lr = 0.f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f, weight_decay = 0.f;

@@ -622,22 +622,7 @@ long gn_bwd_ws_floats(int B, int HW, int C, int G) {
   return (long)B * nchunk * C * 2 + (long)B * C * 2 + (long)B * G * 2;
 }
 
-int launch_gn_backward(const float* x, const float* dy, const float* stats, const float* gamma, const float* beta, int silu,
-                       int B, int HW, int C, int G, float* dx, float* dgamma, float* dbeta, float* ws, hipStream_t s) {
-  T2P_REQUIRE(x && dy && stats && gamma && beta && dx && dgamma && dbeta && ws, "gn_backward pointers");
-  T2P_REQUIRE(B > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0 && B <= 65535, "gn_backward shapes");
-  const int nchunk = (HW + GN_CHUNK - 1) / GN_CHUNK;
-  float* partial = ws;
-  float* sums = partial + (long)B * nchunk * C * 2;
-  float* gs = sums + (long)B * C * 2;
-  hipLaunchKernelGGL(gn_bwd_partial_kernel, dim3(nchunk, B), dim3(256), 0, s, x, dy, stats, gamma, beta, silu, HW, C, G, partial);
-  hipLaunchKernelGGL(gn_bwd_finalize_kernel<true>, dim3(B), dim3(256), 0, s, partial, gamma, nchunk, C, G, sums, gs, dgamma, dbeta);
-  const long total = (long)B * HW * C;
-  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, x, dy, stats, gamma, beta, silu, HW, C, G, gs, dx, total);
-  T2P_HIP_CHECK(hipGetLastError());
-  return T2P_OK;
-}
-
+// fixed order: d gamma / d beta = the per-sample sums added over the batch in sample order
 __global__ __launch_bounds__(256) void gn_bwd_param_sum_kernel(const float* __restrict__ sums, const int B, const int C, float* __restrict__ dgamma,
                                                                float* __restrict__ dbeta) {
   const int c = blockIdx.x * 256 + threadIdx.x;
@@ -647,8 +632,9 @@ __global__ __launch_bounds__(256) void gn_bwd_param_sum_kernel(const float* __re
   dbeta[c] += a;
   dgamma[c] += bq;
 }
-int launch_gn_backward_fixed(const float* x, const float* dy, const float* stats, const float* gamma, const float* beta, int silu,
-                             int B, int HW, int C, int G, float* dx, float* dgamma, float* dbeta, float* ws, hipStream_t s) {
+
+int launch_gn_backward(const float* x, const float* dy, const float* stats, const float* gamma, const float* beta, int silu,
+                       int B, int HW, int C, int G, float* dx, float* dgamma, float* dbeta, float* ws, bool fixed_order, hipStream_t s) {
   T2P_REQUIRE(x && dy && stats && gamma && beta && dx && dgamma && dbeta && ws, "gn_backward pointers");
   T2P_REQUIRE(B > 0 && HW > 0 && C > 0 && G > 0 && C % G == 0 && B <= 65535, "gn_backward shapes");
   const int nchunk = (HW + GN_CHUNK - 1) / GN_CHUNK;
@@ -656,8 +642,12 @@ int launch_gn_backward_fixed(const float* x, const float* dy, const float* stats
   float* sums = partial + (long)B * nchunk * C * 2;
   float* gs = sums + (long)B * C * 2;
   hipLaunchKernelGGL(gn_bwd_partial_kernel, dim3(nchunk, B), dim3(256), 0, s, x, dy, stats, gamma, beta, silu, HW, C, G, partial);
-  hipLaunchKernelGGL(gn_bwd_finalize_kernel<false>, dim3(B), dim3(256), 0, s, partial, gamma, nchunk, C, G, sums, gs, dgamma, dbeta);
-  hipLaunchKernelGGL(gn_bwd_param_sum_kernel, dim3(cdiv_l(C, 256)), dim3(256), 0, s, (const float*)sums, B, C, dgamma, dbeta);
+  if (fixed_order) {
+    hipLaunchKernelGGL(gn_bwd_finalize_kernel<false>, dim3(B), dim3(256), 0, s, partial, gamma, nchunk, C, G, sums, gs, dgamma, dbeta);
+    hipLaunchKernelGGL(gn_bwd_param_sum_kernel, dim3(cdiv_l(C, 256)), dim3(256), 0, s, (const float*)sums, B, C, dgamma, dbeta);
+  } else {
+    hipLaunchKernelGGL(gn_bwd_finalize_kernel<true>, dim3(B), dim3(256), 0, s, partial, gamma, nchunk, C, G, sums, gs, dgamma, dbeta);
+  }
   const long total = (long)B * HW * C;
   hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, x, dy, stats, gamma, beta, silu, HW, C, G, gs, dx, total);
   T2P_HIP_CHECK(hipGetLastError());
@@ -707,14 +697,6 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
     unsafeAtomicAdd(dgamma + c, sg[c]);
     unsafeAtomicAdd(dbeta + c, sb[c]);
   }
-}
-
-int launch_ln_backward(const float* x, const float* dy, const float* gamma, long rows, int C, float eps, float* dx, float* dgamma,
-                       float* dbeta, hipStream_t s) {
-  T2P_REQUIRE(x && dy && gamma && dx && dgamma && dbeta && rows > 0 && C > 0 && C <= 8192, "ln_backward arguments");
-  hipLaunchKernelGGL(ln_bwd_kernel, dim3(cdiv_l(rows, LN_ROWS)), dim3(256), 2 * C * sizeof(float), s, x, dy, gamma, rows, C, eps, dx, dgamma, dbeta);
-  T2P_HIP_CHECK(hipGetLastError());
-  return T2P_OK;
 }
 
 // the same in a fixed summation order (mixed-precision step, which is bitwise reproducible): pass 1 = one wavefront per row, dx and the
@@ -771,17 +753,22 @@ __global__ __launch_bounds__(256) void ln_bwd_cols_finish_kernel(const float* __
   dgamma[c] += g;
   dbeta[c] += b;
 }
-long ln_bwd_fixed_ws_floats(long rows, int C) { return 2 * rows + 2L * C * cdiv_l(rows, LN_COL_ROWS); }
-int launch_ln_backward_fixed(const float* x, const float* dy, const float* gamma, long rows, int C, float eps, float* dx, float* dgamma,
-                             float* dbeta, float* ws, hipStream_t s) {
-  T2P_REQUIRE(x && dy && gamma && dx && dgamma && dbeta && ws && rows > 0 && C > 0, "ln_backward arguments");
-  const int nchunk = cdiv_l(rows, LN_COL_ROWS);
-  T2P_REQUIRE(nchunk <= 65535, "ln_backward rows");
-  float* stats = ws;
-  float* partial = ws + 2 * rows;
-  hipLaunchKernelGGL(ln_bwd_rows_kernel, dim3(cdiv_l(rows, 4)), dim3(256), 0, s, x, dy, gamma, rows, C, eps, dx, stats);
-  hipLaunchKernelGGL(ln_bwd_cols_kernel, dim3(cdiv_l(C, 256), nchunk), dim3(256), 0, s, x, dy, (const float*)stats, rows, C, partial);
-  hipLaunchKernelGGL(ln_bwd_cols_finish_kernel, dim3(cdiv_l(C, 256)), dim3(256), 0, s, (const float*)partial, nchunk, C, dgamma, dbeta);
+long ln_bwd_ws_floats(long rows, int C) { return 2 * rows + 2L * C * cdiv_l(rows, LN_COL_ROWS); }
+int launch_ln_backward(const float* x, const float* dy, const float* gamma, long rows, int C, float eps, float* dx, float* dgamma,
+                       float* dbeta, float* ws, hipStream_t s) {
+  T2P_REQUIRE(x && dy && gamma && dx && dgamma && dbeta && rows > 0 && C > 0, "ln_backward arguments");
+  if (!ws) {
+    T2P_REQUIRE(C <= 8192, "ln_backward arguments");
+    hipLaunchKernelGGL(ln_bwd_kernel, dim3(cdiv_l(rows, LN_ROWS)), dim3(256), 2 * C * sizeof(float), s, x, dy, gamma, rows, C, eps, dx, dgamma, dbeta);
+  } else {
+    const int nchunk = cdiv_l(rows, LN_COL_ROWS);
+    T2P_REQUIRE(nchunk <= 65535, "ln_backward rows");
+    float* stats = ws;
+    float* partial = ws + 2 * rows;
+    hipLaunchKernelGGL(ln_bwd_rows_kernel, dim3(cdiv_l(rows, 4)), dim3(256), 0, s, x, dy, gamma, rows, C, eps, dx, stats);
+    hipLaunchKernelGGL(ln_bwd_cols_kernel, dim3(cdiv_l(C, 256), nchunk), dim3(256), 0, s, x, dy, (const float*)stats, rows, C, partial);
+    hipLaunchKernelGGL(ln_bwd_cols_finish_kernel, dim3(cdiv_l(C, 256)), dim3(256), 0, s, (const float*)partial, nchunk, C, dgamma, dbeta);
+  }
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }
@@ -927,30 +914,18 @@ __global__ __launch_bounds__(256) void colsum_finish_kernel(const float* __restr
     *o = accumulate ? *o + t : t;
   }
 }
-long colsum_fixed_ws_floats(int nz, long rows_per_z, int N) { return (long)nz * cdiv_l(rows_per_z, 256) * N; }
-int launch_colsum_fixed(const float* dy, int nz, long rows_per_z, int N, long ld, float* out, long ld_out, int accumulate, float* ws,
-                        hipStream_t s) {
-  T2P_REQUIRE(dy && out && ws && nz > 0 && nz <= 65535 && rows_per_z > 0 && N > 0 && ld >= N && ld_out >= N, "colsum arguments");
+long colsum_ws_floats(int nz, long rows_per_z, int N) { return (long)nz * cdiv_l(rows_per_z, 256) * N; }
+int launch_colsum(const float* dy, int nz, long rows_per_z, int N, long ld, float* out, long ld_out, int accumulate, float* ws, hipStream_t s) {
+  T2P_REQUIRE(dy && out && nz > 0 && nz <= 65535 && rows_per_z > 0 && N > 0 && ld >= N && ld_out >= N, "colsum arguments");
   const int rpb = 256, nchunk = cdiv_l(rows_per_z, rpb);
   T2P_REQUIRE(nchunk <= 65535, "colsum rows");
-  hipLaunchKernelGGL(colsum_partial_kernel, dim3(cdiv_l(N, 64), nchunk, nz), dim3(256), 0, s, dy, rows_per_z, N, ld, ws, rpb);
-  hipLaunchKernelGGL(colsum_finish_kernel, dim3(cdiv_l(N, 64), nz), dim3(256), 0, s, (const float*)ws, nchunk, N, out, ld_out, accumulate);
-  T2P_HIP_CHECK(hipGetLastError());
-  return T2P_OK;
-}
-int launch_colsum(const float* dy, long rows, int N, long ld, float* out, hipStream_t s) {
-  T2P_REQUIRE(dy && out && rows > 0 && N > 0 && ld >= N, "colsum arguments");
-  const int rpb = 256;
-  T2P_REQUIRE(cdiv_l(rows, rpb) <= 65535, "colsum rows");
-  hipLaunchKernelGGL(colsum_kernel, dim3(cdiv_l(N, 64), cdiv_l(rows, rpb), 1), dim3(256), 0, s, dy, rows, N, ld, out, 0L, rpb);
-  T2P_HIP_CHECK(hipGetLastError());
-  return T2P_OK;
-}
-int launch_colsum_per_sample(const float* dy, int B, int HW, int N, float* out, long ld_out, int accumulate, hipStream_t s) {
-  T2P_REQUIRE(dy && out && B > 0 && B <= 65535 && HW > 0 && N > 0 && ld_out >= N, "colsum_per_sample arguments");
-  if (!accumulate) T2P_HIP_CHECK(hipMemset2DAsync(out, ld_out * sizeof(float), 0, N * sizeof(float), B, s));
-  const int rpb = 256;
-  hipLaunchKernelGGL(colsum_kernel, dim3(cdiv_l(N, 64), cdiv_l(HW, rpb), B), dim3(256), 0, s, dy, (long)HW, N, (long)N, out, ld_out, rpb);
+  if (!ws) {
+    if (!accumulate) T2P_HIP_CHECK(hipMemset2DAsync(out, ld_out * sizeof(float), 0, N * sizeof(float), nz, s));
+    hipLaunchKernelGGL(colsum_kernel, dim3(cdiv_l(N, 64), nchunk, nz), dim3(256), 0, s, dy, rows_per_z, N, ld, out, ld_out, rpb);
+  } else {
+    hipLaunchKernelGGL(colsum_partial_kernel, dim3(cdiv_l(N, 64), nchunk, nz), dim3(256), 0, s, dy, rows_per_z, N, ld, ws, rpb);
+    hipLaunchKernelGGL(colsum_finish_kernel, dim3(cdiv_l(N, 64), nz), dim3(256), 0, s, (const float*)ws, nchunk, N, out, ld_out, accumulate);
+  }
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }
@@ -1296,17 +1271,15 @@ __global__ __launch_bounds__(256) void sumsq_finish_kernel(const double* __restr
   a = block_sum_256_d(a, sh);
   if (threadIdx.x == 0) *out = a;
 }
-int launch_sumsq_fixed(const float* g, long n, double* partial, double* out, hipStream_t s) {
-  T2P_REQUIRE(g && partial && out && n > 0, "sumsq arguments");
-  const int nb = grid_for(n, 256, SUMSQ_BLOCKS);
-  hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nb), dim3(256), 0, s, g, n, partial);
-  hipLaunchKernelGGL(sumsq_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, nb, out);
-  T2P_HIP_CHECK(hipGetLastError());
-  return T2P_OK;
-}
-int launch_sumsq(const float* g, long n, double* out, hipStream_t s) {
+int launch_sumsq(const float* g, long n, double* partial, double* out, hipStream_t s) {
   T2P_REQUIRE(g && out && n > 0, "sumsq arguments");
-  hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for(n, 256, 1024)), dim3(256), 0, s, g, n, out);
+  const int nb = grid_for(n, 256, SUMSQ_BLOCKS);
+  if (!partial) {
+    hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, s, g, n, out);
+  } else {
+    hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nb), dim3(256), 0, s, g, n, partial);
+    hipLaunchKernelGGL(sumsq_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)partial, nb, out);
+  }
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }
