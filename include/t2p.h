@@ -171,6 +171,7 @@ int t2p_sampler_count_dispatches(t2p_sampler* s, float* x, float* x_mean, void* 
  * t2p_train_step        <- step_fn(state, batch, condition), train=True (losses.py:165-176): zero_grad, loss, backward,
  *                          optimize_fn (warm-up on state['step'], clip_grad_norm_, Adam: losses.py:41-49), step += 1, ema.update
  * t2p_train_eval_loss   <- step_fn with train=False (losses.py:177-183): the loss under the EMA weights, model in eval mode
+ * t2p_train_set_ss_blocks <- block_dropout(coords_6d, batch["ss_indices"]) under the ss condition (losses.py:54-64, called at :106-107)
  * The model runs in train mode (models/utils.py:116-118): Dropout_0 of every residual block is active when dropout > 0.       */
 typedef struct t2p_train_config {
   double lr, beta1, eps, weight_decay;   /* optim.lr / beta1 / eps / weight_decay; beta2 = 0.999 as get_optimizer fixes it    */
@@ -219,6 +220,19 @@ int t2p_train_set_sde(t2p_trainer* t, int sde, double beta_min, double beta_max,
 /* parity runs: keep-masks of Dropout_0 for the next pass, one device uint8 [batch][H][W][C] (NHWC, the block's own resolution and
  * width) per residual block in forward order; n = 0 returns to on-device Philox masks */
 int t2p_train_set_dropout_masks(t2p_trainer* t, const uint8_t* const* device_masks, int n);
+/* block_dropout (losses.py:54-64, called at :106-107 when "ss" is in the condition): every secondary-structure block of every sample
+ * is dropped with probability p (the reference: 0.2); a dropped block zeroes channels 4:7 on its rows start:end and on its columns
+ * start:end.  host_blocks: host int32 [n][3] = (sample, start, end), end exclusive, Python slice semantics on an axis of length L (end
+ * clamped to L, start >= end empty, overlapping blocks fine).  host_drop: host uint8 [n], the decision per block (parity runs, or draws
+ * made by the caller in the reference's order), or NULL = drawn on the device: block k is dropped iff u < (float)p, u one Philox
+ * uniform keyed by the trainer seed (counter k, a stream of its own per loss call).  Both arrays are copied at the call.  The list is
+ * per-batch data: the NEXT t2p_train_loss / t2p_train_step / t2p_train_eval_loss consumes it (the reference applies the dropout with
+ * train=False too) and clears it; n = 0 clears it.  The reference zeroes its coords_6d argument in place; here batch->coords_6d is
+ * NOT modified, the zeroing happens on the way into the perturbed input (both branches of losses.py:129's torch.where see it).
+ * Refused with nothing changed: n > 0 on a trainer whose cond_flags lacks bit 2; p outside [0, 1]; a negative start or end (not
+ * wrapped: the dataset never writes one); sample < 0.  A sample >= batch shows at the pass: that pass returns an error, computes and
+ * changes nothing, and the list is cleared. */
+int t2p_train_set_ss_blocks(t2p_trainer* t, const int32_t* host_blocks, int n, const uint8_t* host_drop, double p);
 /* loss_host: host float; score_out (optional): device fp32 (batch, C, L, L), the score the loss was computed from */
 int t2p_train_loss(t2p_trainer* t, const t2p_train_batch* batch, int backward, float* loss_host, float* score_out, void* stream);
 int t2p_train_step(t2p_trainer* t, const t2p_train_batch* batch, float* loss_host, void* stream);
@@ -242,6 +256,13 @@ int t2p_op_tgemm(const float* A, int64_t sAm, int64_t sAk, const float* B, int64
 int t2p_op_tgemm16(int dtype, const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBk, int64_t sBn, float* C, int64_t ldc,
                    int M, int N, int K, int nz, int64_t sAz, int64_t sBz, int64_t sCz, float alpha, float beta, const float* bias_n, int ksplit,
                    int conv, int H, int W, int conv_C, void* stream);
+/* block_dropout alone (losses.py:54-64; the training pass applies it at :106-107 through the same two kernels): out = x (device fp32
+ * (batch, C, L, L)) with channels 4:7 of the dropped blocks' rows and columns zeroed; out may alias x, otherwise x is untouched.
+ * host_blocks / host_drop / p as t2p_train_set_ss_blocks; seed / stream_id: the Philox key and stream of the device draws (host_drop
+ * NULL); drop_out_device (optional): device uint8 [n], the decisions used.  Refused: C < 7, a negative start or end, a sample outside
+ * [0, batch), p outside [0, 1]. */
+int t2p_op_ss_block_dropout(const float* x, float* out, int batch, int C, int L, const int32_t* host_blocks, int n,
+                            const uint8_t* host_drop, double p, uint64_t seed, uint64_t stream_id, uint8_t* drop_out_device, void* stream);
 /* backward halves of the operators (gradients accumulate into dx / dgamma / dbeta / du) */
 int t2p_op_groupnorm_backward(const float* x, const float* dy, const float* gamma, const float* beta, int silu, int batch, int HW, int C,
                               int groups, float eps, float* dx, float* dgamma, float* dbeta, void* stream);

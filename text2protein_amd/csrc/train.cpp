@@ -258,6 +258,33 @@ int Trainer::set_dropout_masks(const uint8_t* const* masks, int n) {
   drop_masks_.assign(masks, masks + n);
   return T2P_OK;
 }
+int Trainer::set_ss_blocks(const int32_t* host_blocks, int n, const uint8_t* host_drop, double p) {
+  T2P_REQUIRE(n >= 0 && (n == 0 || host_blocks), "set_ss_blocks arguments");
+  if (n == 0) { ss_n_ = 0; return T2P_OK; }
+  T2P_REQUIRE(tc_.cond_flags & 2, "set_ss_blocks: this trainer was created without the ss condition (cond_flags bit 2)");
+  T2P_REQUIRE(p >= 0.0 && p <= 1.0, "set_ss_blocks: the dropout probability must lie in [0, 1]");
+  int max_sample = -1;
+  for (int k = 0; k < n; ++k) {
+    const int32_t* b = host_blocks + 3 * k;
+    T2P_REQUIRE(b[0] >= 0, "set_ss_blocks: block " + std::to_string(k) + " has a negative sample index");
+    T2P_REQUIRE(b[1] >= 0 && b[2] >= 0, "set_ss_blocks: block " + std::to_string(k) + " has a negative start or end (not wrapped: the dataset never writes one)");
+    max_sample = std::max(max_sample, (int)b[0]);
+  }
+  // no pass is in flight here (every loss / step / eval pass ends with a stream synchronisation before it returns), so the buffer is
+  // free to overwrite without a device-wide wait
+  if (n > ss_cap_) {                                // grows as needed; the list in it is replaced anyway
+    const int cap = std::max(n, 2 * ss_cap_);
+    int* nb = (int*)pool_.get((size_t)cap * 13);
+    if (!nb) return T2P_ERR_HIP;
+    if (ss_blocks_) pool_.put(ss_blocks_);
+    ss_blocks_ = nb; ss_drop_ = (uint8_t*)(nb + 3 * (size_t)cap); ss_cap_ = cap; ss_n_ = 0;
+  }
+  ss_n_ = 0;                                        // a failed copy leaves no list
+  T2P_HIP_CHECK(hipMemcpy(ss_blocks_, host_blocks, (size_t)n * 12, hipMemcpyHostToDevice));
+  if (host_drop) T2P_HIP_CHECK(hipMemcpy(ss_drop_, host_drop, (size_t)n, hipMemcpyHostToDevice));
+  ss_n_ = n; ss_max_sample_ = max_sample; ss_given_ = host_drop != nullptr; ss_p_ = p;
+  return T2P_OK;
+}
 
 // ---- pass-local memory ------------------------------------------------------------------------------------------------------------------
 float* Trainer::tmp(size_t bytes) {
@@ -695,7 +722,16 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool tra
     T2P_TRY(launch_philox_normal(zb, nx, tc_.seed, rng_z(), nullptr, s_));
     z = zb;
   }
-  T2P_TRY(launch_dsm_perturb(b.coords_6d, z, stdv, mean_coef, b.mask_pair, b.mask_inpaint, tc_.cond_flags, B, Cx, L, perturbed, mask, num_elem, s_));
+  // block_dropout (losses.py:54-64, :106-107): the dropped blocks as residue flags; coords_6d itself stays as the caller gave it
+  uint8_t* ss_rows = nullptr;
+  if (ss_pass_n_ > 0) {
+    ss_rows = (uint8_t*)tmp((size_t)B * L);
+    if (!ss_rows) return T2P_ERR_HIP;
+    T2P_TRY(launch_ss_block_rows(ss_blocks_, ss_pass_n_, ss_given_ ? ss_drop_ : nullptr, (float)ss_p_, tc_.seed, rng_ss(), B, L, ss_rows,
+                                 nullptr, s_));
+  }
+  T2P_TRY(launch_dsm_perturb(b.coords_6d, z, stdv, mean_coef, b.mask_pair, b.mask_inpaint, tc_.cond_flags, B, Cx, L, perturbed, mask, num_elem, s_,
+                             ss_rows));
 
   // UNetModel.forward (ncsnpp.py:220-263)
   T2P_ACT(x0, B, L, L, 8, false);
@@ -780,6 +816,11 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool tra
 
 int Trainer::loss(const t2p_train_batch& b, bool backward, bool use_ema, float* loss_host, float* score_out, hipStream_t s) {
   T2P_REQUIRE(loss_host, "loss output");
+  ss_pass_n_ = ss_n_;                             // the block list is per-batch data: this pass consumes it, whatever becomes of the pass
+  ss_n_ = 0;
+  T2P_REQUIRE(ss_pass_n_ == 0 || ss_max_sample_ < b.batch,
+              "ss blocks: sample index " + std::to_string(ss_max_sample_) + " >= batch " + std::to_string(b.batch) +
+                  "; nothing was computed or changed and the block list is cleared");
   s_ = s;
   if (backward) last_loss_finite_ = false;        // the overflow guard trusts only a completed backward pass
   if (backward) T2P_HIP_CHECK(hipMemsetAsync(Gr_, 0, (size_t)total_ * 4, s));      // optimizer.zero_grad()

@@ -47,6 +47,9 @@ class Trainer {
   int set_dropout_masks(const uint8_t* const* masks, int n);
   // the SDE of the loss (get_sde_loss_fn's `sde`): T2P_SDE_VE (after build), T2P_SDE_VP (std_table: host float[num_scales]) or T2P_SDE_SUBVP
   int set_sde(int sde, double beta_min, double beta_max, const float* std_table);
+  // block_dropout (losses.py:54-64, called at :106-107) of the NEXT loss / step / eval pass: host int32 [n][3] = (sample, start, end) and
+  // the per-block decisions (host uint8 [n]) or nullptr = drawn on the device at probability p.  Consumed by that pass, then cleared
+  int set_ss_blocks(const int32_t* host_blocks, int n, const uint8_t* host_drop, double p);
   // loss_fn (losses.py:105-134); with `backward` also d loss / d parameters into the gradient buffer (zeroed first: optimizer.zero_grad())
   int loss(const t2p_train_batch& b, bool backward, bool use_ema, float* loss_host, float* score_out, hipStream_t s);
   // step_fn with train=True (losses.py:165-176) = loss(backward) + apply()
@@ -83,6 +86,8 @@ class Trainer {
   unsigned long long rng_t() const { return (unsigned long long)loss_calls_; }
   unsigned long long rng_z() const { return (unsigned long long)(loss_calls_ * 4096 + 1); }
   unsigned long long rng_dropout(int k) const { return (unsigned long long)(loss_calls_ * 4096 + 16 + k); }
+  // the block-dropout decisions of the running loss call (counter = the block index); + 2 of the free ids + 2 .. + 15
+  unsigned long long rng_ss() const { return (unsigned long long)(loss_calls_ * 4096 + 2); }
 
   // forward ops: each appends its backward to tape_
   TT* act(int B, int H, int W, int C, bool needs_grad = true);
@@ -130,6 +135,12 @@ class Trainer {
   float* dwc_ = nullptr; size_t dwc_floats_ = 0;     // weight-gradient tile of the largest convolution, compute layout
   std::vector<const uint8_t*> drop_masks_;
   int drop_index_ = 0;
+  // secondary-structure blocks of the next pass (set_ss_blocks): device [cap][3] int32 followed by [cap] uint8 decisions
+  int* ss_blocks_ = nullptr; uint8_t* ss_drop_ = nullptr;
+  int ss_cap_ = 0, ss_n_ = 0, ss_max_sample_ = -1;
+  bool ss_given_ = false;           // explicit decisions (else drawn on the device at ss_p_)
+  double ss_p_ = 0.0;
+  int ss_pass_n_ = 0;               // the running pass: how many blocks it took over (0: none, the kernels of a pass without blocks)
 
   DevPool pool_;
   hipStream_t s_ = nullptr;

@@ -115,6 +115,13 @@ int t2p_train_set_dropout_masks(t2p_trainer* t, const uint8_t* const* device_mas
   API_END
 }
 
+int t2p_train_set_ss_blocks(t2p_trainer* t, const int32_t* host_blocks, int n, const uint8_t* host_drop, double p) {
+  API_BEGIN
+  T2P_REQUIRE(t, "null trainer");
+  return t->impl.set_ss_blocks(host_blocks, n, host_drop, p);
+  API_END
+}
+
 int t2p_train_loss(t2p_trainer* t, const t2p_train_batch* batch, int backward, float* loss_host, float* score_out, void* stream) {
   API_BEGIN
   T2P_REQUIRE(t && batch, "null argument");
@@ -178,6 +185,56 @@ int t2p_op_tgemm16(int dtype, const float* A, int64_t sAm, int64_t sAk, const fl
     (void)hipStreamSynchronize(s);
     (void)hipFree(ws);
   }
+  return rc;
+  API_END
+}
+
+// block_dropout alone, through the two kernels of the training pass: the residue flags, then dsm_perturb with an all-false pair mask
+// (every element takes the select's fallback branch, perturbed = the dropped x)
+int t2p_op_ss_block_dropout(const float* x, float* out, int batch, int C, int L, const int32_t* host_blocks, int n, const uint8_t* host_drop,
+                            double p, uint64_t seed, uint64_t stream_id, uint8_t* drop_out_device, void* stream) {
+  API_BEGIN
+  T2P_REQUIRE(x && out && batch > 0 && L > 0 && n >= 0 && (n == 0 || host_blocks), "ss_block_dropout arguments");
+  T2P_REQUIRE(C >= 7, "ss_block_dropout: channels 4:7 need the 8-channel layout (C >= 7)");
+  T2P_REQUIRE(p >= 0.0 && p <= 1.0, "ss_block_dropout: the dropout probability must lie in [0, 1]");
+  for (int k = 0; k < n; ++k) {
+    const int32_t* b = host_blocks + 3 * k;
+    T2P_REQUIRE(b[0] >= 0 && b[0] < batch, "ss_block_dropout: block " + std::to_string(k) + " names a sample outside the batch");
+    T2P_REQUIRE(b[1] >= 0 && b[2] >= 0, "ss_block_dropout: block " + std::to_string(k) + " has a negative start or end");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const size_t HW = (size_t)L * L, nx = (size_t)batch * C * HW;
+  if (n == 0) {
+    if (out != x) T2P_HIP_CHECK(hipMemcpyAsync(out, x, nx * 4, hipMemcpyDeviceToDevice, s));
+    return T2P_OK;
+  }
+  // one scratch allocation: a copy of x when out aliases it (the kernel's pointers are __restrict__: it never runs in place), [std |
+  // num_elem] floats, blocks, then the byte tables (pair mask = 0, rows, decisions, the mask output)
+  const size_t o_std = out == x ? nx * 4 : 0, o_blocks = o_std + (size_t)batch * 8, o_pair = o_blocks + (size_t)n * 12, o_rows = o_pair + batch * HW,
+               o_drop = o_rows + (size_t)batch * L, o_mask = o_drop + n, total = o_mask + nx;
+  char* ws = nullptr;
+  T2P_HIP_CHECK(hipMalloc(&ws, total));
+  int rc = T2P_OK;
+  hipError_t e = hipMemsetAsync(ws + o_std, 0, o_rows - o_std, s);       // std = 0, pair mask = all false
+  const float* src = x;
+  if (e == hipSuccess && out == x) {
+    e = hipMemcpyAsync(ws, x, nx * 4, hipMemcpyDeviceToDevice, s);
+    src = (const float*)ws;
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(ws + o_blocks, host_blocks, (size_t)n * 12, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && host_drop) e = hipMemcpyAsync(ws + o_drop, host_drop, (size_t)n, hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) {
+    set_last_error(std::string("ss_block_dropout: ") + hipGetErrorString(e));
+    rc = T2P_ERR_HIP;
+  }
+  if (rc == T2P_OK)
+    rc = launch_ss_block_rows((const int*)(ws + o_blocks), n, host_drop ? (const unsigned char*)(ws + o_drop) : nullptr, (float)p, seed, stream_id,
+                              batch, L, (unsigned char*)(ws + o_rows), drop_out_device, s);
+  if (rc == T2P_OK)                                                      // z is never read (the mask is false everywhere): any valid buffer
+    rc = launch_dsm_perturb(src, src, (const float*)(ws + o_std), nullptr, (const unsigned char*)(ws + o_pair), nullptr, 0, batch, C, L, out,
+                            (unsigned char*)(ws + o_mask), (float*)(ws + o_std) + batch, s, (const unsigned char*)(ws + o_rows));
+  (void)hipStreamSynchronize(s);                                         // host_blocks / host_drop and the scratch are free after the call
+  (void)hipFree(ws);
   return rc;
   API_END
 }

@@ -100,9 +100,19 @@ int launch_dsm_prepare_vp(const float* t_in, int B, float t_eps, double beta_min
 // mask[b][c][y][x] = mask_pair[b][y][x] && conditional_mask (length: c != C - 1; ss: c not in 4..6; inpainting: mask_inpaint[b][y][x]);
 // perturbed = mask ? mean_coef[b] x + std[b] z : x (mean_coef == nullptr: the VE form x + std[b] z);  num_elem[b] = #mask
 // (all NCHW; cond_flags: 1 length, 2 ss, 4 inpainting)
+// ss_rows (optional, [B][L] from launch_ss_block_rows): block_dropout (losses.py:54-64) on the way in -- for c in 4..6 the x that enters
+// BOTH branches of the select is 0 where ss_rows[b][y] | ss_rows[b][x].  The reference zeroes its coords_6d argument in place; here x
+// itself is never written, the zeroing happens on the way into `perturbed`.  Without ss_rows: the kernels of a pass without blocks
 int launch_dsm_perturb(const float* x, const float* z, const float* std, const float* mean_coef, const unsigned char* mask_pair,
                        const unsigned char* mask_inpaint, int cond_flags, int B, int C, int L, float* perturbed, unsigned char* mask,
-                       float* num_elem, hipStream_t s);
+                       float* num_elem, hipStream_t s, const unsigned char* ss_rows = nullptr);
+// secondary-structure block list -> residue flags: rows [B][L] uint8 = 1 where residue r lies in a DROPPED block (zeroed here first).
+// blocks: device int32 [n][3] = (sample, start, end), end exclusive, Python slice semantics on an axis of length L (end clamped to L,
+// start >= end empty, overlaps fine; a negative index or a sample outside [0, B) writes nothing -- the host callers refuse them).
+// drop: device uint8 [n] explicit decisions, or nullptr = drawn here: block k is dropped iff u < p, u = (c0 >> 8) 2^-24 of Philox4x32-10
+// with counter k, stream id stream_id and key seed (the uniform of dsm_prepare's t).  drop_out (optional, [n]): the decisions used
+int launch_ss_block_rows(const int* blocks, int n, const unsigned char* drop, float p, unsigned long long seed, unsigned long long stream_id,
+                         int B, int L, unsigned char* rows, unsigned char* drop_out, hipStream_t s);
 // o: the head convolution's output NHWC [B][L L][ldo]; scale[b]: the signed per-sample output scale of dsm_prepare; score = scale[b] o;
 // r = score std[b] + z; loss_sum[b] += sum mask r^2 (double);  d_o [B][L L][ld_do] = 2 r mask std scale / ((num_elem + 1e-8) B), pad columns zero
 int launch_dsm_loss(const float* o, long ldo, const float* z, const float* std, const float* scale, const unsigned char* mask,

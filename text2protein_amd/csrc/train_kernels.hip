@@ -15,6 +15,8 @@
 // Layouts: activations NHWC [B][H W][C] fp32 (the inference engine's layout), the state / noise / masks NCHW as in the reference.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "train_kernels.h"
 
 namespace t2p {
@@ -1148,13 +1150,48 @@ int launch_dsm_prepare_vp(const float* t_in, int B, float t_eps, double beta_min
   return T2P_OK;
 }
 
+// ---- secondary-structure block dropout (losses.py:54-64, called at :106-107) ---------------------------------------------------------------
+// one workgroup per block (sample, start, end): rows[sample][r] = 1 for r in start .. min(end, L) when the block is dropped.  The decision is
+// drop[n] when given, else u < p with u the Philox uniform dsm_time forms ((c0 >> 8) 2^-24), counter = the block index, key = seed.  Every
+// writer writes 1 (plain byte stores); rows is zeroed by the launcher.  A block whose sample or start lies outside the table writes nothing
+__global__ __launch_bounds__(64) void ss_block_rows_kernel(const int* __restrict__ blocks, const int n, const unsigned char* __restrict__ drop,
+                                                           const float p, const unsigned long long seed, const unsigned long long stream_id,
+                                                           const int B, const int L, unsigned char* __restrict__ rows,
+                                                           unsigned char* __restrict__ drop_out) {
+  const int k = blockIdx.x;
+  if (k >= n) return;
+  bool d;
+  if (drop) {
+    d = drop[k] != 0;
+  } else {
+    uint32_t c0 = (uint32_t)k, c1 = 0, c2 = (uint32_t)stream_id, c3 = (uint32_t)(stream_id >> 32), k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (int r = 0; r < 10; ++r) { philox_round(c0, c1, c2, c3, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+    d = (c0 >> 8) * (1.0f / 16777216.0f) < p;
+  }
+  if (drop_out && threadIdx.x == 0) drop_out[k] = d ? 1 : 0;
+  const int b = blocks[3 * k], start = blocks[3 * k + 1], end = min(blocks[3 * k + 2], L);
+  if (!d || b < 0 || b >= B || start < 0) return;
+  for (int r = start + (int)threadIdx.x; r < end; r += 64) rows[(long)b * L + r] = 1;
+}
+int launch_ss_block_rows(const int* blocks, int n, const unsigned char* drop, float p, unsigned long long seed, unsigned long long stream_id,
+                         int B, int L, unsigned char* rows, unsigned char* drop_out, hipStream_t s) {
+  T2P_REQUIRE(blocks && rows && n > 0 && B > 0 && L > 0 && p >= 0.f && p <= 1.f, "ss_block_rows arguments");
+  T2P_HIP_CHECK(hipMemsetAsync(rows, 0, (size_t)B * L, s));
+  hipLaunchKernelGGL(ss_block_rows_kernel, dim3(n), dim3(64), 0, s, blocks, n, drop, p, seed, stream_id, B, L, rows, drop_out);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+
+// SS of dsm_perturb_kernel: the residue flags of the dropped blocks (SsRows), or none (NoSs: the kernel as it is without block dropout)
+struct NoSs {};
+struct SsRows { const unsigned char* rows; int L; };
 // grid (chunks, B)
-template <bool MEAN>
+template <bool MEAN, class SS = NoSs>
 __global__ __launch_bounds__(256) void dsm_perturb_kernel(const float* __restrict__ x, const float* __restrict__ z, const float* __restrict__ stdv,
                                                           const float* __restrict__ mean_coef, const unsigned char* __restrict__ mask_pair,
                                                           const unsigned char* __restrict__ mask_inpaint, const int flags, const int C,
                                                           const int HW, float* __restrict__ perturbed, unsigned char* __restrict__ mask,
-                                                          float* __restrict__ num_elem) {
+                                                          float* __restrict__ num_elem, const SS ss = SS()) {
   __shared__ float sh[4];
   const int b = blockIdx.y;
   const long per = (long)C * HW;
@@ -1168,7 +1205,13 @@ __global__ __launch_bounds__(256) void dsm_perturb_kernel(const float* __restric
     if ((flags & 2) && c >= 4 && c < 7) m = false;
     if ((flags & 4) && !mask_inpaint[(long)b * HW + p]) m = false;
     const long i = (long)b * per + j;
-    const float xv = x[i];
+    float xv = x[i];
+    if constexpr (std::is_same<SS, SsRows>::value) {          // block_dropout: channels 4:7 on the rows and the columns of a dropped block
+      if (c >= 4 && c < 7) {
+        const int pi = p / ss.L, pj = p - pi * ss.L;
+        if (ss.rows[(long)b * ss.L + pi] | ss.rows[(long)b * ss.L + pj]) xv = 0.f;
+      }
+    }
     if (MEAN) perturbed[i] = m ? mc * xv + sd * z[i] : xv;
     else perturbed[i] = m ? xv + sd * z[i] : xv;
     mask[i] = m ? 1 : 0;
@@ -1179,13 +1222,22 @@ __global__ __launch_bounds__(256) void dsm_perturb_kernel(const float* __restric
 }
 int launch_dsm_perturb(const float* x, const float* z, const float* std, const float* mean_coef, const unsigned char* mask_pair,
                        const unsigned char* mask_inpaint, int cond_flags, int B, int C, int L, float* perturbed, unsigned char* mask,
-                       float* num_elem, hipStream_t s) {
+                       float* num_elem, hipStream_t s, const unsigned char* ss_rows) {
   T2P_REQUIRE(x && z && std && mask_pair && perturbed && mask && num_elem && B > 0 && B <= 65535 && C > 0 && L > 0, "dsm_perturb arguments");
   T2P_REQUIRE(!(cond_flags & 4) || mask_inpaint, "dsm_perturb: the inpainting condition needs mask_inpaint");
+  T2P_REQUIRE(!ss_rows || C >= 7, "dsm_perturb: block dropout needs the 8-channel layout (channels 4:7)");
   T2P_HIP_CHECK(hipMemsetAsync(num_elem, 0, B * sizeof(float), s));
   const long per = (long)C * L * L;
   const dim3 grid(std::min(64, cdiv_l(per, 256)), B);
-  if (mean_coef)
+  if (ss_rows) {
+    const SsRows ss{ss_rows, L};
+    if (mean_coef)
+      hipLaunchKernelGGL((dsm_perturb_kernel<true, SsRows>), grid, dim3(256), 0, s, x, z, std, mean_coef, mask_pair, mask_inpaint, cond_flags, C,
+                         L * L, perturbed, mask, num_elem, ss);
+    else
+      hipLaunchKernelGGL((dsm_perturb_kernel<false, SsRows>), grid, dim3(256), 0, s, x, z, std, mean_coef, mask_pair, mask_inpaint, cond_flags, C,
+                         L * L, perturbed, mask, num_elem, ss);
+  } else if (mean_coef)
     hipLaunchKernelGGL(dsm_perturb_kernel<true>, grid, dim3(256), 0, s, x, z, std, mean_coef, mask_pair, mask_inpaint, cond_flags, C, L * L, perturbed,
                        mask, num_elem);
   else

@@ -21,6 +21,7 @@ There is no CPU fallback: without a HIP device ``HipTrainModel`` raises.
 from __future__ import annotations
 
 import ctypes as C
+import random
 from collections import OrderedDict
 
 import numpy as np
@@ -43,6 +44,56 @@ def condition_flags(condition) -> int:
             raise ValueError(f"unknown condition {c!r}")       # the reference ignores unknown names silently (losses.py:115-123)
         flags |= _COND_FLAGS[c]
     return flags
+
+
+def parse_ss_indices(ss_indices, batch_size=None):
+    """``batch["ss_indices"]`` (one string per sample, ``"a:b,c:d"``; ``''`` = no secondary-structure annotation, losses.py:56) as the
+    block list of ``t2p_train_set_ss_blocks``: ``[(sample, start, end), ...]``, samples in order, blocks in string order -- the order in
+    which the reference draws its ``random.random()`` per block (losses.py:55-58).  Raises ``T2PError`` on a list of the wrong length,
+    on a range that is not two integers and on a negative index (Python would wrap it; the dataset never writes one, so it is refused
+    rather than guessed at)."""
+    if isinstance(ss_indices, str) or not hasattr(ss_indices, "__len__"):
+        raise T2PError("ss_indices must be a sequence of strings, one per sample")
+    if batch_size is not None and len(ss_indices) != int(batch_size):
+        raise T2PError(f"ss_indices holds {len(ss_indices)} entries, the batch has {int(batch_size)} samples")
+    blocks = []
+    for b, text in enumerate(ss_indices):
+        if not isinstance(text, str):
+            raise T2PError(f"ss_indices[{b}] is not a string: {text!r}")
+        if text == "":
+            continue
+        for rng in text.split(","):
+            parts = rng.split(":")
+            try:
+                if len(parts) != 2:
+                    raise ValueError(rng)
+                start, end = int(parts[0]), int(parts[1])
+            except ValueError:
+                raise T2PError(f"ss_indices[{b}]: {rng!r} is not a range 'start:end' of two integers") from None
+            if start < 0 or end < 0:
+                raise T2PError(f"ss_indices[{b}]: negative index in {rng!r}")
+            blocks.append((b, start, end))
+    return blocks
+
+
+def draw_block_decisions(blocks, block_dropout=0.2):
+    """One ``random.random() < block_dropout`` per block in list order (losses.py:58): after the same ``random.seed`` the same blocks are
+    dropped as in the reference."""
+    return [1 if random.random() < block_dropout else 0 for _ in blocks]
+
+
+def _set_batch_ss_blocks(model, batch, condition, block_dropout, draw):
+    """losses.py:106-107: under the ``ss`` condition the blocks of ``batch["ss_indices"]`` go to the next pass.  A batch WITHOUT the key
+    runs as before this existed -- nothing is set, nothing is dropped -- where the reference would raise ``KeyError``."""
+    if "ss" not in (condition or []) or "ss_indices" not in batch:
+        return
+    blocks = parse_ss_indices(batch["ss_indices"], batch["coords_6d"].shape[0])
+    model.set_ss_blocks(blocks, drop=draw_block_decisions(blocks, block_dropout) if draw == "host" else None, p=block_dropout)
+
+
+def _check_draw(draw):
+    if draw not in ("host", "device"):
+        raise ValueError(f"block_dropout_draw must be 'host' or 'device', not {draw!r}")
 
 
 class HipTrainModel:
@@ -181,6 +232,23 @@ class HipTrainModel:
         arr = (C.c_void_p * max(len(masks), 1))(*[m.data_ptr() for m in masks])
         check(self.lib.t2p_train_set_dropout_masks(self._h, arr, len(masks)))
 
+    def set_ss_blocks(self, blocks, drop=None, p=0.2):
+        """``block_dropout`` (losses.py:54-64) for the NEXT ``loss`` / ``step`` / ``eval_loss``, which consumes the list: ``blocks`` =
+        ``(sample, start, end)`` triples (``parse_ss_indices``), ``drop`` = one decision per block or None = drawn on the device at
+        probability ``p``.  ``batch["coords_6d"]`` is not modified (the reference zeroes it in place).  ``[]`` clears the list."""
+        arr = np.ascontiguousarray(np.asarray(blocks, dtype=np.int64).reshape(-1, 3))
+        if arr.size and (np.abs(arr) > 2 ** 31 - 1).any():
+            raise T2PError("ss block index out of the int32 range")
+        arr = arr.astype(np.int32)
+        n = arr.shape[0]
+        d = None
+        if drop is not None:
+            d = np.ascontiguousarray(np.asarray(drop).reshape(-1) != 0, dtype=np.uint8)
+            if d.shape[0] != n:
+                raise T2PError(f"{d.shape[0]} block decisions for {n} blocks")
+        check(self.lib.t2p_train_set_ss_blocks(self._h, C.c_void_p(arr.ctypes.data) if n else None, n,
+                                               C.c_void_p(d.ctypes.data) if d is not None and n else None, float(p)))
+
     def _batch(self, batch, t=None, z=None):
         dev = self.device
         hold = [batch["coords_6d"].to(dev, torch.float32).contiguous(), batch["mask_pair"].to(dev, torch.uint8).contiguous(),
@@ -197,11 +265,20 @@ class HipTrainModel:
                 setattr(tb, key, v.data_ptr())
         return tb, hold
 
+    def _pass_inputs(self, batch, t, z, need_weights=True):
+        """``_batch`` for a pass.  A pass that fails here never reaches the library, so a block list set for it (``set_ss_blocks``) is
+        cleared: it is this batch's data and must not reach whichever pass comes next."""
+        try:
+            if need_weights and not self._loaded:
+                raise T2PError("load weights before training")
+            return self._batch(batch, t, z)
+        except Exception:
+            self.lib.t2p_train_set_ss_blocks(self._h, None, 0, None, 0.0)
+            raise
+
     def loss(self, batch, t=None, z=None, backward=False, return_score=False):
         """``loss_fn`` (losses.py:105-134); ``t`` / ``z`` = the draws of :106-107 (None: drawn on the device)."""
-        if not self._loaded:
-            raise T2PError("load weights before training")
-        tb, hold = self._batch(batch, t, z)
+        tb, hold = self._pass_inputs(batch, t, z)
         out = C.c_float()
         score = torch.empty_like(hold[0]) if return_score else None
         check(self.lib.t2p_train_loss(self._h, C.byref(tb), int(backward), C.byref(out), ptr(score), stream_ptr()))
@@ -209,9 +286,7 @@ class HipTrainModel:
 
     def step(self, batch, t=None, z=None):
         """``step_fn`` with train=True (losses.py:165-176) in one call."""
-        if not self._loaded:
-            raise T2PError("load weights before training")
-        tb, hold = self._batch(batch, t, z)
+        tb, hold = self._pass_inputs(batch, t, z)
         out = C.c_float()
         check(self.lib.t2p_train_step(self._h, C.byref(tb), C.byref(out), stream_ptr()))
         return float(out.value)
@@ -236,7 +311,7 @@ class HipTrainModel:
 
     def eval_loss(self, batch, t=None, z=None):
         """``step_fn`` with train=False (losses.py:177-183): the loss under the EMA weights."""
-        tb, hold = self._batch(batch, t, z)
+        tb, hold = self._pass_inputs(batch, t, z, need_weights=False)
         out = C.c_float()
         check(self.lib.t2p_train_eval_loss(self._h, C.byref(tb), C.byref(out), stream_ptr()))
         return float(out.value)
@@ -373,10 +448,16 @@ class ExponentialMovingAverage:
         self.model.set_step(cur[0], ema_updates=int(state_dict["num_updates"]))
 
 
-def get_sde_loss_fn(sde, train, eps=1e-5):
+def get_sde_loss_fn(sde, train, eps=1e-5, block_dropout=0.2, block_dropout_draw="host"):
     """losses.py:66-136 for ``sde`` = VESDE, VPSDE or subVPSDE (the model takes the SDE on first use and keeps it).  ``batch["context"]`` holds the caption embedding (B, T, context_dim); with raw captions pass
-    ``llm_components`` = a callable ``captions -> embedding`` (text2protein_amd.text_context.TextContextProducer)."""
+    ``llm_components`` = a callable ``captions -> embedding`` (text2protein_amd.text_context.TextContextProducer).
+
+    With ``"ss"`` in ``condition`` and ``batch["ss_indices"]`` present, every block is dropped with probability ``block_dropout``
+    (losses.py:54-64, :106-107; train and eval alike).  ``block_dropout_draw="host"``: ``random.random()`` once per block in the
+    reference's order, so the same ``random.seed`` drops the same blocks; ``"device"``: drawn on the GPU from the trainer seed.  A batch
+    without ``ss_indices`` has nothing dropped (the reference would raise ``KeyError``)."""
     _sde_key(sde)
+    _check_draw(block_dropout_draw)
 
     def loss_fn(model, batch, condition=None, llm_components=None, t=None, z=None):
         model.set_sde(sde)
@@ -386,6 +467,7 @@ def get_sde_loss_fn(sde, train, eps=1e-5):
             if llm_components is None:
                 raise T2PError("the batch holds no `context`; pass llm_components=TextContextProducer(...)")
             batch = dict(batch, context=llm_components(batch["caption"]))
+        _set_batch_ss_blocks(model, batch, condition, block_dropout, block_dropout_draw)
         if train:
             return model.loss(batch, t=t, z=z, backward=False)
         return model.eval_loss(batch, t=t, z=z)
@@ -393,13 +475,14 @@ def get_sde_loss_fn(sde, train, eps=1e-5):
     return loss_fn
 
 
-def get_step_fn(sde, train, optimize_fn=None, dist=None):
-    """losses.py:140-186.  ``dist`` (an initialised ``torch.distributed`` module, text2protein_amd.distributed.init_process_group):
+def get_step_fn(sde, train, optimize_fn=None, dist=None, block_dropout=0.2, block_dropout_draw="host"):
+    """losses.py:140-186.  ``block_dropout`` / ``block_dropout_draw``: as in ``get_sde_loss_fn`` (each rank drops the blocks of its shard).  ``dist`` (an initialised ``torch.distributed`` module, text2protein_amd.distributed.init_process_group):
     data-parallel training, one process per GPU -- each rank takes its shard of the batch, the flat gradient buffer is averaged over
     the ranks with ONE all-reduce (RCCL over xGMI) and every rank applies the same update; the returned loss is the mean over the
     ranks.  With equal shards this is the reference's DataParallel step on the concatenated batch (the loss is a mean of per-sample
     terms, losses.py:128-131)."""
     _sde_key(sde)
+    _check_draw(block_dropout_draw)
     world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
 
     def step_fn(state, batch, condition=None, t=None, z=None):
@@ -415,6 +498,7 @@ def get_step_fn(sde, train, optimize_fn=None, dist=None):
         if train:
             if optimize_fn is not None:
                 optimize_fn(state["optimizer"], model.parameters(), step=state["step"])
+            _set_batch_ss_blocks(model, batch, condition, block_dropout, block_dropout_draw)
             prev = model.get_step()
             model.set_step(state["step"])
             if world == 1:
@@ -425,7 +509,11 @@ def get_step_fn(sde, train, optimize_fn=None, dist=None):
                     raise
             else:
                 from . import distributed as D
-                loss = model.loss(batch, t=t, z=z, backward=True)
+                try:
+                    loss = model.loss(batch, t=t, z=z, backward=True)
+                except T2PError:
+                    model.set_step(*prev)                         # a refused pass (a block outside the batch) changes nothing
+                    raise
                 D.allreduce_mean_(model.grad_view(), dist)        # one collective over the whole gradient
                 loss = D.mean_over_ranks(loss, dist, model.device)
                 try:
@@ -435,6 +523,7 @@ def get_step_fn(sde, train, optimize_fn=None, dist=None):
                     raise
             state["step"] += 1
             return loss
+        _set_batch_ss_blocks(model, batch, condition, block_dropout, block_dropout_draw)
         return model.eval_loss(batch, t=t, z=z)                  # ema.store / copy_to / loss / restore (losses.py:177-183)
 
     return step_fn

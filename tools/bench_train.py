@@ -1,6 +1,11 @@
 """Time the training step (t2p_train_step: loss + backward + Adam + EMA) at a BASELINE model size.
 
     python tools/bench_train.py --config cond_length.yml --batch 8 --steps 5 [--tokens 64] [--dropout 0.1] [--dtype f32|f16|bf16] [--sde ve|vp|subvp]
+                                [--condition length,ss [--ss-blocks 64]]
+
+--ss-blocks N: N synthetic secondary-structure blocks per step (8 residues each, spread over the samples and the 100 valid residues),
+dropped on the device at the reference's p = 0.2; needs the `ss` condition, which needs an 8-channel configuration
+(cond_length_inpainting.yml with --condition length,ss).
 
 Prints one JSON line: ms per step, samples/s, the loss sequence, device memory, and the achieved matrix rate against the peak of the
 compute dtype's MFMA (157.3 TFLOP/s f32, 2500 TFLOP/s f16 / bf16), counting a step as 3 x the forward pass AS EXECUTED (the text K / V projections are inside a training
@@ -32,12 +37,16 @@ def main():
     ap.add_argument("--dropout", type=float, default=-1.0)
     ap.add_argument("--dtype", default="f32", choices=sorted(PEAK_TFLOPS))
     ap.add_argument("--sde", default="ve", choices=["ve", "vp", "subvp"], help="the SDE of the loss")
+    ap.add_argument("--condition", default="", help="override model.condition, comma-separated (e.g. length,ss)")
+    ap.add_argument("--ss-blocks", type=int, default=0, help="synthetic secondary-structure blocks per step, drawn on the device")
     a = ap.parse_args()
     from text2protein_amd import losses, sde_lib, synth
     from text2protein_amd.config import load_config
     over = {"data.max_res_num": a.L or (256 if "large" in a.config else 128)}
     if a.dropout >= 0:
         over["model.dropout"] = a.dropout
+    if a.condition:
+        over["model.condition"] = a.condition.split(",")
     cfg = load_config(os.path.join(ROOT, "configs", a.config), **over)
     cfg.device = "cuda:0"
     if "optim" not in cfg:
@@ -62,19 +71,28 @@ def main():
     step_fn = losses.get_step_fn(sde, train=True, optimize_fn=losses.optimization_manager(cfg))
     state = dict(model=model, optimizer=losses.get_optimizer(cfg, model.parameters()),
                  ema=losses.ExponentialMovingAverage(model.parameters(), decay=cfg.model.ema_rate), step=5000)
+    blocks = [(k % B, (8 * (k // B)) % 96, (8 * (k // B)) % 96 + 8) for k in range(a.ss_blocks)]
+    if blocks and "ss" not in (cfg.model.condition or []):
+        raise SystemExit("--ss-blocks needs the ss condition (--condition length,ss on an 8-channel configuration)")
+
+    def one_step():
+        if blocks:
+            model.set_ss_blocks(blocks, drop=None, p=0.2)       # per-batch data: set before every step, consumed by it
+        return step_fn(state, batch, condition=cfg.model.condition)
+
     seq = []
     for _ in range(a.warmup):
-        seq.append(step_fn(state, batch, condition=cfg.model.condition))
+        seq.append(one_step())
     torch.cuda.synchronize()
     t0 = time.time()
     for _ in range(a.steps):
-        seq.append(step_fn(state, batch, condition=cfg.model.condition))
+        seq.append(one_step())
     torch.cuda.synchronize()
     dt = (time.time() - t0) / a.steps
     gf = FWD_GFLOP.get(a.config, 0.0) * 3 * B
     out = {"metric": f"training step ({'fp32' if a.dtype == 'f32' else a.dtype})", "dtype": a.dtype, "sde": a.sde, "config": a.config, "batch": B, "L": L,
            "tokens": a.tokens, "ms_per_step": dt * 1e3, "samples_per_s": B / dt, "losses": [round(v, 5) for v in seq],
-           "device_GiB": model.device_bytes() / 2 ** 30}
+           "device_GiB": model.device_bytes() / 2 ** 30, "channels": C, "condition": list(cfg.model.condition or []), "ss_blocks": len(blocks)}
     tf = gf / dt / 1e3
     if a.dtype == "f32":
         out.update(tflops_f32=tf, frac_of_f32_peak=tf / PEAK_TFLOPS["f32"])
