@@ -412,6 +412,20 @@ int t2p_op_convert(const float* in, void* out, int dtype, int64_t n, void* strea
  * first lengths[b]^2 entries are clip(x[c][mask == 1], -1, 1) in row-major order (= .reshape(L, L)) and its inverse
  * scaling (dist+1)*10, omega*pi, theta*pi, (phi+1)*pi/2. */
 int t2p_op_decode_6d(const float* x, int batch, int channels, int L, float* clipped, float* absval, int32_t* lengths, void* stream);
+/* 6D encode of backbones, the featuriser behind utils.py:108-137: dataset.py:396-450 (get_coords6d: virtual Cb, Cb-Cb distance
+ * within 20 A, omega / theta dihedrals, phi angle, normalised to [-1, 1]), :200-239 (residue and pair masks, padding channel, every
+ * channel times mask_pair) and :114-168 (get_coarse_constraints: helix, beta and block-adjacency channels), padded as PaddingCollate
+ * does (:452-506).  xyz = (batch, L, 3, 3) fp32 device, N / CA / C per residue; nres = (batch) int32 device; atom_ok = (batch, L, 3)
+ * uint8 device or NULL (every atom present; a missing atom counts as (0, 0, 0) whatever xyz holds).  channels = 5, or 8 with the
+ * three secondary-structure channels at 4:7.  host_blocks = n_blocks int32 quadruples (sample, start, last, kind) on the HOST,
+ * kind 0 helix / 1 beta, per sample the helices first, then the strands, each in chain order (the order of the reference's
+ * "start:last" string); the range is the reference's half-open [start:last], `last` being the block's last residue.  Only with
+ * channels = 8; without blocks channels 4:7 are zero.  Outputs: coords_6d = (batch, channels, L, L) fp32, mask_pair =
+ * (batch, L, L) uint8, every element written.  Refused before anything is launched (status and message, outputs untouched):
+ * nres[b] outside [1, L], a block outside [0, nres) of its sample, start > last, a sample index outside the batch, a kind other
+ * than 0 / 1, blocks with channels = 5, any other channel count.  nres is read back on the host: the call synchronises the stream. */
+int t2p_op_encode_6d(const float* xyz, const int32_t* nres, const uint8_t* atom_ok, int batch, int channels, int L,
+                     const int32_t* host_blocks, int n_blocks, float* coords_6d, uint8_t* mask_pair, void* stream);
 /* text context = embed_tokens(ids), sampling_6d.py:134-137: out[(b,t)][:] = table[ids[(b,t)]][:] as fp32; the table
  * ([vocab][dim], fp32 / bf16 / f16 by table_dtype) stays resident.  *bad_flag (device int, zeroed by the caller) is
  * set to 1 when an id falls outside [0, vocab). */

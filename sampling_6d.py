@@ -16,10 +16,14 @@ Differences, all at the edges of the hot path:
     synthetic (``--context synthetic``).
   * ``--decode`` additionally writes ``decoded_<id>.npz`` per sample: the reference's first folding stage
     (sampling_rosetta.py:69-96: mask rounding, crop, clip, inverse scaling) done on the device.
-  * ``--pdb`` conditions need biotite and are broken in the reference: refused.  Their tensor half is
-    reachable through ``--inpaint_coords <file.pt|synthetic>`` (the featurised chain the reference would have computed from
-    the PDB file): the conditions named in ``config.model.condition`` (length / ss / inpainting with ``--mask_info``) are
-    built from it exactly as ``get_condition_from_batch`` does (utils.py:84-106).  ``--mask_info`` alone is an error.
+  * ``--pdb FILE [--chain A] [--mask_info 1:5,10:15] [--sse LETTERS|FILE]``: the conditions of ``config.model.condition``
+    from one chain of a PDB file (utils.py:122-137).  The reference goes through biotite there (and is broken, SURVEY.md 2
+    row 10); here the backbone is read by a small reader of our own and featurised on the GPU (text2protein_amd/encode.py:
+    dataset.py:114-168, :200-239, :396-450).  The secondary-structure letters of an 8-channel model (biotite's P-SEA in the
+    reference) are an input: ``--sse`` takes one of a / b / c per residue, or a file holding them.  Without ``--mask_info``
+    the reference's default "1:5,10:15" applies.
+  * ``--inpaint_coords <file.pt|synthetic>`` gives the same conditions from maps featurised elsewhere: built exactly as
+    ``get_condition_from_batch`` does (utils.py:84-106).  ``--mask_info`` without either source is an error.
   * ``checkpoint`` may be the word ``synthetic`` (hash-generated weights, no file needed).
   * extra flags: --dtype (f32|f16|bf16), --seed, --ids, --num_scales / --max_res_num overrides.
 Under ``python -m torch.distributed.run --nproc-per-node N`` (or with ``--gpus N``, which starts the N ranks
@@ -47,7 +51,10 @@ def main():
     parser.add_argument("--pdb", type=str, default=None)
     parser.add_argument("--chain", type=str, default="A")
     parser.add_argument("--mask_info", type=str, default=None,
-                        help="inpainting residue ranges (reference default '1:5,10:15'); needs --inpaint_coords")
+                        help="inpainting residue ranges (reference default '1:5,10:15'); needs --pdb or --inpaint_coords")
+    parser.add_argument("--sse", type=str, default=None,
+                        help="with --pdb and an 8-channel model: the chain's secondary-structure letters (one of a/b/c per residue), "
+                             "or a file holding them")
     parser.add_argument("--tag", type=str, default="test")
     parser.add_argument("--device", type=str, default="cuda")
     parser.add_argument("--batch_size", type=int, default=32)
@@ -77,11 +84,12 @@ def main():
     args = parser.parse_args()
 
     assert not (args.pdb is not None and args.select_length)
-    if args.pdb is not None:
-        raise SystemExit("--pdb conditions are outside the sampling hot path (need biotite; see SURVEY.md section 2, row 10); "
-                         "pass the featurised maps with --inpaint_coords instead")
-    if args.mask_info is not None and args.inpaint_coords is None:
-        raise SystemExit("--mask_info selects residues of KNOWN 6D maps: give their source with --inpaint_coords <file.pt|synthetic>")
+    if args.pdb is not None and args.inpaint_coords is not None:
+        raise SystemExit("--pdb and --inpaint_coords both name a source of the known 6D maps: give one")
+    if args.sse is not None and args.pdb is None:
+        raise SystemExit("--sse annotates the chain read with --pdb")
+    if args.mask_info is not None and args.inpaint_coords is None and args.pdb is None:
+        raise SystemExit("--mask_info selects residues of KNOWN 6D maps: give their source with --pdb <file> or --inpaint_coords <file.pt|synthetic>")
     assert not (args.inpaint_coords is not None and args.select_length)
 
     from text2protein_amd import distributed as D
@@ -89,8 +97,9 @@ def main():
         import sys
         raise SystemExit(D.launch_local(args.gpus, [os.path.abspath(__file__), *sys.argv[1:]]))
     from text2protein_amd import sampling, sde_lib, synth
+    from text2protein_amd._lib import T2PError
     from text2protein_amd.checkpoint import restore_checkpoint
-    from text2protein_amd.conditions import get_condition_from_batch, get_mask_all_lengths
+    from text2protein_amd.conditions import get_condition_from_batch, get_conditions_from_pdb, get_mask_all_lengths
     from text2protein_amd.config import load_config
     from text2protein_amd.model import HipScoreModel
 
@@ -110,6 +119,19 @@ def main():
     workdir = Path(args.outdir) if args.outdir else Path("sampling", "coords_6d", Path(args.config).stem, run, args.tag)
     if rank == 0:
         workdir.mkdir(parents=True, exist_ok=True)
+
+    pdb_condition = None
+    if args.pdb is not None:
+        sse = args.sse
+        if sse is not None and os.path.exists(sse):
+            sse = "".join(open(sse).read().split())
+        try:
+            # sampling_6d.py:146-147; the chain is the same for every iteration, so it is featurised once (and before the model is
+            # built: a file that cannot be used is reported at once)
+            pdb_condition = get_conditions_from_pdb(args.pdb, config, chain=args.chain, mask_info=args.mask_info or "1:5,10:15",
+                                                    batch_size=args.batch_size, sse=sse)
+        except (OSError, ValueError, T2PError) as e:
+            raise SystemExit(f"--pdb: {e}")
 
     # Initialize model (get_model + restore_checkpoint + ema.copy_to, sampling_6d.py:64-73)
     score_model = HipScoreModel(config, dtype=args.dtype, device=device)
@@ -188,6 +210,8 @@ def main():
         if args.select_length:
             mask = get_mask_all_lengths(config, batch_size=B)[args.length_index - 1]
             condition = {"length": mask.to(device)}
+        elif pdb_condition is not None:
+            condition = pdb_condition
         elif known is not None:
             # sampling_6d.py:146-147 -> get_condition_from_batch (utils.py:84-106): every condition the model was trained with
             condition = to_device(get_condition_from_batch(config, known, mask_info=args.mask_info or "1:5,10:15"))

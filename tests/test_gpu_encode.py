@@ -1,0 +1,309 @@
+"""6D encode on the GPU (t2p_op_encode_6d, text2protein_amd/encode.py) against the reference's own featuriser run in float64
+(tests/golden/encode_6d.npz, written by tests/golden/make_golden_encode.py: dataset.py:396-450, :114-168, :200-239), then the layers on
+top of it: the condition builder from a PDB file, a training step on an encoded batch and the command line.
+
+Bound on the unmasked neighbour pairs (max abs difference, omega / theta circular) = 4 x ref_f32_gap: dist 3.9e-06, omega 5.8e-05,
+theta 5.5e-05, phi 2.7e-05.  The tests print the measured maxima.
+"""
+import ctypes as C
+import json
+import os
+import pickle
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+import yaml
+
+from helpers import GOLDEN, load_golden
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PDB = os.path.join(GOLDEN, "encode_chain.pdb")
+SSE8 = "caaaaacc"
+CASES = {"L64": (64, ("8", "19", "40", "64")), "L37": (37, ("8", "19", "40cut", "64cut"))}
+
+
+@pytest.fixture(scope="module")
+def gold():
+    g = load_golden("encode_6d")
+    g["meta"] = json.loads(str(g["meta"]))
+    return g
+
+
+def _inputs(gold, L, keys):
+    """The padded batch.  Padding rows hold NaN and missing atoms hold a large number: neither may reach the output."""
+    B = len(keys)
+    xyz = torch.full((B, L, 3, 3), float("nan"))
+    ok = torch.zeros(B, L, 3, dtype=torch.uint8)
+    nres = []
+    for b, k in enumerate(keys):
+        x, a = torch.from_numpy(gold[f"xyz_{k}"]).float(), torch.from_numpy(gold[f"atom_ok_{k}"])
+        n = x.shape[0]
+        xyz[b, :n], ok[b, :n] = torch.where(a[:, :, None] != 0, x, torch.full_like(x, 999.0)), a
+        nres.append(n)
+    return xyz.cuda(), torch.tensor(nres, dtype=torch.int32).cuda(), ok.cuda(), [gold["meta"]["chains"][k]["sse"] for k in keys]
+
+
+@pytest.fixture(scope="module")
+def encoded(gold):
+    """Every (case, channel count) encoded once and shared, with the reference padded the same way (PaddingCollate: zeros)."""
+    from text2protein_amd.encode import encode_6d_batch
+    out = {}
+    for name, (L, keys) in CASES.items():
+        xyz, nres, ok, sse = _inputs(gold, L, keys)
+        ref = np.zeros((len(keys), 8, L, L))
+        for b, k in enumerate(keys):
+            n = gold[f"xyz_{k}"].shape[0]
+            ref[b, :, :n, :n] = gold[f"coords_6d_{k}"]
+        for ch in (5, 8):
+            got = encode_6d_batch(xyz, nres, atom_ok=ok, sse=sse if ch == 8 else None, num_channels=ch)
+            torch.cuda.synchronize()
+            out[name, ch] = (got, ref if ch == 8 else ref[:, [0, 1, 2, 3, 7]], keys)
+    return out
+
+
+@pytest.mark.parametrize("channels", [5, 8])
+@pytest.mark.parametrize("case", list(CASES))
+def test_encode_matches_the_reference(gold, encoded, case, channels):
+    got, ref, keys = encoded[case, channels]
+    x, mp = got["coords_6d"].cpu().numpy(), got["mask_pair"].cpu().numpy()
+    L = CASES[case][0]
+    assert x.shape == ref.shape == (4, channels, L, L) and x.dtype == np.float32 and got["mask_pair"].dtype == torch.bool
+    assert got["lengths"].tolist() == [gold[f"xyz_{k}"].shape[0] for k in keys]
+    assert np.isfinite(x).all()
+    m = ref[:, -1] != 0
+    assert np.array_equal(mp, m)                                        # mask_pair, bit-exact (zero outside nres)
+    assert np.array_equal(x[:, -1], ref[:, -1])                         # the padding channel
+    assert (x[~np.broadcast_to(m[:, None], x.shape)] == 0).all()        # every masked pixel and everything outside nres: exact 0
+    far = m & (ref[:, 0] == 1.0)                                        # far pairs and the diagonal: the constants
+    for c, v in enumerate((1.0, 0.0, 0.0, -1.0)):
+        assert (x[:, c][far] == v).all(), c
+    if channels == 8:
+        assert np.array_equal(x[:, 4:7], ref[:, 4:7])                   # helix, beta, adjacency: bit-exact
+        assert got["ss_indices"] == [gold["meta"]["chains"][k]["ss_indices"] for k in keys]
+        if case == "L64":
+            assert 0 < ref[:, 6].sum() < ref[:, 5].sum() and (ref[:, 4].sum(axis=(1, 2)) > 0).all()
+    else:
+        assert got["ss_indices"] == [""] * 4
+    near = m & ~far                                                     # together with `far` and ~m: every pixel
+    assert near.sum() > 1500 if case == "L64" else near.sum() > 1000
+    gap = gold["ref_f32_gap"]
+    worst = []
+    for c in range(4):
+        d = np.abs(x[:, c].astype(np.float64) - ref[:, c])
+        if c in (1, 2):
+            d = np.minimum(d, 2.0 - d)
+        worst.append(float(d[near].max()))
+    print(f"encode_6d {case} C={channels}: max abs difference (dist, omega, theta, phi) = " + ", ".join(f"{w:.2e}" for w in worst)
+          + "; bounds " + ", ".join(f"{4 * v:.2e}" for v in gap))
+    for c in range(4):
+        assert worst[c] <= 4.0 * gap[c], (c, worst[c], 4.0 * gap[c])
+
+
+def test_eight_channels_without_blocks_are_zero_and_shapes_agree(gold, encoded):
+    """C = 8 with no letters: channels 4:7 are zero and everything else equals the 5-channel result bit for bit."""
+    from text2protein_amd.encode import encode_6d_batch
+    xyz, nres, ok, _ = _inputs(gold, 64, CASES["L64"][1])
+    got = encode_6d_batch(xyz, nres, atom_ok=ok, num_channels=8)
+    five = encoded["L64", 5][0]
+    assert (got["coords_6d"][:, 4:7] == 0).all()
+    assert torch.equal(got["coords_6d"][:, [0, 1, 2, 3, 7]], five["coords_6d"]) and torch.equal(got["mask_pair"], five["mask_pair"])
+    # atom_ok = None means every atom present: the full-backbone samples come out the same
+    full = encode_6d_batch(torch.nan_to_num(xyz[[0, 3]], nan=0.0), nres[[0, 3]], num_channels=5)
+    assert torch.equal(full["coords_6d"], five["coords_6d"][[0, 3]])
+
+
+def test_output_is_finite_when_residues_share_coordinates():
+    """Two residues without any atom sit at the origin together (distance 0, every angle degenerate), next to duplicated residues
+    that ARE present (unmasked zero-length Cb-Cb vector): no NaN / Inf anywhere, the degenerate angles are the reference's 0."""
+    from text2protein_amd.encode import encode_6d_batch
+    g = torch.Generator().manual_seed(5)
+    xyz = torch.randn(2, 12, 3, 3, generator=g) * 0.8      # everything well inside the 20 A cut-off
+    ok = torch.ones(2, 12, 3, dtype=torch.uint8)
+    ok[0, 3], ok[0, 7] = 0, 0                       # sample 0: residues 3 and 7 missing altogether
+    xyz[1, 5] = xyz[1, 2]                           # sample 1: residues 2 and 5 coincide, all atoms present
+    xyz[1, 9] = 0                                   # and one present residue whose three atoms coincide (Cb = Ca)
+    for ch, sse in ((5, None), (8, ["caaaaccbbbbc", "bbbbbccaaaac"])):
+        out = encode_6d_batch(xyz.cuda(), torch.tensor([12, 12]), atom_ok=ok.cuda(), sse=sse, num_channels=ch)
+        x = out["coords_6d"].cpu()
+        assert torch.isfinite(x).all()
+        assert not out["mask_pair"][0, 3].any() and not out["mask_pair"][0, :, 7].any() and out["mask_pair"][1].all()
+        assert x[1, :4, 2, 5].tolist() == [-1.0, 0.0, 0.0, 0.0] and x[1, :4, 5, 2].tolist() == [-1.0, 0.0, 0.0, 0.0]
+        assert float(x[1, 3, 9, 0]) == 0.0 and float(x[1, 1, 9, 0]) == 0.0
+
+
+def test_round_trip_through_decode(gold, encoded):
+    """decode_6d(encode) of the full-backbone samples: L == nres and dist_abs is the Cb distance clipped at 20 A."""
+    from text2protein_amd.decode import decode_6d
+    got, ref, keys = encoded["L64", 5]
+    dec = decode_6d(got["coords_6d"][[0, 2, 3]])
+    tol = 4.0 * gold["ref_f32_gap"][0] * 10.0                         # dist_abs = (dist + 1) * 10
+    for d, b in zip(dec, (0, 2, 3)):
+        xyz = gold[f"xyz_{keys[b]}"]
+        n = xyz.shape[0]
+        assert d["L"] == n
+        bv, cv = xyz[:, 1] - xyz[:, 0], xyz[:, 2] - xyz[:, 1]
+        cb = -0.58273431 * np.cross(bv, cv) + 0.56802827 * bv - 0.54067466 * cv + xyz[:, 1]
+        want = np.minimum(np.linalg.norm(cb[:, None] - cb[None, :], axis=-1), 20.0)
+        np.fill_diagonal(want, 20.0)
+        err = float(np.abs(d["dist_abs"].astype(np.float64) - want).max())
+        print(f"round trip, {n} residues: max |dist_abs - Cb distance| = {err:.2e} A (bound {tol:.2e})")
+        assert err <= tol
+        assert np.array_equal(d["omega"], got["coords_6d"][b, 1, :n, :n].cpu().numpy())
+
+
+def test_refusals_leave_the_outputs_untouched():
+    from text2protein_amd import _lib
+    lib = _lib.load()
+    B, L = 2, 16
+    xyz = torch.randn(B, L, 3, 3, generator=torch.Generator().manual_seed(1)).cuda()
+
+    def call(nres, channels, blocks, alloc=8):
+        n = torch.tensor(nres, dtype=torch.int32).cuda()
+        coords = torch.full((B, alloc, L, L), 7.0).cuda()
+        mask = torch.full((B, L, L), 9, dtype=torch.uint8).cuda()
+        arr = np.ascontiguousarray(np.asarray(blocks, dtype=np.int32).reshape(-1, 4))
+        rc = lib.t2p_op_encode_6d(_lib.ptr(xyz), _lib.ptr(n), None, B, channels, L, C.c_void_p(arr.ctypes.data) if len(arr) else None, len(arr),
+                                  _lib.ptr(coords), _lib.ptr(mask), _lib.stream_ptr())
+        torch.cuda.synchronize()
+        return rc, lib.t2p_last_error().decode(), bool((coords == 7.0).all()) and bool((mask == 9).all())
+
+    rc, _, untouched = call([16, 10], 8, [(0, 2, 8, 0), (1, 5, 9, 1), (1, 3, 3, 1)])        # the valid extremes run
+    assert rc == 0 and not untouched
+    for what, args in {
+        "nres = 0": ([0, 10], 5, []),
+        "nres > L": ([16, 17], 5, []),
+        "block past nres": ([16, 10], 8, [(1, 5, 10, 0)]),
+        "negative start": ([16, 10], 8, [(0, -1, 4, 0)]),
+        "start > last": ([16, 10], 8, [(0, 6, 5, 1)]),
+        "sample outside the batch": ([16, 10], 8, [(2, 1, 5, 0)]),
+        "negative sample": ([16, 10], 8, [(-1, 1, 5, 0)]),
+        "unknown kind": ([16, 10], 8, [(0, 1, 5, 2)]),
+        "blocks with 5 channels": ([16, 10], 5, [(0, 1, 5, 0)]),
+        "6 channels": ([16, 10], 6, []),
+        "7 channels": ([16, 10], 7, []),
+    }.items():
+        rc, msg, untouched = call(*args)
+        assert rc != 0 and "encode_6d" in msg, what
+        assert untouched, what
+
+
+def _tiny_inpaint_cfg(tmp_path):
+    from text2protein_amd.config import tiny_config
+    cfg = tiny_config(**{"model.num_scales": 4, "model.condition": ["length", "inpainting"], "data.num_channels": 8})
+    cfg_path = tmp_path / "tiny_inp.yml"
+    with open(cfg_path, "w") as f:
+        yaml.safe_dump(yaml.safe_load(json.dumps(cfg)), f)
+    return cfg, cfg_path
+
+
+def _encode_chain(L, channels):
+    from text2protein_amd.encode import encode_6d_batch, read_backbone
+    xyz, ok, n = read_backbone(PDB)
+    x, a = torch.zeros(1, L, 3, 3), torch.zeros(1, L, 3, dtype=torch.uint8)
+    x[0, :n], a[0, :n] = torch.from_numpy(xyz), torch.from_numpy(ok)
+    return encode_6d_batch(x.cuda(), torch.tensor([n]), atom_ok=a.cuda(), sse=[SSE8] if channels == 8 else None, num_channels=channels), n
+
+
+def test_conditions_from_pdb(gold):
+    """get_conditions_from_pdb (utils.py:122-137) on the fixture file at batch 2: the three conditions with the shapes get_pc_sampler
+    takes, equal to the reference's featurisation of the same chain."""
+    from text2protein_amd.conditions import get_conditions_from_pdb
+    from text2protein_amd.config import tiny_config
+    cfg = tiny_config(**{"model.condition": ["length", "ss", "inpainting"], "data.num_channels": 8})
+    cfg.device = "cuda:0"
+    L = cfg.data.max_res_num
+    cond = get_conditions_from_pdb(PDB, cfg, chain="A", mask_info="1:5,10:15", batch_size=2, sse=SSE8)
+    assert set(cond) == {"length", "ss", "inpainting"} and set(cond["inpainting"]) == {"coords_6d", "mask_inpaint"}
+    coords, mi = cond["inpainting"]["coords_6d"], cond["inpainting"]["mask_inpaint"]
+    assert tuple(cond["length"].shape) == (2, L, L) and cond["length"].dtype == torch.bool
+    assert tuple(cond["ss"].shape) == (2, 3, L, L) and tuple(coords.shape) == (2, 8, L, L) and coords.dtype == torch.float32
+    assert tuple(mi.shape) == (2, L, L) and mi.dtype == torch.bool
+    assert all(t.device.type == "cuda" for t in (cond["length"], cond["ss"], coords, mi))
+    inside = torch.arange(L) < 8
+    assert torch.equal(cond["length"].cpu(), (inside[:, None] & inside[None, :]).expand(2, L, L))
+    sel = torch.zeros(L, dtype=torch.bool)
+    sel[[1, 2, 3, 4, 5, 10, 11, 12, 13, 14, 15]] = True
+    assert torch.equal(mi.cpu(), (sel[:, None] | sel[None, :]).expand(2, L, L))
+    assert torch.equal(coords[0], coords[1]) and torch.equal(cond["ss"], coords[:, 4:7])
+    ref = gold["coords_6d_8"]
+    x = coords[0].cpu().numpy()
+    assert (x[:, 8:] == 0).all() and (x[:, :, 8:] == 0).all()
+    assert np.array_equal(x[4:, :8, :8], ref[4:]) and x[4, 1:5, 1:5].all() and x[4].sum() == 16
+    assert np.abs(x[0, :8, :8] - ref[0]).max() <= 4 * gold["ref_f32_gap"][0]
+    five = tiny_config(**{"model.condition": ["length"]})
+    five.device = "cuda:0"
+    assert set(get_conditions_from_pdb(PDB, five, batch_size=3)) == {"length"}
+
+
+def test_training_step_on_an_encoded_batch():
+    """One step of get_step_fn on a batch that holds nothing but encode_6d_batch's output (with its ss_indices) and a context."""
+    from text2protein_amd import losses, sde_lib, synth
+    from text2protein_amd.config import tiny_config
+    from text2protein_amd.encode import encode_6d_batch
+    cfg = tiny_config(**{"data.num_channels": 8, "model.condition": ["length", "ss"], "model.dropout": 0.0, "model.num_scales": 50})
+    cfg.device = "cuda:0"
+    L = cfg.data.max_res_num
+    g = torch.Generator().manual_seed(3)
+    steps = torch.nn.functional.normalize(torch.randn(2, L, 3, generator=g), dim=-1) * 3.8
+    ca = torch.cumsum(steps, dim=1)
+    xyz = torch.stack([ca + 1.46 * torch.nn.functional.normalize(torch.randn(2, L, 3, generator=g), dim=-1), ca,
+                       ca + 1.52 * torch.nn.functional.normalize(torch.randn(2, L, 3, generator=g), dim=-1)], dim=2)
+    batch = encode_6d_batch(xyz.cuda(), torch.tensor([16, 11]), sse=["caaaaaccbbbbccbb", "bbbbbcaaaac"], num_channels=8)
+    assert batch["ss_indices"] == ["1:5,8:11", "6:9,0:4"]
+    batch["context"] = synth.synth_context(2, 3, cfg.model.context_dim, 1)
+    model = losses.HipTrainModel(cfg, device="cuda:0", seed=11)
+    model.load_state_dict(synth.synth_state_dict(cfg, 3))
+    sde = sde_lib.VESDE(sigma_min=cfg.model.sigma_min, sigma_max=cfg.model.sigma_max, N=cfg.model.num_scales)
+    step_fn = losses.get_step_fn(sde, train=True, optimize_fn=losses.optimization_manager(cfg))
+    state = dict(model=model, optimizer=losses.get_optimizer(cfg, model.parameters()),
+                 ema=losses.ExponentialMovingAverage(model.parameters(), decay=cfg.model.ema_rate), step=100)
+    loss = step_fn(state, batch, condition=cfg.model.condition)
+    print("training step on an encoded batch: loss", loss)
+    assert np.isfinite(loss) and loss > 0 and state["step"] == 101
+
+
+@pytest.mark.parametrize("channels", [8, 5])
+def test_cli_pdb_equals_inpaint_coords(tmp_path, channels):
+    """sampling_6d.py --pdb against --inpaint_coords with the maps encode_6d_batch gives for the same chain, same seed: the written
+    samples are bit-identical, and the known region is the encoded map."""
+    cfg, cfg_path = _tiny_inpaint_cfg(tmp_path)
+    if channels == 5:
+        cfg.data.num_channels = 5
+        with open(cfg_path, "w") as f:
+            yaml.safe_dump(yaml.safe_load(json.dumps(cfg)), f)
+    L = cfg.data.max_res_num
+    enc, n = _encode_chain(L, channels)
+    coords = enc["coords_6d"].cpu()
+    torch.save({"coords_6d": coords, "lengths": [n]}, tmp_path / "known.pt")
+    base = [sys.executable, os.path.join(ROOT, "sampling_6d.py"), str(cfg_path), "synthetic", "--batch_size", "2", "--dtype", "f32",
+            "--context_tokens", "4", "--seed", "5", "--mask_info", "1:5,10:15"]
+    sse = ["--sse", SSE8] if channels == 8 else []
+    runs = {"pdb": ["--pdb", PDB, "--chain", "A"] + sse, "pt": ["--inpaint_coords", str(tmp_path / "known.pt")]}
+    got = {}
+    for name, extra in runs.items():
+        r = subprocess.run(base + extra + ["--outdir", str(tmp_path / name)], capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stdout + r.stderr
+        got[name] = []
+        for i in range(2):
+            with open(tmp_path / name / f"sampled_{i}.pkl", "rb") as f:
+                got[name].append(pickle.load(f)[0])
+    for a, b in zip(got["pdb"], got["pt"]):
+        assert torch.equal(a, b)
+    t = got["pdb"][1]
+    sel = torch.zeros(L, dtype=torch.bool)
+    sel[[1, 2, 3, 4, 5, 10, 11, 12, 13, 14, 15]] = True
+    inside = torch.arange(L) < n
+    free = (inside[:, None] & inside[None, :]) & (sel[:, None] | sel[None, :])
+    assert torch.isfinite(t).all() and torch.equal(t[:-1][:, ~free], coords[0, :-1][:, ~free]) and torch.equal(t[-1], coords[0, -1])
+    assert float((t[:4][:, free] - coords[0, :4][:, free]).abs().max()) > 1e-3
+    if channels == 8:
+        # an 8-channel model without --sse, and a chain the configuration has no room for, are refused with a message
+        r = subprocess.run(base + ["--pdb", PDB, "--outdir", str(tmp_path / "x")], capture_output=True, text=True, timeout=120, cwd=str(tmp_path))
+        assert r.returncode != 0 and "--sse" in r.stderr + r.stdout
+        r = subprocess.run(base + ["--pdb", PDB, "--sse", SSE8, "--max_res_num", "4", "--outdir", str(tmp_path / "x")], capture_output=True,
+                           text=True, timeout=120, cwd=str(tmp_path))
+        assert r.returncode != 0 and "residues" in r.stderr + r.stdout

@@ -4,8 +4,12 @@
                                               ``length_index - 1`` (sampling_6d.py:145)
   selected_mask_batch      utils.py:62-81     "1:5,10:15" -> (B, L, L) bool, inclusive 0-based ranges
   get_condition_from_batch utils.py:84-106    {"length" | "ss" | "inpainting"} from a batch of 6D maps
-The PDB-driven builders (utils.py:108-137) need biotite and call ``ProteinDataset`` with a
-signature it does not have; they are out of scope.
+  get_conditions_from_pdb  utils.py:122-137   the same from one chain of a PDB file, featurised on the device
+                                              (text2protein_amd/encode.py: dataset.py:114-168, :200-239, :396-450)
+The reference's builder goes through biotite and calls ``ProteinDataset`` with a signature it does not have (SURVEY.md section 2,
+row 10); here the chain is read by ``encode.read_backbone`` and encoded by ``t2p_op_encode_6d``.  The secondary-structure letters
+of the 8-channel layout (biotite's P-SEA in the reference) are an input.  ``get_conditions_random`` (utils.py:108-120) draws from a
+dataset directory and stays out of scope.
 """
 from __future__ import annotations
 
@@ -77,6 +81,34 @@ def get_condition_from_batch(config, batch, mask_info=None):
         else:
             raise ValueError(f"unknown condition {name!r}")
     return out
+
+
+def get_conditions_from_pdb(pdb, config, chain="A", mask_info=None, batch_size=8, sse=None):
+    """utils.py:122-137: chain ``chain`` of the file ``pdb``, featurised (dataset.py:311-325) and padded to ``max_res_num``
+    (PaddingCollate), repeated over the batch, then ``get_condition_from_batch``; every tensor on ``config.device``, which must be a
+    GPU.  ``sse``: one of a / b / c per residue (P-SEA letters), required by the 8-channel layout.  A chain outside
+    ``[min_res_num, max_res_num]`` is refused (the reference's dataset drops it, dataset.py:282-284)."""
+    from .encode import encode_6d_batch, read_backbone
+    xyz, atom_ok, nres = read_backbone(pdb, chain)
+    lo, hi, C = config.data.min_res_num, config.data.max_res_num, config.data.num_channels
+    if nres < lo or nres > hi:
+        raise ValueError(f"chain {chain!r} of {pdb} has {nres} residues, outside [{lo}, {hi}] (data.min_res_num, data.max_res_num)")
+    if C == 8:
+        if sse is None:
+            raise ValueError("an 8-channel model needs the chain's secondary-structure letters (a / b / c per residue): pass --sse")
+        if len(sse) != nres:
+            raise ValueError(f"--sse holds {len(sse)} letters, chain {chain!r} of {pdb} has {nres} residues")
+    elif sse is not None:
+        raise ValueError("--sse applies to 8-channel models only (data.num_channels)")
+    device = torch.device(config.device if str(config.device) != "cuda" else "cuda:0")
+    x = torch.zeros(1, hi, 3, 3)
+    ok = torch.zeros(1, hi, 3, dtype=torch.uint8)
+    x[0, :nres], ok[0, :nres] = torch.from_numpy(xyz), torch.from_numpy(atom_ok)
+    one = encode_6d_batch(x.to(device), torch.tensor([nres]), atom_ok=ok.to(device), sse=None if sse is None else [sse], num_channels=C)
+    batch = {"coords_6d": one["coords_6d"].repeat(batch_size, 1, 1, 1), "mask_pair": one["mask_pair"].repeat(batch_size, 1, 1),
+             "lengths": one["lengths"].repeat(batch_size), "ss_indices": one["ss_indices"] * batch_size}
+    cond = get_condition_from_batch(config, batch, mask_info=mask_info)
+    return {k: {kk: vv.to(device) for kk, vv in v.items()} if isinstance(v, dict) else v.to(device) for k, v in cond.items()}
 
 
 def synthetic_condition(config, batch, kind, device, length=100, mask_info="1:5,10:15", seed=0):

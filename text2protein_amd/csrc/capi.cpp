@@ -560,6 +560,50 @@ int t2p_op_decode_6d(const float* x, int batch, int channels, int L, float* clip
   API_END
 }
 
+// everything the kernels index with is checked here, on the host, before the first launch: nres (read back from the device) and the
+// block list; the ordered block pairs of each sample (one workgroup each) are enumerated here as well
+int t2p_op_encode_6d(const float* xyz, const int32_t* nres, const uint8_t* atom_ok, int batch, int channels, int L,
+                     const int32_t* host_blocks, int n_blocks, float* coords_6d, uint8_t* mask_pair, void* stream) {
+  API_BEGIN
+  T2P_REQUIRE(xyz && nres && coords_6d && mask_pair && batch > 0 && L > 0, "encode_6d arguments");
+  T2P_REQUIRE(channels == 5 || channels == 8, "encode_6d: the channel count must be 5 or 8, not " + std::to_string(channels));
+  T2P_REQUIRE(n_blocks >= 0 && (n_blocks == 0 || host_blocks), "encode_6d: block list arguments");
+  T2P_REQUIRE(n_blocks == 0 || channels == 8, "encode_6d: secondary-structure blocks need the 8-channel layout");
+  T2P_REQUIRE((long)L * L < (1L << 30) && batch <= 65535, "encode_6d: map or batch too large");
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<int32_t> n((size_t)batch);
+  T2P_HIP_CHECK(hipMemcpyAsync(n.data(), nres, (size_t)batch * 4, hipMemcpyDeviceToHost, s));
+  T2P_HIP_CHECK(hipStreamSynchronize(s));
+  for (int b = 0; b < batch; ++b)
+    T2P_REQUIRE(n[b] >= 1 && n[b] <= L, "encode_6d: nres[" + std::to_string(b) + "] = " + std::to_string(n[b]) + " is outside [1, " + std::to_string(L) + "]");
+  std::vector<std::vector<int32_t>> of_sample((size_t)batch);
+  for (int k = 0; k < n_blocks; ++k) {
+    const int32_t* q = host_blocks + 4 * (size_t)k;
+    const std::string name = "encode_6d: block " + std::to_string(k);
+    T2P_REQUIRE(q[0] >= 0 && q[0] < batch, name + " names a sample outside the batch");
+    T2P_REQUIRE(q[1] <= q[2], name + " starts after its last residue");
+    T2P_REQUIRE(q[1] >= 0 && q[2] < n[q[0]], name + " lies outside the " + std::to_string(n[q[0]]) + " residues of its sample");
+    T2P_REQUIRE(q[3] == 0 || q[3] == 1, name + " is neither a helix (0) nor a strand (1)");
+    of_sample[q[0]].push_back(k);
+  }
+  if (n_blocks == 0) return launch_encode6d(xyz, nres, atom_ok, batch, channels, L, nullptr, nullptr, 0, coords_6d, mask_pair, s);
+  std::vector<int32_t> up(host_blocks, host_blocks + 4 * (size_t)n_blocks);      // [blocks | pairs], one upload
+  for (const auto& ks : of_sample)
+    for (int32_t k1 : ks)
+      for (int32_t k2 : ks) { up.push_back(k1); up.push_back(k2); }
+  const size_t npairs = (up.size() - 4 * (size_t)n_blocks) / 2;
+  T2P_REQUIRE(npairs < (1u << 30), "encode_6d: too many block pairs");
+  struct Scratch {          // the device copy of [blocks | pairs]: released on every way out, after the stream has drained
+    int32_t* p = nullptr; hipStream_t s;
+    ~Scratch() { if (p) { (void)hipStreamSynchronize(s); (void)hipFree(p); } }
+  } dev;
+  dev.s = s;
+  T2P_HIP_CHECK(hipMalloc(&dev.p, up.size() * 4));
+  T2P_HIP_CHECK(hipMemcpyAsync(dev.p, up.data(), up.size() * 4, hipMemcpyHostToDevice, s));
+  return launch_encode6d(xyz, nres, atom_ok, batch, channels, L, dev.p, dev.p + 4 * (size_t)n_blocks, (int)npairs, coords_6d, mask_pair, s);
+  API_END
+}
+
 int t2p_op_embedding_gather(const void* table, int table_dtype, const int32_t* ids, float* out, int64_t n_tokens, int dim, int vocab,
                             int32_t* bad_flag, void* stream) {
   API_BEGIN

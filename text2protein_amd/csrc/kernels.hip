@@ -1709,6 +1709,160 @@ int launch_decode6d(const float* x, int B, int C, int L, float* clipped, float* 
   return T2P_OK;
 }
 
+// ================================== before the sampler: 6D encode ===================================
+// dataset.py:396-450 (get_coords6d), :200-239 (masks, padding channel) and :114-168 (get_coarse_constraints) for a padded batch.
+// Every vector the angles are taken from is built from SHORT differences -- the virtual-Cb offset of a residue (about 1.5 A) and
+// Ca_j - Ca_i -- so fp32 rounding of coordinates far from the origin does not enter: Cb_j - Cb_i = (Ca_j - Ca_i) + (off_j - off_i).
+struct V3 { float x, y, z; };
+__device__ __forceinline__ V3 v3sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ V3 v3add(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ V3 v3neg(V3 a) { return {-a.x, -a.y, -a.z}; }
+__device__ __forceinline__ float v3dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ V3 v3cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ V3 v3axpy(float s, V3 a, V3 b) { return {b.x - s * a.x, b.y - s * a.y, b.z - s * a.z}; }   // b - s a
+
+// atom `a` (0 N, 1 Ca, 2 C) of residue r; a missing atom is (0, 0, 0) whatever the buffer holds (dataset.py:219)
+__device__ __forceinline__ V3 enc_atom(const float* xyz, const unsigned char* ok, long r, int a) {
+  if (ok && !ok[r * 3 + a]) return {0.f, 0.f, 0.f};
+  const float* p = xyz + (r * 3 + a) * 3;
+  return {p[0], p[1], p[2]};
+}
+// Ca, b = Ca - N and off = Cb - Ca of residue r (dataset.py:405-409)
+__device__ __forceinline__ void enc_residue(const float* xyz, const unsigned char* ok, long r, V3& ca, V3& bv, V3& off) {
+  const V3 n = enc_atom(xyz, ok, r, 0), c = enc_atom(xyz, ok, r, 2);
+  ca = enc_atom(xyz, ok, r, 1);
+  bv = v3sub(ca, n);
+  const V3 cv = v3sub(c, ca), av = v3cross(bv, cv);
+  off = {-0.58273431f * av.x + 0.56802827f * bv.x - 0.54067466f * cv.x, -0.58273431f * av.y + 0.56802827f * bv.y - 0.54067466f * cv.y,
+         -0.58273431f * av.z + 0.56802827f * bv.z - 0.54067466f * cv.z};
+}
+// residue r takes part iff r - 1, r and r + 1 (where they exist) hold all three atoms (dataset.py:209-218)
+__device__ __forceinline__ bool enc_valid(const unsigned char* ok, long base, int r, int n) {
+  if (!ok) return true;
+  const int lo = max(r - 1, 0), hi = min(r + 1, n - 1);
+  bool v = true;
+  for (int q = lo; q <= hi; ++q) v = v && ok[(base + q) * 3] && ok[(base + q) * 3 + 1] && ok[(base + q) * 3 + 2];
+  return v;
+}
+// get_dihedrals (dataset.py:364-380) with b0 = -(b - a), b1 = c - b, b2 = d - c given; |b1| = 0 is the reference's NaN -> nan_to_num -> 0.
+// A zero-length projected vector leaves x = y = 0 with signs that depend on the other vector (atan2(+-0, -0) is +-pi): the angle is
+// undefined there and 0 is written, whatever the signs of the zeros
+__device__ __forceinline__ float enc_dihedral(V3 b0, V3 b1, V3 b2) {
+  const float n1 = sqrtf(v3dot(b1, b1));
+  if (!(n1 > 0.f)) return 0.f;
+  const float inv = 1.f / n1;
+  b1 = {b1.x * inv, b1.y * inv, b1.z * inv};
+  const V3 v = v3axpy(v3dot(b0, b1), b1, b0), w = v3axpy(v3dot(b2, b1), b1, b2);
+  const float y = v3dot(v3cross(b1, v), w), x = v3dot(v, w);
+  return (x == 0.f && y == 0.f) ? 0.f : atan2f(y, x);
+}
+#define T2P_ENC_DMAX 20.f
+// one (sample, i, j) pixel per thread, consecutive threads along j: every channel row of the NCHW output is stored coalesced; every
+// element of coords_6d and mask_pair is written (padding and the 4:7 channels of the 8-channel layout as zeros)
+__global__ __launch_bounds__(256) void encode_6d_kernel(const float* __restrict__ xyz, const int* __restrict__ nres,
+                                                        const unsigned char* __restrict__ atom_ok, int C, int L, float* __restrict__ out,
+                                                        unsigned char* __restrict__ mask_pair) {
+  const int b = blockIdx.y;
+  const long HW = (long)L * L, p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= HW) return;
+  const int i = (int)(p / L), j = (int)(p - (long)i * L), n = nres[b];
+  const long base = (long)b * L;
+  const float PI_F = 3.14159274101257324f;
+  float g0 = 0.f, g1 = 0.f, g2 = 0.f, g3 = 0.f;
+  bool m = false;
+  if (i < n && j < n) m = enc_valid(atom_ok, base, i, n) && enc_valid(atom_ok, base, j, n);
+  if (m) {
+    g0 = 1.f; g3 = -1.f;                                  // far pairs and the diagonal: dist = dmax, the angles 0 (dataset.py:422-434)
+    if (i != j) {
+      V3 cai, bi, oi, caj, bj, oj;
+      enc_residue(xyz, atom_ok, base + i, cai, bi, oi);
+      enc_residue(xyz, atom_ok, base + j, caj, bj, oj);
+      const V3 d = v3add(v3sub(caj, cai), v3sub(oj, oi));  // Cb_j - Cb_i
+      const float dist = sqrtf(v3dot(d, d));
+      if (dist <= T2P_ENC_DMAX) {
+        g0 = dist / T2P_ENC_DMAX * 2.f - 1.f;
+        g1 = enc_dihedral(v3neg(oi), d, v3neg(oj)) / PI_F;          // Ca_i, Cb_i, Cb_j, Ca_j
+        g2 = enc_dihedral(v3neg(bi), oi, d) / PI_F;                  // N_i, Ca_i, Cb_i, Cb_j
+        const V3 v = v3neg(oi), cr = v3cross(v, d);                  // angle Ca_i, Cb_i, Cb_j
+        const bool degenerate = !(v3dot(v, v) > 0.f) || !(dist > 0.f);     // get_angles' 0 / 0 -> nan_to_num -> 0
+        g3 = degenerate ? 0.f : atan2f(sqrtf(v3dot(cr, cr)), v3dot(v, d)) / PI_F * 2.f - 1.f;
+        g0 = g0 == g0 ? g0 : 0.f; g1 = g1 == g1 ? g1 : 0.f; g2 = g2 == g2 ? g2 : 0.f; g3 = g3 == g3 ? g3 : 0.f;   // never a NaN out
+      }
+    }
+  }
+  float* o = out + (long)b * C * HW + p;
+  o[0] = g0; o[HW] = g1; o[2 * HW] = g2; o[3 * HW] = g3;
+  for (int c = 4; c < C - 1; ++c) o[c * HW] = 0.f;
+  o[(C - 1) * HW] = m ? 1.f : 0.f;
+  mask_pair[(long)b * HW + p] = m ? 1 : 0;
+}
+
+// channels 4:7 (helix, beta, block adjacency; dataset.py:141-163), one workgroup per ordered pair of blocks of one sample:
+// blocks = [n][4] (sample, start, last, kind: 0 helix, 1 beta), pairs = [npairs][2] block indices.  The rectangle is the reference's
+// half-open [start:last] x [start:last]; the adjacency test takes the minimum over it of the normalised Cb distance BEFORE the pair
+// mask (dataset.py:229 runs before :238), missing atoms at the origin, so it is recomputed here and not read back from channel 0.
+__global__ __launch_bounds__(256) void ss_constraints_kernel(const float* __restrict__ xyz, const unsigned char* __restrict__ atom_ok,
+                                                             const int* __restrict__ blocks, const int* __restrict__ pairs, int C, int L,
+                                                             const unsigned char* __restrict__ mask_pair, float* __restrict__ out) {
+  __shared__ float wave_min[4];
+  const int k1 = pairs[2 * blockIdx.x], k2 = pairs[2 * blockIdx.x + 1], t = threadIdx.x;
+  const int b = blocks[4 * k1], s1 = blocks[4 * k1 + 1], l1 = blocks[4 * k1 + 2], kind1 = blocks[4 * k1 + 3];
+  const int s2 = blocks[4 * k2 + 1], l2 = blocks[4 * k2 + 2], kind2 = blocks[4 * k2 + 3];
+  const int h = l1 - s1, w = l2 - s2;
+  if (h <= 0 || w <= 0) return;                           // an empty rectangle sets nothing (uniform over the workgroup)
+  const long base = (long)b * L, HW = (long)L * L;
+  bool adjacent = false;
+  if (k1 != k2) {
+    float mn = 3.0e38f;
+    for (int e = t; e < h * w; e += 256) {
+      const int i = s1 + e / w, j = s2 + e % w;
+      float dn = 1.f;                                     // dist = dmax on the diagonal and beyond the cut-off
+      if (i != j) {
+        V3 cai, bi, oi, caj, bj, oj;
+        enc_residue(xyz, atom_ok, base + i, cai, bi, oi);
+        enc_residue(xyz, atom_ok, base + j, caj, bj, oj);
+        const V3 d = v3add(v3sub(caj, cai), v3sub(oj, oi));
+        const float dist = sqrtf(v3dot(d, d));
+        if (dist <= T2P_ENC_DMAX) dn = dist / T2P_ENC_DMAX * 2.f - 1.f;
+      }
+      mn = fminf(mn, dn);
+    }
+    for (int off = 32; off > 0; off >>= 1) mn = fminf(mn, __shfl_xor(mn, off, 64));
+    if ((t & 63) == 0) wave_min[t >> 6] = mn;
+    __syncthreads();
+    mn = fminf(fminf(wave_min[0], wave_min[1]), fminf(wave_min[2], wave_min[3]));
+    adjacent = mn < 5.f / T2P_ENC_DMAX * 2.f - 1.f;       // dist_threshold = 5 (dataset.py:229, :119, :162)
+  }
+  const bool helix = k1 == k2 && kind1 == 0, beta = kind1 == 1 && kind2 == 1;
+  if (!helix && !beta && !adjacent) return;
+  float* o = out + (long)b * C * HW;
+  const unsigned char* mp = mask_pair + (long)b * HW;
+  for (int e = t; e < h * w; e += 256) {
+    const long p = (long)(s1 + e / w) * L + (s2 + e % w);
+    if (!mp[p]) continue;                                 // the channels are multiplied by mask_pair like the rest (dataset.py:238)
+    if (helix) o[4 * HW + p] = 1.f;
+    if (beta) o[5 * HW + p] = 1.f;
+    if (adjacent) o[6 * HW + p] = 1.f;
+  }
+}
+// the arguments are checked by the caller (t2p_op_encode_6d reads nres and the blocks on the host before anything is launched);
+// blocks / pairs are device copies, npairs = 0 leaves the 4:7 channels zero
+int launch_encode6d(const float* xyz, const int* nres, const unsigned char* atom_ok, int B, int C, int L, const int* blocks, const int* pairs,
+                    int npairs, float* coords_6d, unsigned char* mask_pair, hipStream_t s) {
+  T2P_REQUIRE(xyz && nres && coords_6d && mask_pair && B > 0 && L > 0, "encode_6d arguments");
+  T2P_REQUIRE(C == 5 || C == 8, "encode_6d: the channel count must be 5 or 8");
+  T2P_REQUIRE((long)L * L < (1L << 30) && B <= 65535, "encode_6d: map or batch too large");
+  T2P_REQUIRE(npairs == 0 || (C == 8 && blocks && pairs), "encode_6d: secondary-structure blocks need the 8-channel layout");
+  const long HW = (long)L * L;
+  hipLaunchKernelGGL(encode_6d_kernel, dim3((unsigned)((HW + 255) / 256), B), dim3(256), 0, s, xyz, nres, atom_ok, C, L, coords_6d, mask_pair);
+  T2P_HIP_CHECK(hipGetLastError());
+  if (npairs > 0) {
+    hipLaunchKernelGGL(ss_constraints_kernel, dim3(npairs), dim3(256), 0, s, xyz, atom_ok, blocks, pairs, C, L, mask_pair, coords_6d);
+    T2P_HIP_CHECK(hipGetLastError());
+  }
+  return T2P_OK;
+}
+
 // ================================== before the sampler: text context ================================
 // context[b, t, :] = table[ids[b, t], :]  (llm.model.embed_tokens(tokens), reference sampling_6d.py:137;
 // modeling_llama nn.Embedding).  One wavefront per token, 16-byte lanes; fp32 output (the sampler's

@@ -233,6 +233,11 @@ int launch_gather_label(const int* labels, const int* step_counter, const float*
                         hipStream_t s, const int* label_table = nullptr);
 int launch_apply_mask(float* x, const unsigned char* mask, const float* x_initial, long n, hipStream_t s);
 int launch_decode6d(const float* x, int B, int C, int L, float* clipped, float* absval, int* lengths, hipStream_t s);
+// 6D encode of a padded batch of backbones (dataset.py:396-450, :200-239, :114-168): xyz [B][L][3][3] fp32 (N, Ca, C), nres [B],
+// atom_ok [B][L][3] or null -> coords_6d [B][C][L][L] (C = 5 or 8), mask_pair [B][L][L]; blocks [n][4] / pairs [npairs][2]: device
+// copies of the secondary-structure blocks and of the ordered block pairs of one sample each (ss_constraints_kernel)
+int launch_encode6d(const float* xyz, const int* nres, const unsigned char* atom_ok, int B, int C, int L, const int* blocks, const int* pairs,
+                    int npairs, float* coords_6d, unsigned char* mask_pair, hipStream_t s);
 int launch_embedding_gather(const void* table, int dtype, const int* ids, float* out, long ntok, int dim, int vocab, int* bad, hipStream_t s);
 
 }  // namespace t2p
