@@ -268,6 +268,23 @@ int t2p_op_groupnorm_backward(const float* x, const float* dy, const float* gamm
                               int groups, float eps, float* dx, float* dgamma, float* dbeta, void* stream);
 int t2p_op_layernorm_backward(const float* x, const float* dy, const float* gamma, int64_t rows, int C, float eps, float* dx, float* dgamma,
                               float* dbeta, void* stream);
+/* the same with the form of the parameter-gradient reduction chosen by the caller: fixed_order = 0 float atomics (the f32 step, what the
+ * two entries above run), 1 a fixed summation order through a workspace the call allocates and frees (what the 16-bit step runs:
+ * bitwise reproducible) */
+int t2p_op_groupnorm_backward_form(const float* x, const float* dy, const float* gamma, const float* beta, int silu, int batch, int HW,
+                                   int C, int groups, float eps, float* dx, float* dgamma, float* dbeta, int fixed_order, void* stream);
+int t2p_op_layernorm_backward_form(const float* x, const float* dy, const float* gamma, int64_t rows, int C, float eps, float* dx,
+                                   float* dgamma, float* dbeta, int fixed_order, void* stream);
+/* column sums (bias gradients; nz = batch: the per-sample time-embedding bias): out[z][n] (+)= sum_r dy[(z rows_per_z + r) ld + n],
+ * n < N, out rows of ld_out floats (columns N.. untouched); accumulate = 0 overwrites; fixed_order as above */
+int t2p_op_colsum(const float* dy, int nz, int64_t rows_per_z, int N, int64_t ld, float* out, int64_t ld_out, int accumulate,
+                  int fixed_order, void* stream);
+/* *result_host = sum g[i]^2 in double (the gradient norm of clip_grad_norm_ and of the overflow guard); fixed_order as above */
+int t2p_op_sumsq(const float* g, int64_t n, int fixed_order, double* result_host, void* stream);
+/* the backward seed's scale of the 16-bit VP / sub-VP step: s2_host[0] = S = 2^e, e = the largest integer with 2^e max|x| <= target,
+ * clamped to [-60, 60] (so S and 1 / S are normal floats whatever x holds, a subnormal maximum included); S = 1 when x is all zero
+ * or holds an infinity or a NaN; s2_host[1] = 1 / S.  target > 0 */
+int t2p_op_seed_scale(const float* x, int64_t n, float target, float* s2_host, void* stream);
 int t2p_op_softmax_backward(const float* P, float* dP_inout, int64_t rows, int n, float scale, void* stream);
 int t2p_op_geglu_backward(const float* u, const float* dy, float* du, int64_t rows, int inner, void* stream);
 
@@ -439,7 +456,8 @@ int t2p_op_apply_mask(float* x, const uint8_t* mask, const float* x_initial, int
 int t2p_profile_begin(void);
 /* Plan switches for tests and A/B measurements: they select between kernel geometries / fusions that all
  * produce correct results (key 0 LDS-DMA GEMM on/off, 2 tile geometry, 3 split-K, 4..25 individual fusions and
- * kernel forms -- the full list with one line each: tools/README.md; text2protein_amd/csrc/capi.cpp).  Key 1 is the
+ * kernel forms -- the full list with one line each: tools/README.md; text2protein_amd/csrc/capi.cpp; key 48, read by t2p_train_create:
+ * the 16-bit training step's fixed-order reductions, scaled backward seed and overflow guard on f32 products).  Key 1 is the
  * timing-only ablation mask of the LDS-DMA kernel: its bits 128 / 256 (DMA issue order) and 4096 (LDS-staged instead of
  * register epilogue), results unchanged, are always accepted, the bits that skip work and so produce
  * WRONG results exist only in a library built with -DT2P_ABLATION (python -m text2protein_amd.build --ablation)

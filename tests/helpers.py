@@ -213,3 +213,69 @@ def projection(name, tensor, seed=99, cache=None):
         if cache is not None:
             cache[name] = r
     return float((v * r.double()).sum())
+
+
+def check_step_against_fixture(name, g, case, cfg, inp, model, step_fn, batch, *, loss_tol, score_tol, grad_tol, param_tol, delta_tol,
+                               step_batch=None, before_loss=None, before_step=None, after=None):
+    """The fp32 procedure of the whole-step tests (test_gpu_train / test_gpu_train_sde / test_gpu_train_ss: test_training_step_vs_reference)
+    on a model that is ready for its first pass: the loss and the score; every gradient through its norm and a random projection against
+    max(norm, zero-gradient floor), the total norm, the stored tensors element by element; then ONE step through ``step_fn`` and the
+    parameters, the EMA and both Adam moments the same way, the stored post-step parameters and the parameter UPDATE.  Every figure is
+    printed before anything is asserted and returned.  ``delta_tol`` None: the update's rel-L2 is reported only (the ss fixtures, where
+    test_gpu_train_ss explains why).  ``before_loss(model)`` / ``before_step()`` run just before the two passes; ``step_batch`` replaces
+    ``batch`` in the step (the ss cases hand the reference's strings to the Python mirror there); ``after(ctx)`` runs last with the tensors
+    read back (ctx: names, full, T, sd, grads, post), for checks only one fixture family makes."""
+    from text2protein_amd import losses, synth
+    names = [str(n) for n in g["names"]]
+    assert [n for n, _ in model.param_table()] == names and len(model._keep) == int(g["n_dropout_calls"])
+    if before_loss:
+        before_loss(model)
+    loss0, score = model.loss(batch, t=inp["t"], z=inp["z"], backward=True, return_score=True)
+    out = {"score_rel_l2": rel_l2(score.cpu()[:, :, ::8, ::8] if case.get("full_size") else score.cpu(), g["score"]),
+           "loss_rel": abs(loss0 - float(g["loss"])) / abs(float(g["loss"]))}
+    grads = model.read(losses.GRAD)
+    T = float(g["grad_total_norm"])
+    got_T = float(torch.sqrt(sum((v.double() ** 2).sum() for v in grads.values())))
+    floor = {"grads": 3e-5 * T, "m": 3e-6 * T, "v": 1e-12 * T * T, "post": 0.0, "ema": 0.0}
+    pcache = {}
+
+    def norms_and_projections(key, got):
+        wn = wp = 0.0
+        for i, n in enumerate(names):
+            scale = max(float(g[key + "_norm"][i]), floor[key], 1e-30)
+            wn = max(wn, abs(float(got[n].double().norm()) - float(g[key + "_norm"][i])) / scale)
+            wp = max(wp, abs(projection(n, got[n], cache=pcache) - float(g[key + "_proj"][i])) / scale)
+        return wn, wp
+
+    out["grad_norm"], out["grad_proj"] = norms_and_projections("grads", grads)
+    out["grad_total_rel"] = abs(got_T - T) / T
+    full = [k[5:] for k in g if k.startswith("grad:")]
+    out["grad_rel_l2"] = max(rel_l2(grads[n], g["grad:" + n]) for n in full)
+    print(f"{name}: loss {loss0:.6f} (reference {float(g['loss']):.6f}, rel {out['loss_rel']:.1e}), score rel-L2 {out['score_rel_l2']:.1e}, "
+          f"gradient norms {out['grad_norm']:.1e} / projections {out['grad_proj']:.1e} of max(norm, floor), total norm rel "
+          f"{out['grad_total_rel']:.1e}, worst stored gradient rel-L2 {out['grad_rel_l2']:.1e} over {len(full)} tensors")
+    assert out["loss_rel"] < loss_tol and out["score_rel_l2"] < score_tol and out["grad_rel_l2"] < grad_tol
+    assert out["grad_norm"] <= grad_tol and out["grad_proj"] <= 10 * grad_tol and out["grad_total_rel"] <= grad_tol
+    # the step itself
+    if before_step:
+        before_step()
+    state = dict(model=model, optimizer=losses.get_optimizer(cfg, model.parameters()),
+                 ema=losses.ExponentialMovingAverage(model.parameters(), decay=cfg.model.ema_rate), step=case["step0"])
+    loss1 = step_fn(state, batch if step_batch is None else step_batch, condition=cfg.model.condition, t=inp["t"], z=inp["z"])
+    assert abs(loss1 - loss0) <= 1e-6 * abs(loss0) and state["step"] == case["step0"] + 1
+    assert model.get_step() == (case["step0"] + 1, 1, 1)
+    post = {"post": model.read(losses.PARAM), "ema": model.read(losses.EMA), "m": model.read(losses.EXP_AVG), "v": model.read(losses.EXP_AVG_SQ)}
+    worst = {}
+    for key, tol in (("post", param_tol), ("ema", param_tol), ("m", grad_tol), ("v", 2 * grad_tol)):
+        worst[key] = norms_and_projections(key, post[key]) + (tol,)
+        out[key + "_norm"], out[key + "_proj"] = worst[key][:2]
+    sd = synth.synth_state_dict(cfg, case["seed"])
+    out["post_rel_l2"] = max(rel_l2(post["post"][n], g["post:" + n]) for n in full)
+    out["update_rel_l2"] = max(rel_l2(post["post"][n] - sd[n], torch.from_numpy(g["post:" + n]) - sd[n]) for n in full)
+    print(f"{name}: post-step parameters worst rel-L2 {out['post_rel_l2']:.1e}, parameter UPDATE worst rel-L2 {out['update_rel_l2']:.1e}; worst "
+          "norm / projection error of max(norm, floor): " + ", ".join(f"{k} {wn:.1e} / {wp:.1e}" for k, (wn, wp, _) in worst.items()))
+    assert all(wn <= tol and wp <= 10 * tol for wn, wp, tol in worst.values()), worst
+    assert out["post_rel_l2"] < param_tol and (delta_tol is None or out["update_rel_l2"] < delta_tol)
+    if after:
+        after(dict(names=names, full=full, T=T, sd=sd, grads=grads, post=post))
+    return out

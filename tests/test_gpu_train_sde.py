@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import TRAIN_CASES, load_golden, projection, rel_l2, train_inputs
+from helpers import TRAIN_CASES, check_step_against_fixture, load_golden, projection, rel_l2, train_inputs
 from sde_train_cases import SDE_TRAIN_CASES, make_sde
 
 pytestmark = pytest.mark.gpu
@@ -88,60 +88,17 @@ def test_training_step_vs_reference(name):
     tolerances of the VE step (test_gpu_train.test_training_step_vs_reference): the loss, the score, every gradient (norm + random
     projection for all tensors against max(norm, zero-gradient floor), element by element for the stored ones), the total norm, then the
     parameters, the EMA and both Adam moments after the update."""
-    from text2protein_amd import losses, synth
     g = load_golden(name)
     case, cfg, inp, model = _setup(name)
-    names = [str(n) for n in g["names"]]
-    assert [n for n, _ in model.param_table()] == names
-    assert len(model._keep) == int(g["n_dropout_calls"])
     assert np.array_equal(inp["t"].numpy(), g["t"])
-    batch = _batch(inp)
     sde, step_fn, _ = _fns(cfg, case)
     model.set_sde(sde)
-    loss0, score = model.loss(batch, t=inp["t"], z=inp["z"], backward=True, return_score=True)
-    e_score = rel_l2(score.cpu()[:, :, ::8, ::8] if case.get("full_size") else score.cpu(), g["score"])
-    e_loss = abs(loss0 - float(g["loss"])) / abs(float(g["loss"]))
-    grads = model.read(losses.GRAD)
-    T = float(g["grad_total_norm"])
-    got_T = float(torch.sqrt(sum((v.double() ** 2).sum() for v in grads.values())))
-    floor = {"grads": 3e-5 * T, "m": 3e-6 * T, "v": 1e-12 * T * T, "post": 0.0, "ema": 0.0}
-    pcache = {}
-    worst_norm = worst_proj = 0.0
-    for i, n in enumerate(names):
-        scale = max(float(g["grads_norm"][i]), floor["grads"], 1e-30)
-        worst_norm = max(worst_norm, abs(float(grads[n].double().norm()) - float(g["grads_norm"][i])) / scale)
-        worst_proj = max(worst_proj, abs(projection(n, grads[n], cache=pcache) - float(g["grads_proj"][i])) / scale)
-    full = [k[5:] for k in g if k.startswith("grad:")]
-    e_grad = max(rel_l2(grads[n], g["grad:" + n]) for n in full)
-    print(f"{name}: loss {loss0:.6f} (reference {float(g['loss']):.6f}, rel {e_loss:.1e}), score rel-L2 {e_score:.1e}, gradient norms "
-          f"{worst_norm:.1e} / projections {worst_proj:.1e} of max(norm, floor), total norm rel {abs(got_T - T) / T:.1e}, worst stored gradient "
-          f"rel-L2 {e_grad:.1e} over {len(full)} tensors")
-    assert e_loss < LOSS_TOL and e_score < SCORE_TOL and e_grad < GRAD_TOL
-    assert worst_norm <= GRAD_TOL and worst_proj <= 10 * GRAD_TOL and abs(got_T - T) <= GRAD_TOL * T
-    # the step itself
-    state = _state(model, cfg, case["step0"])
-    loss1 = step_fn(state, batch, condition=cfg.model.condition, t=inp["t"], z=inp["z"])
-    assert abs(loss1 - loss0) <= 1e-6 * abs(loss0) and state["step"] == case["step0"] + 1
-    assert model.get_step() == (case["step0"] + 1, 1, 1)
-    post = {"post": model.read(losses.PARAM), "ema": model.read(losses.EMA), "m": model.read(losses.EXP_AVG), "v": model.read(losses.EXP_AVG_SQ)}
     # (sign-like first Adam update at the full learning rate, see the VE test: 1e-4 at full size.  train_tinyB_vp steps at the full rate
     # too (step0 >= warmup) with one sample at t = 0.99: measured 9.5e-6 of the norm on the post-step projection, DESIGN.md section 7)
-    ptol = 1e-4 if case.get("full_size") else 2e-5 if name == "train_tinyB_vp" else PARAM_TOL
-    worst = {}
-    for key, tol in (("post", ptol), ("ema", ptol), ("m", GRAD_TOL), ("v", 2 * GRAD_TOL)):
-        wn = wp = 0.0
-        for i, n in enumerate(names):
-            scale = max(float(g[key + "_norm"][i]), floor[key], 1e-30)
-            wn = max(wn, abs(float(post[key][n].double().norm()) - float(g[key + "_norm"][i])) / scale)
-            wp = max(wp, abs(projection(n, post[key][n], cache=pcache) - float(g[key + "_proj"][i])) / scale)
-        worst[key] = (wn, wp, tol)
-    sd = synth.synth_state_dict(cfg, case["seed"])
-    e_post = max(rel_l2(post["post"][n], g["post:" + n]) for n in full)
-    e_delta = max(rel_l2(post["post"][n] - sd[n], torch.from_numpy(g["post:" + n]) - sd[n]) for n in full)
-    print(f"{name}: post-step parameters worst rel-L2 {e_post:.1e}, parameter UPDATE worst rel-L2 {e_delta:.1e}; worst norm / projection "
-          "error of max(norm, floor): " + ", ".join(f"{k} {wn:.1e} / {wp:.1e}" for k, (wn, wp, _) in worst.items()))
-    assert all(wn <= tol and wp <= 10 * tol for wn, wp, tol in worst.values()), worst
-    assert e_post < ptol and e_delta < (2e-2 if case.get("full_size") else 5e-3)
+    full_size = bool(case.get("full_size"))
+    check_step_against_fixture(name, g, case, cfg, inp, model, step_fn, _batch(inp), loss_tol=LOSS_TOL, score_tol=SCORE_TOL, grad_tol=GRAD_TOL,
+                               param_tol=1e-4 if full_size else 2e-5 if name == "train_tinyB_vp" else PARAM_TOL,
+                               delta_tol=2e-2 if full_size else 5e-3)
 
 
 # ---- 2. the per-sample quantities alone -----------------------------------------------------------------------------------------------

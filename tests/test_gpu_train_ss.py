@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import TRAIN_CASES, load_golden, projection, rel_l2, train_inputs
+from helpers import TRAIN_CASES, check_step_against_fixture, load_golden, projection, rel_l2, train_inputs
 from sde_train_cases import make_sde
 from ss_train_cases import BLOCK_DROPOUT, SS_TRAIN_CASES, dropped_coords, ss_record
 from test_gpu_train import GRAD_TOL, LOSS_TOL, PARAM_TOL
@@ -171,86 +171,54 @@ def test_training_step_vs_reference(name):
     """ONE fp32 step with the fixture's blocks and decisions against autograd through the reference UNetModel on the coordinates the
     reference's block_dropout produced: loss, every gradient, then the parameters, the EMA and both Adam moments after the update, at
     test_gpu_train.py's tolerances.  The step itself goes through get_step_fn with batch["ss_indices"] under the fixture's random.seed."""
-    from text2protein_amd import losses, synth
     g = load_golden(name)
     case, cfg, inp, model = _setup(name)
-    names = [str(n) for n in g["names"]]
-    assert [n for n, _ in model.param_table()] == names and len(model._keep) == int(g["n_dropout_calls"])
     assert "t" not in g or np.array_equal(inp["t"].numpy(), g["t"])
+    sde, step_fn, _ = _fns(cfg, case)
+    model.set_sde(sde)
+    check_ss_step_against_fixture(name, g, case, cfg, inp, model, step_fn)
+
+
+def check_ss_step_against_fixture(name, g, case, cfg, inp, model, step_fn, label=None):
+    """helpers.check_step_against_fixture for a block-dropout fixture, with what only these fixtures need: the fixture's blocks and
+    decisions for the loss, the strings and the reference's own draws (random.seed) for the step through the Python mirror; the fixture
+    tells a step without the dropout apart; the caller's coords_6d is not modified; the update element by element where it is determined."""
     rec = ss_record(g)
     batch = _batch(inp)
     coords_before = batch["coords_6d"].clone()
-    sde, step_fn, _ = _fns(cfg, case)
-    model.set_sde(sde)
-    model.set_ss_blocks(rec["blocks"], drop=rec["decisions"])
-    loss0, score = model.loss(batch, t=inp["t"], z=inp["z"], backward=True, return_score=True)
-    e_score = rel_l2(score.cpu(), g["score"])
-    e_loss = abs(loss0 - float(g["loss"])) / abs(float(g["loss"]))
     base_loss = float(load_golden(case["base"])["loss"])
-    grads = model.read(losses.GRAD)
-    T = float(g["grad_total_norm"])
-    got_T = float(torch.sqrt(sum((v.double() ** 2).sum() for v in grads.values())))
-    floor = {"grads": 3e-5 * T, "m": 3e-6 * T, "v": 1e-12 * T * T, "post": 0.0, "ema": 0.0}
-    pcache = {}
-    worst_norm = worst_proj = 0.0
-    for i, n in enumerate(names):
-        scale = max(float(g["grads_norm"][i]), floor["grads"], 1e-30)
-        worst_norm = max(worst_norm, abs(float(grads[n].double().norm()) - float(g["grads_norm"][i])) / scale)
-        worst_proj = max(worst_proj, abs(projection(n, grads[n], cache=pcache) - float(g["grads_proj"][i])) / scale)
-    full = [k[5:] for k in g if k.startswith("grad:")]
-    e_grad = max(rel_l2(grads[n], g["grad:" + n]) for n in full)
-    print(f"{name}: loss {loss0:.6f} (reference {float(g['loss']):.6f}, rel {e_loss:.1e}; without block dropout {base_loss:.6f}), score rel-L2 "
-          f"{e_score:.1e}, gradient norms {worst_norm:.1e} / projections {worst_proj:.1e} of max(norm, floor), total norm rel "
-          f"{abs(got_T - T) / T:.1e}, worst stored gradient rel-L2 {e_grad:.1e} over {len(full)} tensors")
     assert abs(float(g["loss"]) - base_loss) > 100 * LOSS_TOL * abs(base_loss)      # the fixture tells a step without the dropout apart
-    assert e_loss < LOSS_TOL and e_score < 1e-5 and e_grad < GRAD_TOL
-    assert worst_norm <= GRAD_TOL and worst_proj <= 10 * GRAD_TOL and abs(got_T - T) <= GRAD_TOL * T
-    # the step itself, through the Python mirror: the strings and the reference's own draws
-    state = _state(model, cfg, case["step0"])
-    random.seed(case["py_seed"])
-    loss1 = step_fn(state, dict(batch, ss_indices=case["ss_indices"]), condition=cfg.model.condition, t=inp["t"], z=inp["z"])
-    assert abs(loss1 - loss0) <= 1e-6 * abs(loss0) and state["step"] == case["step0"] + 1
-    assert model.get_step() == (case["step0"] + 1, 1, 1)
-    assert torch.equal(batch["coords_6d"], coords_before)                 # the caller's coords_6d is not modified
-    post = {"post": model.read(losses.PARAM), "ema": model.read(losses.EMA), "m": model.read(losses.EXP_AVG), "v": model.read(losses.EXP_AVG_SQ)}
-    worst = {}
-    for key, tol in (("post", PARAM_TOL), ("ema", PARAM_TOL), ("m", GRAD_TOL), ("v", 2 * GRAD_TOL)):
-        wn = wp = 0.0
-        for i, n in enumerate(names):
-            scale = max(float(g[key + "_norm"][i]), floor[key], 1e-30)
-            wn = max(wn, abs(float(post[key][n].double().norm()) - float(g[key + "_norm"][i])) / scale)
-            wp = max(wp, abs(projection(n, post[key][n], cache=pcache) - float(g[key + "_proj"][i])) / scale)
-        worst[key] = (wn, wp, tol)
-    sd = synth.synth_state_dict(cfg, case["seed"])
-    e_post = max(rel_l2(post["post"][n], g["post:" + n]) for n in full)
-    e_delta, n_delta = max((rel_l2(post["post"][n] - sd[n], torch.from_numpy(g["post:" + n]) - sd[n]), n) for n in full)
-    print(f"{name}: post-step parameters worst rel-L2 {e_post:.1e}, parameter UPDATE worst rel-L2 {e_delta:.1e} ({n_delta}, gradient norm "
-          f"{float(g['grads_norm'][names.index(n_delta)]):.2e} over {post['post'][n_delta].numel()} elements, largest |update difference| "
-          f"{float((post['post'][n_delta] - torch.from_numpy(g['post:' + n_delta])).abs().max()):.2e} at lr "
-          f"{cfg.optim.lr * min(case['step0'] / cfg.optim.warmup, 1.0):.1e}); worst norm / projection "
-          "error of max(norm, floor): " + ", ".join(f"{k} {wn:.1e} / {wp:.1e}" for k, (wn, wp, _) in worst.items()))
-    assert all(wn <= tol and wp <= 10 * tol for wn, wp, tol in worst.values()), worst
-    assert e_post < PARAM_TOL
-    # The update itself.  Its rel-L2 over a whole tensor is only reported (measured 5.8e-3 VE / 6.3e-3 VP, on tensors with elements whose
-    # gradient is within rounding of zero: Adam's first step moves an element by lr g / (|g| + eps), so such an element may land
-    # anywhere between -lr and +lr on either side and no gradient tolerance bounds the difference).  Asserted is the update of every
-    # element whose gradient is FAR from zero, where it is determined: with c = the clipping factor and |c g| >= 1000 eps the step is
-    # sign(g) lr to within 1e-3 lr, and an element with |g| > 2 GRAD_TOL ||g|| cannot have another sign here than in the reference (the
-    # element error is at most the tensor's, asserted above).  Bound: 2e-3 lr + 4 ulp of the parameter.
-    lr = cfg.optim.lr * min(case["step0"] / cfg.optim.warmup, 1.0)
-    clip = min(1.0, cfg.optim.grad_clip / (T + 1e-6)) if cfg.optim.grad_clip >= 0 else 1.0
-    assert cfg.optim.weight_decay == 0 and cfg.optim.eps == 1e-8
-    checked = 0
-    for n in full:
-        gref = torch.from_numpy(g["grad:" + n]).double()
-        sel = (gref.abs() > 2 * GRAD_TOL * float(gref.norm())) & (gref.abs() * clip >= 1000 * cfg.optim.eps)
-        got_d, ref_d = (post["post"][n] - sd[n])[sel], (torch.from_numpy(g["post:" + n]) - sd[n])[sel]
-        bound = 2e-3 * lr + 4 * 6e-8 * sd[n][sel].abs()
-        assert ((got_d - ref_d).abs() <= bound).all(), (n, float((got_d - ref_d).abs().max()), lr)
-        assert ((got_d + lr * torch.sign(gref[sel]).float()).abs() <= bound).all(), n       # and it is -lr sign(g)
-        checked += int(sel.sum())
-    print(f"{name}: update checked element by element on {checked} elements with a gradient far from zero (lr {lr:.1e}, clip factor {clip:.3g})")
-    assert checked > 1000
+
+    def update_where_determined(ctx):
+        # The update itself.  Its rel-L2 over a whole tensor is only reported (measured 5.8e-3 VE / 6.3e-3 VP, on tensors with elements whose
+        # gradient is within rounding of zero: Adam's first step moves an element by lr g / (|g| + eps), so such an element may land
+        # anywhere between -lr and +lr on either side and no gradient tolerance bounds the difference).  Asserted is the update of every
+        # element whose gradient is FAR from zero, where it is determined: with c = the clipping factor and |c g| >= 1000 eps the step is
+        # sign(g) lr to within 1e-3 lr, and an element with |g| > 2 GRAD_TOL ||g|| cannot have another sign here than in the reference (the
+        # element error is at most the tensor's, asserted above).  Bound: 2e-3 lr + 4 ulp of the parameter.
+        assert torch.equal(batch["coords_6d"], coords_before)                 # the caller's coords_6d is not modified
+        post, sd, T = ctx["post"], ctx["sd"], ctx["T"]
+        lr = cfg.optim.lr * min(case["step0"] / cfg.optim.warmup, 1.0)
+        clip = min(1.0, cfg.optim.grad_clip / (T + 1e-6)) if cfg.optim.grad_clip >= 0 else 1.0
+        assert cfg.optim.weight_decay == 0 and cfg.optim.eps == 1e-8
+        checked = 0
+        for n in ctx["full"]:
+            gref = torch.from_numpy(g["grad:" + n]).double()
+            sel = (gref.abs() > 2 * GRAD_TOL * float(gref.norm())) & (gref.abs() * clip >= 1000 * cfg.optim.eps)
+            got_d, ref_d = (post["post"][n] - sd[n])[sel], (torch.from_numpy(g["post:" + n]) - sd[n])[sel]
+            bound = 2e-3 * lr + 4 * 6e-8 * sd[n][sel].abs()
+            assert ((got_d - ref_d).abs() <= bound).all(), (n, float((got_d - ref_d).abs().max()), lr)
+            assert ((got_d + lr * torch.sign(gref[sel]).float()).abs() <= bound).all(), n       # and it is -lr sign(g)
+            checked += int(sel.sum())
+        print(f"{name}: loss without block dropout {base_loss:.6f}; update checked element by element on {checked} elements with a gradient far "
+              f"from zero (lr {lr:.1e}, clip factor {clip:.3g})")
+        assert checked > 1000
+
+    return check_step_against_fixture(label or name, g, case, cfg, inp, model, step_fn, batch, loss_tol=LOSS_TOL, score_tol=1e-5,
+                                      grad_tol=GRAD_TOL, param_tol=PARAM_TOL, delta_tol=None,
+                                      before_loss=lambda m: m.set_ss_blocks(rec["blocks"], drop=rec["decisions"]),
+                                      before_step=lambda: random.seed(case["py_seed"]),
+                                      step_batch=dict(batch, ss_indices=case["ss_indices"]), after=update_where_determined)
 
 
 # ---- 3. f16 / bf16 ----------------------------------------------------------------------------------------------------------------------

@@ -142,6 +142,11 @@ SIGNATURES = {
     "t2p_op_ss_block_dropout": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, C.c_double, _u64, _u64, _vp, _vp]),
     "t2p_op_groupnorm_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "t2p_op_layernorm_backward": (_i, [_vp, _vp, _vp, _i64, _i, _f, _vp, _vp, _vp, _vp]),
+    "t2p_op_groupnorm_backward_form": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp]),
+    "t2p_op_layernorm_backward_form": (_i, [_vp, _vp, _vp, _i64, _i, _f, _vp, _vp, _vp, _i, _vp]),
+    "t2p_op_colsum": (_i, [_vp, _i, _i64, _i, _i64, _vp, _i64, _i, _i, _vp]),
+    "t2p_op_sumsq": (_i, [_vp, _i64, _i, C.POINTER(C.c_double), _vp]),
+    "t2p_op_seed_scale": (_i, [_vp, _i64, _f, C.POINTER(_f), _vp]),
     "t2p_op_softmax_backward": (_i, [_vp, _vp, _i64, _i, _f, _vp]),
     "t2p_op_geglu_backward": (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
 }

@@ -16,10 +16,13 @@
 // implicit GEMM (fp32 activations rounded once into a pass-local 16-bit copy, 16-bit weight copies made by prep_weights), every strided product on
 // launch_tgemm16; the input and head convolutions (5 or 8 channels) keep the exact-f32 kernel for their forward and data gradient.
 // The dtype is looked at in three places only: tg (which strided GEMM), conv3x3 (a convolution that has 16-bit weight copies runs on
-// them) and fixed_order_ (set in build(): which form of the reduction launchers; reduce_ws hands out their workspace, or null).
+// them) and plumbing16_ (set in build(): which form of the reduction launchers, reduce_ws hands out their workspace or
+// null; the scaled backward seed; the overflow guard of apply()).  The first two are the PRODUCTS, the third is everything else the
+// 16-bit step does differently; plan switch 48 (g_train_plumbing16, read at build()) turns the third on in an f32 trainer, so that it
+// can be held to the reference at fp32 tolerances with every product exact.
 // The backward pass is seeded with S dL/do, S = 2^round(log2(B C L L)) (the fp32 seed is ~1e-5 at full size, at the bottom of
 // f16's normal range; under the VP / sub-VP SDE S is chosen on the device from max|dL/do|), and S is divided out of the flat gradient buffer once at the end.  Every reduction that feeds a gradient, the
-// gradient norm or an update runs in a fixed order (fixed_order_), so the gradients and the state after a 16-bit step are bitwise reproducible (the
+// gradient norm or an update runs in a fixed order (plumbing16_), so the gradients and the state after a 16-bit step are bitwise reproducible (the
 // scalar loss itself is still summed with double atomics, shared with the fp32 step).  apply() refuses (and changes nothing) when the
 // loss or the gradient norm is not finite.
 #include "train.h"
@@ -29,6 +32,8 @@
 #include <cstring>
 
 namespace t2p {
+
+bool g_train_plumbing16 = false;   // plan switch 48: a trainer created while it is set runs the 16-bit step's plumbing on its own products
 
 static int gn_groups_of(int c) { return std::min(c / 4, 32); }   // layers.py:282
 
@@ -107,7 +112,8 @@ int Trainer::build() {
   T2P_REQUIRE(mc_.compute_dtype == DT_F32 || mc_.compute_dtype == DT_F16 || mc_.compute_dtype == DT_BF16,
               "the training step computes in f32, f16 or bf16");
   dt_ = mc_.compute_dtype;
-  fixed_order_ = dt_ != DT_F32;            // the 16-bit step is bitwise reproducible; the f32 step keeps its atomic reductions
+  plumbing16_ = dt_ != DT_F32 || g_train_plumbing16;   // which products (dt_) and which plumbing are two questions; with it every
+                                                       // reduction runs in a fixed order (bitwise reproducible), without it on atomics
   T2P_REQUIRE(tc_.dropout >= 0.0 && tc_.dropout < 1.0 && tc_.ema_rate >= 0.0 && tc_.ema_rate <= 1.0, "dropout / ema_rate");
   int dev = 0;
   T2P_HIP_CHECK(hipGetDevice(&dev));       // fails without a HIP device: there is no CPU fallback
@@ -181,7 +187,7 @@ int Trainer::build() {
       if (!c->wf16 || !c->wd16) return T2P_ERR_HIP;
     }
   }
-  if (fixed_order_) {
+  if (plumbing16_) {
     sumsq_part_ = (double*)pool_.persistent(1024 * 8);
     if (!sumsq_part_) return T2P_ERR_HIP;
   }
@@ -331,8 +337,8 @@ int Trainer::prep_weights(const float* P, hipStream_t s) {
 }
 
 int Trainer::reduce_ws(long floats, float** ws) {
-  *ws = fixed_order_ ? tmp((size_t)floats * 4) : nullptr;
-  return fixed_order_ && !*ws ? T2P_ERR_HIP : T2P_OK;
+  *ws = plumbing16_ ? tmp((size_t)floats * 4) : nullptr;
+  return plumbing16_ && !*ws ? T2P_ERR_HIP : T2P_OK;
 }
 
 // out [nz][N] += the column sums of the nz blocks of `rows` rows of dy: nz = 1 a bias gradient, nz = B the per-sample time-embedding bias
@@ -466,7 +472,7 @@ int Trainer::group_norm(TT* x, const Norm& n, int silu, TT** out) {
     T2P_GRAD(gx, x);
     float* ws = tmp((size_t)gn_bwd_ws_floats(B, HW, N.C, N.G) * 4);
     if (!ws) return T2P_ERR_HIP;
-    return launch_gn_backward(x->p, y->g, stats, Pc_ + N.g, Pc_ + N.b, silu, B, HW, N.C, N.G, gx, Gr_ + N.g, Gr_ + N.b, ws, fixed_order_, s_);
+    return launch_gn_backward(x->p, y->g, stats, Pc_ + N.g, Pc_ + N.b, silu, B, HW, N.C, N.G, gx, Gr_ + N.g, Gr_ + N.b, ws, plumbing16_, s_);
   });
   return T2P_OK;
 }
@@ -795,8 +801,8 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool tra
   // VP / sub-VP: the seed carries std |scale| = up to 1 / sigma_min with scale_by_sigma (the sigma table is indexed by a label that
   // grows with t) and a residual r of that size, so a fixed S overflows f16 at large t: S is chosen on the device as the largest
   // power of two with S max|dL/do| <= 64, the magnitude the VE seed has.
-  const bool dev_scale = backward && dt_ != DT_F32 && sde_ != T2P_SDE_VE;
-  const float S = dt_ == DT_F32 ? 1.f : std::ldexp(1.f, (int)std::lround(std::log2((double)B * Cx * HW)));
+  const bool dev_scale = backward && plumbing16_ && sde_ != T2P_SDE_VE;
+  const float S = !plumbing16_ ? 1.f : std::ldexp(1.f, (int)std::lround(std::log2((double)B * Cx * HW)));
   float* s2 = nullptr;                            // device pair {S, 1 / S} of the VP / sub-VP 16-bit step
   if (dev_scale) {
     s2 = tmp(8);
@@ -846,11 +852,12 @@ int Trainer::apply(hipStream_t s) {
   a.p = P_; a.g = Gr_; a.m = M_; a.v = V_; a.n = total_;
   a.lr = (float)(tc_.warmup > 0 ? tc_.lr * std::min((double)step_ / tc_.warmup, 1.0) : tc_.lr);
   a.beta1 = (float)tc_.beta1; a.beta2 = 0.999f; a.eps = (float)tc_.eps; a.weight_decay = (float)tc_.weight_decay;
+  a.one_minus_beta1 = (float)(1.0 - tc_.beta1); a.one_minus_beta2 = (float)(1.0 - 0.999);
   const int64_t k = adam_k_ + 1;
   a.bias1 = (float)(1.0 - std::pow(tc_.beta1, (double)k));
   a.bias2_sqrt = (float)std::sqrt(1.0 - std::pow(0.999, (double)k));
   a.grad_clip = (float)tc_.grad_clip;
-  const bool guard = dt_ != DT_F32;               // overflow guard (AMP's skipped step, reported): a loss or gradient norm that is not finite changes nothing
+  const bool guard = plumbing16_;                 // overflow guard (AMP's skipped step, reported): a loss or gradient norm that is not finite changes nothing
   if (guard || tc_.grad_clip >= 0) {
     if (!sumsq_part_) T2P_HIP_CHECK(hipMemsetAsync(sumsq_, 0, 8, s));     // the atomic form accumulates
     T2P_TRY(launch_sumsq(Gr_, total_, sumsq_part_, sumsq_, s));

@@ -3,7 +3,8 @@
 // score_sde_pytorch/models/ema.py:32-49).  compute_dtype F32: exact-f32 products; F16 / BF16: 16-bit products with fp32 accumulation,
 // everything the optimizer sees (parameters, gradients, moments, EMA, loss) fp32.  Every operator of the network (linear, conv3x3,
 // group_norm, layer_norm, attention, add_scale) is one member that runs its forward and appends its backward to the tape; the
-// dtypes differ inside tg (which strided GEMM), conv3x3 (which implicit GEMM) and in fixed_order_ (which form of the reductions).
+// dtypes differ inside tg (which strided GEMM), conv3x3 (which implicit GEMM) and in plumbing16_ (which form of the reductions, the
+// scaled backward seed, the overflow guard).
 #pragma once
 #include <deque>
 #include <functional>
@@ -15,6 +16,11 @@
 #include "train_kernels.h"
 
 namespace t2p {
+
+// plan switch 48 (t2p_debug_set): a trainer CREATED while it is set uses everything the 16-bit step uses except the products -- the
+// fixed-order reductions, the scaled backward seed (host power of two for VE, seed_scale on the device for VP / sub-VP) and the
+// overflow guard -- with tg and conv3x3 on the f32 kernels.  Off by default; the product path never sets it
+extern bool g_train_plumbing16;
 
 struct TParam {           // one learnable tensor: a slice of the flat buffers, in the reference's parameters() order
   std::string name;
@@ -123,9 +129,10 @@ class Trainer {
   float* vp_std_ = nullptr;         // VP: sqrt_1m_alphas_cumprod, float[num_scales] (the divisor of the score, models/utils.py:154)
   int64_t step_ = 0, adam_k_ = 0, ema_k_ = 0, loss_calls_ = 0;
   int dt_ = DT_F32;                 // compute dtype of the products
-  bool fixed_order_ = false;        // 16-bit modes: every reduction that feeds a gradient or an update runs in a fixed order
-  double* sumsq_part_ = nullptr;    // fixed_order_: the partial sums of the gradient norm (launch_sumsq)
-  bool last_loss_finite_ = false;   // 16-bit modes: the last backward pass completed with a finite loss (the overflow guard of apply)
+  bool plumbing16_ = false;         // the 16-bit step's plumbing (16-bit modes, or an f32 trainer created under plan switch 48): every reduction
+                                    // that feeds a gradient or an update runs in a fixed order, the backward seed is scaled, apply() is guarded
+  double* sumsq_part_ = nullptr;    // plumbing16_: the partial sums of the gradient norm (launch_sumsq)
+  bool last_loss_finite_ = false;   // plumbing16_: the last backward pass completed with a finite loss (the overflow guard of apply)
   std::vector<std::vector<LayerT>> in_stages_, out_stages_;
   std::vector<LayerT> mid_;
   Lin pre0_, pre1_;

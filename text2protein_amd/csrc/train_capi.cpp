@@ -1,4 +1,5 @@
 // extern "C" surface of the training step (declarations and reference citations: include/t2p.h, "training step").
+#include <algorithm>
 #include <new>
 
 #include "train.h"
@@ -240,11 +241,9 @@ int t2p_op_ss_block_dropout(const float* x, float* out, int batch, int C, int L,
 }
 
 // the op-level backward entry points take eps and recompute the forward statistics themselves (tests hold no engine state)
-int t2p_op_groupnorm_backward(const float* x, const float* dy, const float* gamma, const float* beta, int silu, int batch, int HW, int C,
-                              int groups, float eps, float* dx, float* dgamma, float* dbeta, void* stream) {
-  API_BEGIN
+static int op_groupnorm_backward(const float* x, const float* dy, const float* gamma, const float* beta, int silu, int batch, int HW, int C,
+                                 int groups, float eps, float* dx, float* dgamma, float* dbeta, bool fixed_order, hipStream_t s) {
   T2P_REQUIRE(x && dy && gamma && beta && dx && dgamma && dbeta && batch > 0 && HW > 0 && C > 0 && groups > 0 && C % groups == 0, "groupnorm_backward arguments");
-  hipStream_t s = (hipStream_t)stream;
   float *stats = nullptr, *partial = nullptr, *ws = nullptr;
   const int nparts = gn_num_chunks(HW) * ((C + 1023) / 1024);
   int rc = T2P_OK;
@@ -258,10 +257,23 @@ int t2p_op_groupnorm_backward(const float* x, const float* dy, const float* gamm
   GroupNormArgs a;
   a.x0 = x; a.C0 = C; a.B = batch; a.HW = HW; a.G = groups; a.eps = eps; a.partial = partial; a.stats = stats;
   if (rc == T2P_OK) rc = launch_gn_stats(a, s);
-  if (rc == T2P_OK) rc = launch_gn_backward(x, dy, stats, gamma, beta, silu, batch, HW, C, groups, dx, dgamma, dbeta, ws, false, s);
+  if (rc == T2P_OK) rc = launch_gn_backward(x, dy, stats, gamma, beta, silu, batch, HW, C, groups, dx, dgamma, dbeta, ws, fixed_order, s);
   (void)hipStreamSynchronize(s);
   (void)hipFree(stats); (void)hipFree(partial); (void)hipFree(ws);   // hipFree(nullptr) is a no-op: one cleanup path, whichever step failed
   return rc;
+}
+
+int t2p_op_groupnorm_backward(const float* x, const float* dy, const float* gamma, const float* beta, int silu, int batch, int HW, int C,
+                              int groups, float eps, float* dx, float* dgamma, float* dbeta, void* stream) {
+  API_BEGIN
+  return op_groupnorm_backward(x, dy, gamma, beta, silu, batch, HW, C, groups, eps, dx, dgamma, dbeta, false, (hipStream_t)stream);
+  API_END
+}
+
+int t2p_op_groupnorm_backward_form(const float* x, const float* dy, const float* gamma, const float* beta, int silu, int batch, int HW, int C,
+                                   int groups, float eps, float* dx, float* dgamma, float* dbeta, int fixed_order, void* stream) {
+  API_BEGIN
+  return op_groupnorm_backward(x, dy, gamma, beta, silu, batch, HW, C, groups, eps, dx, dgamma, dbeta, fixed_order != 0, (hipStream_t)stream);
   API_END
 }
 
@@ -269,6 +281,89 @@ int t2p_op_layernorm_backward(const float* x, const float* dy, const float* gamm
                               float* dbeta, void* stream) {
   API_BEGIN
   return launch_ln_backward(x, dy, gamma, rows, C, eps, dx, dgamma, dbeta, nullptr, (hipStream_t)stream);
+  API_END
+}
+
+// the fixed-order forms take a workspace: allocated here from the launcher's own size function, freed after the stream has drained
+static int op_ws_alloc(const char* what, long floats, float** ws) {
+  const hipError_t e = hipMalloc(ws, (size_t)std::max(floats, 1L) * 4);
+  if (e == hipSuccess) return T2P_OK;
+  *ws = nullptr;
+  set_last_error(std::string(what) + ": hipMalloc: " + hipGetErrorString(e));
+  return T2P_ERR_HIP;
+}
+
+int t2p_op_layernorm_backward_form(const float* x, const float* dy, const float* gamma, int64_t rows, int C, float eps, float* dx,
+                                   float* dgamma, float* dbeta, int fixed_order, void* stream) {
+  API_BEGIN
+  hipStream_t s = (hipStream_t)stream;
+  if (!fixed_order) return launch_ln_backward(x, dy, gamma, rows, C, eps, dx, dgamma, dbeta, nullptr, s);
+  T2P_REQUIRE(rows > 0 && C > 0, "layernorm_backward arguments");
+  float* ws = nullptr;
+  T2P_TRY(op_ws_alloc("layernorm_backward", ln_bwd_ws_floats(rows, C), &ws));
+  const int rc = launch_ln_backward(x, dy, gamma, rows, C, eps, dx, dgamma, dbeta, ws, s);
+  (void)hipStreamSynchronize(s);
+  (void)hipFree(ws);
+  return rc;
+  API_END
+}
+
+int t2p_op_colsum(const float* dy, int nz, int64_t rows_per_z, int N, int64_t ld, float* out, int64_t ld_out, int accumulate, int fixed_order,
+                  void* stream) {
+  API_BEGIN
+  hipStream_t s = (hipStream_t)stream;
+  if (!fixed_order) return launch_colsum(dy, nz, rows_per_z, N, ld, out, ld_out, accumulate, nullptr, s);
+  T2P_REQUIRE(nz > 0 && rows_per_z > 0 && N > 0, "colsum arguments");
+  float* ws = nullptr;
+  T2P_TRY(op_ws_alloc("colsum", colsum_ws_floats(nz, rows_per_z, N), &ws));
+  const int rc = launch_colsum(dy, nz, rows_per_z, N, ld, out, ld_out, accumulate, ws, s);
+  (void)hipStreamSynchronize(s);
+  (void)hipFree(ws);
+  return rc;
+  API_END
+}
+
+int t2p_op_sumsq(const float* g, int64_t n, int fixed_order, double* result_host, void* stream) {
+  API_BEGIN
+  T2P_REQUIRE(g && n > 0 && result_host, "sumsq arguments");
+  hipStream_t s = (hipStream_t)stream;
+  double* buf = nullptr;                  // [0]: the result, [1 .. 1024]: the partials of the fixed-order form
+  const hipError_t e = hipMalloc(&buf, (size_t)1025 * 8);
+  if (e != hipSuccess) {
+    set_last_error(std::string("sumsq: hipMalloc: ") + hipGetErrorString(e));
+    return T2P_ERR_HIP;
+  }
+  int rc = T2P_OK;
+  if (hipMemsetAsync(buf, 0, 8, s) != hipSuccess) rc = T2P_ERR_HIP;      // the atomic form accumulates
+  if (rc == T2P_OK) rc = launch_sumsq(g, n, fixed_order ? buf + 1 : nullptr, buf, s);
+  if (rc == T2P_OK && (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(result_host, buf, 8, hipMemcpyDeviceToHost) != hipSuccess)) {
+    set_last_error("sumsq: reading the result back failed");
+    rc = T2P_ERR_HIP;
+  }
+  (void)hipStreamSynchronize(s);
+  (void)hipFree(buf);
+  return rc;
+  API_END
+}
+
+int t2p_op_seed_scale(const float* x, int64_t n, float target, float* s2_host, void* stream) {
+  API_BEGIN
+  T2P_REQUIRE(x && n > 0 && s2_host && target > 0.f, "seed_scale arguments");
+  hipStream_t s = (hipStream_t)stream;
+  float* buf = nullptr;                   // [0 .. 1]: {S, 1 / S}, [2]: the absmax word
+  const hipError_t e = hipMalloc(&buf, 3 * 4);
+  if (e != hipSuccess) {
+    set_last_error(std::string("seed_scale: hipMalloc: ") + hipGetErrorString(e));
+    return T2P_ERR_HIP;
+  }
+  int rc = launch_seed_scale(x, n, target, (unsigned int*)(buf + 2), buf, s);
+  if (rc == T2P_OK && (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(s2_host, buf, 8, hipMemcpyDeviceToHost) != hipSuccess)) {
+    set_last_error("seed_scale: reading the result back failed");
+    rc = T2P_ERR_HIP;
+  }
+  (void)hipStreamSynchronize(s);
+  (void)hipFree(buf);
+  return rc;
   API_END
 }
 

@@ -126,6 +126,7 @@ int launch_sumsq(const float* g, long n, double* partial, double* out, hipStream
 struct AdamArgs {
   float* p = nullptr; float* g = nullptr; float* m = nullptr; float* v = nullptr; long n = 0;
   float lr = 0.f, beta1 = 0.9f, beta2 = 0.999f, eps = 1e-8f, weight_decay = 0.f;
+  float one_minus_beta1 = 0.1f, one_minus_beta2 = 0.001f;   // rounded from double, as torch rounds its scalars: 1.f - 0.999f is 1.3e-5 off 0.001f
   float bias1 = 1.f, bias2_sqrt = 1.f;    // 1 - beta1^k, sqrt(1 - beta2^k)
   float grad_clip = -1.f;                 // >= 0: g *= min(1, grad_clip / (sqrt(*sumsq) + 1e-6)) first (written back, as clip_grad_norm_ does)
   const double* sumsq = nullptr;
@@ -133,8 +134,9 @@ struct AdamArgs {
 int launch_adam(const AdamArgs& a, hipStream_t s);
 int launch_ema(float* shadow, const float* p, float one_minus_decay, long n, hipStream_t s);   // shadow -= (1 - d) (shadow - p)
 int launch_scale(float* x, float a, long n, hipStream_t s);                                   // x *= a
-// s2[0] = S = the largest power of two with S max|x| <= target (1 when x is all zero or not finite), s2[1] = 1 / S; absmax: one
-// device word of scratch.  The maximum is taken with integer atomics on the bit patterns: the same S whatever the order of arrival
+// s2[0] = S = 2^e, e = the largest integer with 2^e max|x| <= target, clamped to [-60, 60] (S and 1 / S stay normal floats for any
+// maximum, a subnormal one included; beyond the clamp S max|x| <= target no longer holds); S = 1 when x is all zero or not finite;
+// s2[1] = 1 / S; absmax: one device word of scratch.  The maximum is taken with integer atomics on the bit patterns: the same S whatever the order of arrival
 int launch_seed_scale(const float* x, long n, float target, unsigned int* absmax, float* s2, hipStream_t s);
 int launch_scale_dev(float* x, const float* a, long n, hipStream_t s);                        // x *= *a (a on the device)
 

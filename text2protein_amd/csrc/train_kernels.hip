@@ -1344,8 +1344,8 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
     float g = a.g[i] * clip;
     a.g[i] = g;                                        // clip_grad_norm_ scales .grad in place
     if (a.weight_decay != 0.f) g += a.weight_decay * a.p[i];
-    const float m = a.beta1 * a.m[i] + (1.f - a.beta1) * g;
-    const float v = a.beta2 * a.v[i] + (1.f - a.beta2) * g * g;
+    const float m = a.beta1 * a.m[i] + a.one_minus_beta1 * g;
+    const float v = a.beta2 * a.v[i] + a.one_minus_beta2 * g * g;
     a.m[i] = m; a.v[i] = v;
     a.p[i] -= step * m / (sqrtf(v) / a.bias2_sqrt + a.eps);
   }
@@ -1386,14 +1386,29 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ x
   for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned int)__shfl_xor((int)m, o));
   if ((threadIdx.x & 63) == 0 && m != 0) atomicMax(out, m);
 }
+// v > 0 finite = (1 + frac 2^-23) 2^e: returns frac (23 bits) and e, a subnormal v normalised first
+__device__ inline unsigned int pow2_split(const float v, int* e) {
+  const unsigned int b = __float_as_uint(v);
+  int ex = (int)(b >> 23);
+  unsigned int frac = b & 0x7fffffu;
+  if (ex == 0) {                                   // subnormal: frac != 0, its leading one moves up to the implicit position
+    const int sh = __clz((int)frac) - 8;
+    frac = (frac << sh) & 0x7fffffu;
+    ex = 1 - sh;
+  }
+  *e = ex - 127;
+  return frac;
+}
 __global__ void seed_scale_kernel(const unsigned int* __restrict__ absmax, const float target, float* __restrict__ s2) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const float m = __uint_as_float(*absmax);
   float S = 1.f;
   if (m > 0.f && m < INFINITY) {                 // (a NaN or infinite seed keeps S = 1: the loss is not finite and apply() refuses)
-    int e = 0;
-    frexpf(target / m, &e);                      // target / m = f 2^e, f in [0.5, 1): 2^(e - 1) <= target / m
-    S = ldexpf(1.f, min(max(e - 1, -60), 60));
+    // m = fm 2^em, target = ft 2^et, fm and ft in [1, 2): floor(log2(target / m)) = et - em - (ft < fm).  From the bit patterns, not from
+    // the quotient: target / m overflows for a subnormal m, and frexpf of an infinity leaves the exponent unspecified
+    int em = 0, et = 0;
+    const unsigned int fm = pow2_split(m, &em), ft = pow2_split(target, &et);
+    S = ldexpf(1.f, min(max(et - em - (ft < fm ? 1 : 0), -60), 60));
   }
   s2[0] = S; s2[1] = 1.f / S;
 }
