@@ -154,6 +154,69 @@ int t2p_sampler_run(t2p_sampler* s, float* x, float* out, int prior_given, int n
  * on `stream` (not the default stream) and discarded, nothing executes; call after at least one eager step */
 int t2p_sampler_count_dispatches(t2p_sampler* s, float* x, float* x_mean, void* stream, int* n_out);
 
+/* ---- DDIM sampler with classifier-free guidance ---------------------------------------------------
+ * The reference's second sampler for the same network (sampler/diffusion_sampler.py, twin model/diffusion_sampler.py): a strided
+ * DDIM loop over a VP-trained noise predictor, guided on the text embedding, with static clipping of the predicted clean sample.
+ * t2p_ddim_create        <- DiffusionSampler.__init__ + the schedule of ddim_sample        (diffusion_sampler.py:13-64, 87-89)
+ * t2p_ddim_set_context   <- `cond` and `cond * 0`                                          (:128)
+ * t2p_ddim_step          <- one iteration of the loop body                                 (:94-112, 116-142)
+ * t2p_ddim_run           <- ddim_sample(shape, cond)                                       (:72-114)
+ * Guidance costs ONE evaluation per step: the context is [ctx ; 0] at batch 2B (to_k / to_v have no bias, so the zero half gives
+ * zero keys and values, as `cond * 0` does) and the network runs on [x ; x].  With w == 1 the zero-context half is skipped
+ * (batch B): 1 a + 0 b == a for finite b -- the one place the evaluation count differs from the reference, which evaluates both. */
+typedef struct t2p_ddim_config {
+  int32_t timesteps;        /* length of the beta schedule; labels are < timesteps <= model.num_scales   */
+  int32_t sampling_steps;   /* rows of the step table                                                     */
+  double eta;               /* ddim_eta in [0, 1]                                                         */
+  double w;                 /* guidance weight: eps = w eps(ctx) + (1 - w) eps(0)                         */
+  int32_t clip;             /* 1 = clamp the predicted clean sample to [-1, 1] ('static'), 0 = 'dynamic' */
+  int32_t batch;            /* chains B                                                                   */
+  uint64_t seed;            /* on-device Philox noise: draw 0 is the prior, draw k + 1 belongs to step k  */
+} t2p_ddim_config;
+/* one loop step (t, t_next) of ddim_sample, in the reference's float32 arithmetic: t the time label; sqrt_recip / sqrt_recipm1 =
+ * sqrt_recip(m1)_alphas_cumprod[t]; sqrt_an = sqrt(alphas_cumprod[t_next]); c, sigma as :105-106; last = (t_next < 0): the step
+ * returns the clean sample and reads no noise (the other three are then ignored) */
+typedef struct t2p_ddim_step_row {
+  int32_t t;
+  float sqrt_recip, sqrt_recipm1, sqrt_an, c, sigma;
+  int32_t last;
+} t2p_ddim_step_row;
+typedef struct t2p_ddim t2p_ddim;
+/* table: host rows [cfg->sampling_steps], copied.  Refused with nothing created: an engine that is not finalized, eta outside
+ * [0, 1], sampling_steps < 1, a label outside [0, num_scales), timesteps outside [1, num_scales], batch < 1. */
+int t2p_ddim_create(t2p_engine* e, const t2p_ddim_config* cfg, const t2p_ddim_step_row* table, t2p_ddim** out);
+void t2p_ddim_destroy(t2p_ddim* d);
+int t2p_ddim_set_seed(t2p_ddim* d, uint64_t seed);
+/* mask: device uint8 (B,C,L,L), 1 where the chain evolves; x_initial: device fp32; both NULL = unconditional.  Frozen entries are
+ * re-imposed by every update (an extension: the reference's DDIM loop takes no condition).  The pointers are borrowed. */
+int t2p_ddim_set_condition(t2p_ddim* d, const uint8_t* mask, const float* x_initial);
+/* context: device fp32 [batch][tokens][context_dim]; builds [ctx ; 0] on the device and projects it through the engine
+ * (t2p_engine_set_context at batch 2B; at batch B when w == 1).  batch != cfg.batch is refused, nothing changes. */
+int t2p_ddim_set_context(t2p_ddim* d, const float* context, int batch, int tokens, void* stream);
+/* the next t2p_ddim_step is loop step `step` (0 at the start of a run) on a fresh x; a step outside the table is refused */
+int t2p_ddim_reset(t2p_ddim* d, int step, void* stream);
+/* One DDIM step at the current step index, in place on x (device fp32; the state is its first (B,C,L,L) block).  With w != 1, x
+ * must have room for 2B samples: the second block is the engine's copy of the first (the [x ; x] input), written by the first step
+ * after t2p_ddim_reset and by every update.  x0_out (optional): device fp32 (B,C,L,L), the clipped clean-sample prediction.
+ * noise: device standard-normal draws (parity runs) or NULL = drawn inside the update kernel.  Enqueues on `stream` only: no host
+ * synchronisation, copy or allocation once the first step has sized the engine's activation pool.  A step beyond the table is
+ * refused and x is left unchanged. */
+int t2p_ddim_step(t2p_ddim* d, float* x, float* x0_out, const float* noise, void* stream);
+/* Full run: x (sized as for t2p_ddim_step) holds the already conditioned prior when `prior_given`, else it is drawn on the device
+ * (randn, then the mask); n_steps <= 0 = the whole table.  out: device fp32 (B,C,L,L), may be x. */
+int t2p_ddim_run(t2p_ddim* d, float* x, float* out, int prior_given, int n_steps, void* stream);
+/* The update of one DDIM step as an operator over n elements, every scalar by value:
+ *   eps = w eps_c + w1 eps_u   (eps_u NULL: eps = eps_c; w1 = (float)(1 - w) as the reference rounds it)
+ *   x0 = sqrt_recip x - sqrt_recipm1 eps, clamped to [-1, 1] when clip;   x_next = last ? x0 : x0 sqrt_an + c eps + sigma z
+ *   x_next = mask ? x_next : x_initial
+ * each product and sum rounded to float32 in this order.  z NULL = drawn in the kernel, equal to t2p_op_philox_normal(seed,
+ * stream_id) bit for bit (nothing is drawn when sigma == 0); no z is read or drawn when last.  x_out may alias x; x_out2
+ * (optional) receives a second copy of x_next, x0_out (optional) the clean-sample prediction. */
+int t2p_op_ddim_update(const float* x, const float* eps_c, const float* eps_u, const float* z, const uint8_t* mask,
+                       const float* x_initial, float* x_out, float* x_out2, float* x0_out, int64_t n, float w, float w1,
+                       float sqrt_recip, float sqrt_recipm1, float sqrt_an, float c, float sigma, int clip, int last,
+                       uint64_t seed, uint64_t stream_id, void* stream);
+
 /* ---- training step ---------------------------------------------------------------
  * model->compute_dtype selects the products: T2P_DTYPE_F32 exact f32; T2P_DTYPE_F16 / T2P_DTYPE_BF16 16-bit operands with fp32
  * accumulation (residual-block 3x3 convolutions on the 16-bit implicit GEMM, every other product on t2p_op_tgemm16; input / head

@@ -26,6 +26,10 @@ Differences, all at the edges of the hot path:
     ``get_condition_from_batch`` does (utils.py:84-106).  ``--mask_info`` without either source is an error.
   * ``checkpoint`` may be the word ``synthetic`` (hash-generated weights, no file needed).
   * extra flags: --dtype (f32|f16|bf16), --seed, --ids, --num_scales / --max_res_num overrides.
+  * ``--sampler ddim [--ddim_steps 50] [--ddim_eta 1.0] [--guidance_w 0.0]``: the reference's other sampler for the same network
+    (sampler/diffusion_sampler.py: strided DDIM with classifier-free guidance on the text context) instead of the
+    predictor-corrector loop.  It reads the network output as a noise prediction, so the config must say ``training.sde: vpsde``.
+    The conditions and the output files are the same.
 Under ``python -m torch.distributed.run --nproc-per-node N`` (or with ``--gpus N``, which starts the N ranks
 itself) every rank samples ``--batch_size`` chains on its own GPU and rank 0 gathers them with one RCCL
 all_gather before writing (text2protein_amd/distributed.py).  ``--global_batch_norm`` reproduces the reference's
@@ -81,6 +85,13 @@ def main():
     parser.add_argument("--gpus", type=int, default=1, help="start this many ranks (one per GPU) when not under torch.distributed.run")
     parser.add_argument("--global_batch_norm", action="store_true",
                         help="Langevin batch means over every rank's chains (the reference's DataParallel semantics)")
+    parser.add_argument("--sampler", type=str, default="pc", choices=["pc", "ddim"],
+                        help="pc: the predictor-corrector SDE loop (default); ddim: strided DDIM with classifier-free guidance "
+                             "(needs training.sde: vpsde)")
+    parser.add_argument("--ddim_steps", type=int, default=50, help="--sampler ddim: loop steps (sampling_steps)")
+    parser.add_argument("--ddim_eta", type=float, default=1.0, help="--sampler ddim: eta in [0, 1] (0 = deterministic)")
+    parser.add_argument("--guidance_w", type=float, default=0.0,
+                        help="--sampler ddim: eps = w eps(text) + (1 - w) eps(no text); the reference's default is 0")
     args = parser.parse_args()
 
     assert not (args.pdb is not None and args.select_length)
@@ -110,6 +121,9 @@ def main():
     if args.max_res_num:
         overrides["data.max_res_num"] = args.max_res_num
     config = load_config(args.config, **overrides)
+    if args.sampler == "ddim" and config.training.sde != "vpsde":      # before anything touches a device
+        raise SystemExit(f"--sampler ddim needs a noise-prediction network: training.sde must be vpsde, {args.config} says "
+                         f"{config.training.sde} (a VE-trained output is a score, not a noise prediction)")
     device = f"cuda:{local_rank}" if args.device == "cuda" else args.device
     config.device = device
     torch.cuda.set_device(torch.device(device))
@@ -156,7 +170,19 @@ def main():
     if args.global_batch_norm and dist is not None:
         kw = {"global_batch": B * world, "all_reduce": lambda sums: D.allreduce_norm_sums(sums, dist)}
     # every rank its own noise stream; every iteration of the --n_iter loop a fresh one (call index, sampling.py)
-    sampling_fn = sampling.get_sampling_fn(config, sde, sampling_shape, sampling_eps, seed=D.rank_seed(args.seed, rank), **kw)
+    if args.sampler == "ddim":
+        from text2protein_amd.ddim import DiffusionSampler
+        try:
+            ddim = DiffusionSampler.from_sde(score_model, sde, sampling_steps=args.ddim_steps, ddim_eta=args.ddim_eta,
+                                             w=args.guidance_w, seed=D.rank_seed(args.seed, rank))
+        except T2PError as e:
+            raise SystemExit(f"--sampler ddim: {e}")
+        evaluations = args.ddim_steps * (1 if args.guidance_w == 1.0 else 2)
+
+        def sampling_fn(model, condition=None, context=None):
+            return ddim.ddim_sample(sampling_shape, context, condition=condition), evaluations
+    else:
+        sampling_fn = sampling.get_sampling_fn(config, sde, sampling_shape, sampling_eps, seed=D.rank_seed(args.seed, rank), **kw)
 
     caption_ids = None
     if args.captions:

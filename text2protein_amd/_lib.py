@@ -35,6 +35,16 @@ class SamplerConfig(C.Structure):
                 ("seed", C.c_uint64)]
 
 
+class DdimConfig(C.Structure):           # t2p_ddim_config
+    _fields_ = [("timesteps", C.c_int32), ("sampling_steps", C.c_int32), ("eta", C.c_double), ("w", C.c_double),
+                ("clip", C.c_int32), ("batch", C.c_int32), ("seed", C.c_uint64)]
+
+
+class DdimStepRow(C.Structure):          # t2p_ddim_step_row
+    _fields_ = [("t", C.c_int32), ("sqrt_recip", C.c_float), ("sqrt_recipm1", C.c_float), ("sqrt_an", C.c_float),
+                ("c", C.c_float), ("sigma", C.c_float), ("last", C.c_int32)]
+
+
 class TrainConfig(C.Structure):          # t2p_train_config
     _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
                 ("warmup", C.c_double), ("grad_clip", C.c_double), ("ema_rate", C.c_double), ("dropout", C.c_double),
@@ -75,6 +85,16 @@ SIGNATURES = {
     "t2p_sampler_run": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "t2p_sampler_set_vp_tables": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "t2p_sampler_count_dispatches": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int)]),
+    # DDIM sampler with classifier-free guidance (csrc/ddim.hip)
+    "t2p_ddim_create": (_i, [_vp, C.POINTER(DdimConfig), C.POINTER(DdimStepRow), C.POINTER(_vp)]),
+    "t2p_ddim_destroy": (None, [_vp]),
+    "t2p_ddim_set_seed": (_i, [_vp, _u64]),
+    "t2p_ddim_set_condition": (_i, [_vp, _vp, _vp]),
+    "t2p_ddim_set_context": (_i, [_vp, _vp, _i, _i, _vp]),
+    "t2p_ddim_reset": (_i, [_vp, _i, _vp]),
+    "t2p_ddim_step": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "t2p_ddim_run": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "t2p_op_ddim_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _f, _f, _i, _i, _u64, _u64, _vp]),
     "t2p_op_gemm": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _vp, _vp, _f, _vp]),
     "t2p_op_conv3x3_shortcut": (_i, [_i, _vp, _vp, _vp, _vp, _i, _vp, _i, _f, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "t2p_op_conv3x3_groupnorm": (_i, [_i, _vp, _vp, _vp, _vp, _vp, C.c_float, _i, _i, _vp, _vp, C.c_float, _i, _vp, _i, _vp, _vp,

@@ -1,6 +1,7 @@
 // extern "C" surface of libt2p_hip.so (declarations and reference citations: include/t2p.h).
 #include <new>
 
+#include "ddim.h"
 #include "engine.h"
 #include "train.h"   // g_train_plumbing16 (plan switch 48)
 
@@ -184,6 +185,82 @@ int t2p_sampler_run(t2p_sampler* s, float* x, float* out, int prior_given, int n
   API_BEGIN
   T2P_REQUIRE(s, "null sampler");
   return s->impl.run(x, out, prior_given, n_steps, (hipStream_t)stream);
+  API_END
+}
+
+// ---- DDIM sampler (ddim.hip) ----------------------------------------------------------------------
+int t2p_ddim_create(t2p_engine* e, const t2p_ddim_config* cfg, const t2p_ddim_step_row* table, t2p_ddim** out) {
+  API_BEGIN
+  T2P_REQUIRE(e && cfg && out, "null argument");
+  t2p_ddim* d = new t2p_ddim(&e->impl, *cfg);
+  int rc = d->impl.init(table);
+  if (rc != T2P_OK) {
+    delete d;
+    return rc;
+  }
+  *out = d;
+  return T2P_OK;
+  API_END
+}
+
+void t2p_ddim_destroy(t2p_ddim* d) { delete d; }
+
+int t2p_ddim_set_seed(t2p_ddim* d, uint64_t seed) {
+  API_BEGIN
+  T2P_REQUIRE(d, "null ddim sampler");
+  d->impl.set_seed(seed);
+  return T2P_OK;
+  API_END
+}
+
+int t2p_ddim_set_condition(t2p_ddim* d, const uint8_t* mask, const float* x_initial) {
+  API_BEGIN
+  T2P_REQUIRE(d, "null ddim sampler");
+  T2P_REQUIRE((mask == nullptr) == (x_initial == nullptr), "mask and x_initial go together");
+  return d->impl.set_condition(mask, x_initial);
+  API_END
+}
+
+int t2p_ddim_set_context(t2p_ddim* d, const float* context, int batch, int tokens, void* stream) {
+  API_BEGIN
+  T2P_REQUIRE(d, "null ddim sampler");
+  return d->impl.set_context(context, batch, tokens, (hipStream_t)stream);
+  API_END
+}
+
+int t2p_ddim_reset(t2p_ddim* d, int step, void* stream) {
+  API_BEGIN
+  T2P_REQUIRE(d, "null ddim sampler");
+  (void)stream;          // the step index lives on the host: nothing to enqueue
+  return d->impl.reset(step);
+  API_END
+}
+
+int t2p_ddim_step(t2p_ddim* d, float* x, float* x0_out, const float* noise, void* stream) {
+  API_BEGIN
+  T2P_REQUIRE(d, "null ddim sampler");
+  return d->impl.step(x, x0_out, noise, (hipStream_t)stream);
+  API_END
+}
+
+int t2p_ddim_run(t2p_ddim* d, float* x, float* out, int prior_given, int n_steps, void* stream) {
+  API_BEGIN
+  T2P_REQUIRE(d, "null ddim sampler");
+  return d->impl.run(x, out, prior_given, n_steps, (hipStream_t)stream);
+  API_END
+}
+
+int t2p_op_ddim_update(const float* x, const float* eps_c, const float* eps_u, const float* z, const uint8_t* mask,
+                       const float* x_initial, float* x_out, float* x_out2, float* x0_out, int64_t n, float w, float w1,
+                       float sqrt_recip, float sqrt_recipm1, float sqrt_an, float c, float sigma, int clip, int last,
+                       uint64_t seed, uint64_t stream_id, void* stream) {
+  API_BEGIN
+  DdimUpdateArgs a;
+  a.x = x; a.eps_c = eps_c; a.eps_u = eps_u; a.z = z; a.mask = mask; a.x_initial = x_initial;
+  a.x_out = x_out; a.x_out2 = x_out2; a.x0_out = x0_out; a.n = n; a.w = w; a.w1 = w1;
+  a.sqrt_recip = sqrt_recip; a.sqrt_recipm1 = sqrt_recipm1; a.sqrt_an = sqrt_an; a.c = c; a.sigma = sigma;
+  a.clip = clip; a.last = last; a.seed = seed; a.stream_id = stream_id;
+  return launch_ddim_update(a, (hipStream_t)stream);
   API_END
 }
 

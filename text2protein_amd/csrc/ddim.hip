@@ -1,0 +1,253 @@
+// DDIM sampling with classifier-free guidance on the score engine: the strided loop of the reference's second sampler
+// (sampler/diffusion_sampler.py:72-142; twin model/diffusion_sampler.py).  One elementwise kernel per step does the guidance
+// sum, the clean-sample prediction, its static clipping, the DDIM move, the conditional re-masking and the noise draw; the
+// host loop (class Ddim) evaluates the network ONCE per step on [x ; x] under the context [ctx ; 0] at batch 2B.
+#include "ddim.h"
+
+#include <cmath>
+
+namespace t2p {
+
+// ---- Philox4x32-10 + Box-Muller: the draw of philox_normal_kernel (kernels.hip) for quad q of stream `stream`, step word 0.
+// Kept textually the same as there so that the in-kernel noise equals t2p_op_philox_normal(seed, stream) bit for bit.
+__device__ inline void ddim_philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
+  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
+  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+}
+
+__device__ inline void ddim_philox_normal4(long q, unsigned long long seed, unsigned long long stream, float (&z)[4]) {
+  uint32_t c[4] = {(uint32_t)q, (uint32_t)((unsigned long long)q >> 32), (uint32_t)stream, 0u};
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    ddim_philox_round(c, k0, k1);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);   // (0, 1)
+    const float u2 = (float)(c[2 * h + 1] >> 8) * (1.0f / 16777216.0f);         // [0, 1)
+    const float rad = sqrtf(-2.f * logf(u1));
+    float sn, cs;
+    sincosf(6.283185307179586f * u2, &sn, &cs);
+    z[2 * h] = rad * cs;
+    z[2 * h + 1] = rad * sn;
+  }
+}
+
+// one element, rounded where the reference's float32 tensor expressions round (diffusion_sampler.py:128, 141-142, 133, 110-112)
+__device__ inline float ddim_element(const DdimUpdateArgs& a, float x, float ec, float eu, float z, float* x0_out) {
+#pragma clang fp contract(off)
+  float eps = ec;
+  if (a.eps_u) {
+    const float pc = a.w * ec, pu = a.w1 * eu;
+    eps = pc + pu;
+  }
+  const float px = a.sqrt_recip * x, pe = a.sqrt_recipm1 * eps;
+  float x0 = px - pe;
+  if (a.clip) x0 = x0 < -1.f ? -1.f : (x0 > 1.f ? 1.f : x0);     // torch.clamp: a NaN stays a NaN
+  *x0_out = x0;
+  if (a.last) return x0;
+  const float t0 = x0 * a.sqrt_an, t1 = a.c * eps, t2 = a.sigma * z;
+  const float s01 = t0 + t1;
+  return s01 + t2;
+}
+
+// One thread per quad of consecutive elements (the unit of a Philox draw).  VEC: every pointer is 16-byte aligned (the mask
+// 4-byte) and n % 4 == 0, so the quad moves as one 16-byte access per tensor; otherwise element by element, bounded by n.
+template <bool VEC>
+__global__ __launch_bounds__(256) void ddim_update_kernel(DdimUpdateArgs a) {
+  const long nq = (a.n + 3) / 4;
+  const bool mid = !a.last;
+  const bool draw = mid && !a.z && a.sigma != 0.f;     // sigma == 0: the term is sigma * 0, nothing is drawn
+  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
+    const long i = q * 4;
+    const int cnt = VEC ? 4 : (int)(a.n - i < 4 ? a.n - i : 4);
+    alignas(16) float x[4], ec[4], eu[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f}, xi[4] = {0.f, 0.f, 0.f, 0.f};
+    alignas(4) unsigned char m[4] = {1, 1, 1, 1};
+    if (VEC) {
+      *(float4*)x = *(const float4*)(a.x + i);
+      *(float4*)ec = *(const float4*)(a.eps_c + i);
+      if (a.eps_u) *(float4*)eu = *(const float4*)(a.eps_u + i);
+      if (mid && a.z) *(float4*)z = *(const float4*)(a.z + i);
+      if (a.mask) {
+        *(uchar4*)m = *(const uchar4*)(a.mask + i);
+        *(float4*)xi = *(const float4*)(a.x_initial + i);
+      }
+    } else {
+      for (int k = 0; k < cnt; ++k) {
+        x[k] = a.x[i + k];
+        ec[k] = a.eps_c[i + k];
+        if (a.eps_u) eu[k] = a.eps_u[i + k];
+        if (mid && a.z) z[k] = a.z[i + k];
+        if (a.mask) { m[k] = a.mask[i + k]; xi[k] = a.x_initial[i + k]; }
+      }
+    }
+    if (draw) ddim_philox_normal4(q, a.seed, a.stream_id, z);
+    alignas(16) float xn[4], x0[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      xn[k] = ddim_element(a, x[k], ec[k], eu[k], z[k], &x0[k]);
+      if (!m[k]) xn[k] = xi[k];
+    }
+    if (VEC) {
+      *(float4*)(a.x_out + i) = *(const float4*)xn;
+      if (a.x_out2) *(float4*)(a.x_out2 + i) = *(const float4*)xn;
+      if (a.x0_out) *(float4*)(a.x0_out + i) = *(const float4*)x0;
+    } else {
+      for (int k = 0; k < cnt; ++k) {
+        a.x_out[i + k] = xn[k];
+        if (a.x_out2) a.x_out2[i + k] = xn[k];
+        if (a.x0_out) a.x0_out[i + k] = x0[k];
+      }
+    }
+  }
+}
+
+int launch_ddim_update(const DdimUpdateArgs& a, hipStream_t s) {
+  T2P_REQUIRE(a.x && a.eps_c && a.x_out && a.n > 0, "ddim_update arguments");
+  T2P_REQUIRE((a.mask == nullptr) == (a.x_initial == nullptr), "mask and x_initial go together");
+  T2P_REQUIRE(a.clip == 0 || a.clip == 1, "clip is 0 or 1");
+  T2P_REQUIRE(a.last == 0 || a.last == 1, "last is 0 or 1");
+  auto al = [](const void* p, uintptr_t k) { return ((uintptr_t)p % k) == 0; };   // a null pointer counts as aligned
+  const bool vec = a.n % 4 == 0 && al(a.x, 16) && al(a.eps_c, 16) && al(a.eps_u, 16) && al(a.z, 16) && al(a.mask, 4) &&
+                   al(a.x_initial, 16) && al(a.x_out, 16) && al(a.x_out2, 16) && al(a.x0_out, 16);
+  const dim3 grid(ew_grid((a.n + 3) / 4));
+  if (vec) hipLaunchKernelGGL(ddim_update_kernel<true>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(ddim_update_kernel<false>, grid, dim3(256), 0, s, a);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+
+__global__ __launch_bounds__(256) void ddim_mirror_kernel(const float* src, float* d0, float* d1, long n) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const float v = src[i];
+    d0[i] = v;
+    if (d1) d1[i] = v;
+  }
+}
+int launch_ddim_mirror(const float* src, float* d0, float* d1, long n, hipStream_t s) {
+  T2P_REQUIRE(src && d0 && n > 0, "ddim_mirror arguments");
+  hipLaunchKernelGGL(ddim_mirror_kernel, dim3(ew_grid(n)), dim3(256), 0, s, src, d0, d1, n);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+
+__global__ __launch_bounds__(256) void ddim_context2_kernel(const float* ctx, float* out, long n) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    out[i] = ctx[i];
+    out[n + i] = 0.f;
+  }
+}
+int launch_ddim_context2(const float* ctx, float* out, long n, hipStream_t s) {
+  T2P_REQUIRE(ctx && out && n > 0, "ddim_context2 arguments");
+  hipLaunchKernelGGL(ddim_context2_kernel, dim3(ew_grid(n)), dim3(256), 0, s, ctx, out, n);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the loop of DiffusionSampler.ddim_sample (diffusion_sampler.py:87-114) over the step table the Python mirror computed
+Ddim::~Ddim() {
+  (void)hipFree(labels_);
+  (void)hipFree(eps_);
+  (void)hipFree(ctx2_);
+}
+
+int Ddim::init(const t2p_ddim_step_row* table) {
+  T2P_REQUIRE(e_->finalized(), "finalize the engine first");
+  T2P_REQUIRE(table, "null step table");
+  T2P_REQUIRE(cfg_.sampling_steps >= 1, "sampling_steps must be at least 1");
+  T2P_REQUIRE(cfg_.eta >= 0.0 && cfg_.eta <= 1.0, "eta must lie in [0, 1]");       // also refuses a NaN
+  T2P_REQUIRE(std::isfinite(cfg_.w), "the guidance weight must be finite");
+  T2P_REQUIRE(cfg_.timesteps >= 1 && cfg_.timesteps <= e_->cfg().num_scales, "timesteps must lie in [1, model.num_scales]");
+  T2P_REQUIRE(cfg_.batch > 0 && cfg_.batch <= (1 << 20), "batch");
+  T2P_REQUIRE(cfg_.clip == 0 || cfg_.clip == 1, "clip is 0 or 1");
+  const int S = cfg_.sampling_steps, B2 = 2 * cfg_.batch;
+  for (int i = 0; i < S; ++i) {
+    T2P_REQUIRE(table[i].t >= 0 && table[i].t < e_->cfg().num_scales, "time label outside [0, num_scales)");
+    T2P_REQUIRE(table[i].last == 0 || table[i].last == 1, "last is 0 or 1");
+  }
+  table_.assign(table, table + S);
+  const t2p_model_config& m = e_->cfg();
+  n_ = (long)m.num_channels * m.max_res_num * m.max_res_num * cfg_.batch;
+  std::vector<int32_t> lab((size_t)S * B2);
+  for (int i = 0; i < S; ++i) std::fill(lab.begin() + (size_t)i * B2, lab.begin() + (size_t)(i + 1) * B2, table_[i].t);
+  T2P_HIP_CHECK(hipMalloc((void**)&labels_, lab.size() * 4));
+  T2P_HIP_CHECK(hipMalloc((void**)&eps_, (size_t)n_ * 2 * 4));
+  T2P_HIP_CHECK(hipMemcpy(labels_, lab.data(), lab.size() * 4, hipMemcpyHostToDevice));
+  return T2P_OK;
+}
+
+int Ddim::set_context(const float* ctx, int B, int T, hipStream_t s) {
+  T2P_REQUIRE(ctx && T > 0, "set_context arguments");
+  T2P_REQUIRE(B == cfg_.batch, "the context batch must equal cfg.batch");
+  if (!guided()) {          // w == 1: 1 eps_c + 0 eps_u == eps_c, the zero-context half is never evaluated
+    T2P_TRY(e_->set_context(ctx, B, T, s));
+    have_context_ = true;
+    return T2P_OK;
+  }
+  const size_t half = (size_t)B * T * e_->cfg().context_dim;
+  if (2 * half > ctx2_floats_) {
+    float* p = nullptr;
+    T2P_HIP_CHECK(hipMalloc((void**)&p, 2 * half * 4));
+    (void)hipFree(ctx2_);     // (waits for the work that may still read it)
+    ctx2_ = p;
+    ctx2_floats_ = 2 * half;
+  }
+  T2P_TRY(launch_ddim_context2(ctx, ctx2_, (long)half, s));
+  have_context_ = false;      // a failure below leaves the engine's text caches in an unknown state
+  T2P_TRY(e_->set_context(ctx2_, 2 * B, T, s));
+  have_context_ = true;
+  return T2P_OK;
+}
+
+int Ddim::reset(int step) {
+  T2P_REQUIRE(step >= 0 && step < cfg_.sampling_steps, "step out of range");
+  host_step_ = step;
+  mirrored_ = nullptr;
+  return T2P_OK;
+}
+
+int Ddim::step(float* x, float* x0_out, const float* noise, hipStream_t s) {
+  T2P_REQUIRE(x, "x is null");
+  T2P_REQUIRE(have_context_, "call t2p_ddim_set_context first");
+  T2P_REQUIRE(host_step_ >= 0 && host_step_ < cfg_.sampling_steps, "DDIM step index beyond the step table: call t2p_ddim_reset before another run");
+  const t2p_ddim_step_row& r = table_[host_step_];
+  const int B = cfg_.batch;
+  const bool g = guided();
+  if (g && mirrored_ != x) {     // first step on this buffer: the zero-context half of the evaluation reads a copy of x
+    T2P_TRY(launch_ddim_mirror(x, x + n_, nullptr, n_, s));
+    mirrored_ = x;
+  }
+  T2P_TRY(e_->score(x, labels_ + (size_t)host_step_ * 2 * B, nullptr, eps_, g ? 2 * B : B, s));
+  DdimUpdateArgs a;
+  a.x = x; a.eps_c = eps_; a.eps_u = g ? eps_ + n_ : nullptr; a.z = noise; a.mask = mask_; a.x_initial = x_init_;
+  a.x_out = x; a.x_out2 = g ? x + n_ : nullptr; a.x0_out = x0_out; a.n = n_;
+  a.w = (float)cfg_.w; a.w1 = (float)(1.0 - cfg_.w);
+  a.sqrt_recip = r.sqrt_recip; a.sqrt_recipm1 = r.sqrt_recipm1; a.sqrt_an = r.sqrt_an; a.c = r.c; a.sigma = r.sigma;
+  a.clip = cfg_.clip; a.last = r.last;
+  a.seed = cfg_.seed; a.stream_id = (unsigned long long)host_step_ + 1;     // draw 0 is the prior
+  T2P_TRY(launch_ddim_update(a, s));
+  ++host_step_;
+  return T2P_OK;
+}
+
+int Ddim::run(float* x, float* out, int prior_given, int n_steps, hipStream_t s) {
+  T2P_REQUIRE(x && out, "null pointer");
+  T2P_REQUIRE(have_context_, "call t2p_ddim_set_context first");
+  if (n_steps <= 0 || n_steps > cfg_.sampling_steps) n_steps = cfg_.sampling_steps;
+  T2P_TRY(reset(0));
+  if (!prior_given) {            // torch.randn(shape) (diffusion_sampler.py:91), then the condition
+    T2P_TRY(launch_philox_normal(x, n_, cfg_.seed, 0, nullptr, s));
+    if (mask_) T2P_TRY(launch_apply_mask(x, mask_, x_init_, n_, s));
+  }
+  for (int i = 0; i < n_steps; ++i) T2P_TRY(step(x, nullptr, nullptr, s));
+  if (out != x) T2P_TRY(launch_ddim_mirror(x, out, nullptr, n_, s));
+  return T2P_OK;
+}
+
+}  // namespace t2p

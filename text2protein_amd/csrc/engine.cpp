@@ -716,6 +716,7 @@ int Engine::finalize() {
     inv[i] = (float)(1.0 / s);
   }
   T2P_TRY(upload_f32(inv, &inv_sigma_));
+  T2P_TRY(upload_f32(std::vector<float>(N, 1.f), &unit_scale_));
   host_.clear();
   finalized_ = true;
   return T2P_OK;
@@ -1543,13 +1544,8 @@ int Engine::score(const float* x, const int* labels, const int* step_counter, fl
   tb_ = tb;
   tb_ld_ = labels ? arch_.temb_total : 0;
   POOL_GET(scale, float*, (size_t)B * 4);
-  if (cfg_.scale_by_sigma) {
-    T2P_TRY(launch_gather_label(labels, step_counter, inv_sigma_, scale, B, N, s, label_table));
-  } else {
-    std::vector<float> ones(B, 1.f);
-    T2P_HIP_CHECK(hipMemcpyAsync(scale, ones.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
-    T2P_HIP_CHECK(hipStreamSynchronize(s));
-  }
+  // without scale_by_sigma the same gather reads a table of ones: no host copy, nothing for the stream to wait on
+  T2P_TRY(launch_gather_label(labels, step_counter, cfg_.scale_by_sigma ? inv_sigma_ : unit_scale_, scale, B, N, s, label_table));
   const bool hlp = res_lowp() && (Cx == 5 || Cx == 8) && pre_conv_direct_;   // the residual stream starts here
   POOL_GET(h0, float*, (size_t)B * HW * arch_.nf * (hlp ? dtype_size(dtype()) : 4));
   float* h0_stats = nullptr;

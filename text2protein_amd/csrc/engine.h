@@ -139,6 +139,7 @@ class Engine {
   const std::vector<ParamInfo>& params() const { return arch_.params; }
   int load_param(const char* name, const float* data, const int64_t* shape, int ndim);
   int finalize();
+  bool finalized() const { return finalized_; }
   int set_context(const float* ctx, int B, int T, hipStream_t s);
   // labels == nullptr: every row uses *step_counter (device int)
   // label_table (with step_counter): device int[num_scales], the time label of loop step i (fused sampler)
@@ -192,6 +193,7 @@ class Engine {
   float* pre_conv_direct_ = nullptr;   // [nf][9][C] fp32 weights of the direct input convolution
   void* pre_conv_split_ = nullptr;     // the same, each weight as two f16 terms (pre_conv_split_kernel; 16-bit modes)
   float* inv_sigma_ = nullptr;  // [N] fp32, 1 / sigmas[label] (descending sigmas)
+  float* unit_scale_ = nullptr; // [N] fp32 ones: the output scale without scale_by_sigma
   int ctx_B_ = 0, ctx_T_ = 0, ctx_Tpad_ = 0;
   void* splitk_ws_ = nullptr;
   size_t splitk_ws_bytes_ = 0;

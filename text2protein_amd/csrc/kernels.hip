@@ -414,11 +414,6 @@ int launch_gn_apply_cols(const GroupNormApplyArgs& a, hipStream_t s) {
   return T2P_OK;
 }
 
-static inline int ew_grid(long total, int block = 256) {
-  long g = (total + block - 1) / block;
-  return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
-}
-
 int launch_gn_apply(const GroupNormApplyArgs& a, hipStream_t s) {
   const int C = a.C0 + a.C1;
   T2P_REQUIRE(a.x0 && a.stats && a.gamma && a.beta && a.out, "null pointer");

@@ -92,6 +92,12 @@ int launch_timestep_embedding(const int* labels, const float* labels_f, const in
 int launch_small_linear(const float* in, const float* W, const float* bias, float* out, int rows, int K, int N,
                         int silu, hipStream_t s);
 
+// grid of an elementwise launch: one thread per item up to 16384 blocks, grid-stride loops cover the rest
+static inline int ew_grid(long total, int block = 256) {
+  long g = (total + block - 1) / block;
+  return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
+}
+
 // ---- reverse-diffusion predictor + Langevin corrector (sampling.py:157-199) ------------------------
 // sums[0] = sum_b ||grad_b||_2, sums[1] = sum_b ||noise_b||_2  (per-sample norms, summed over b)
 int launch_langevin_norms(const float* grad, const float* noise, int B, long per_sample, float* sq_ws,
