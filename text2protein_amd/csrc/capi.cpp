@@ -3,6 +3,7 @@
 
 #include "ddim.h"
 #include "engine.h"
+#include "sampler.h"
 #include "train.h"   // g_train_plumbing16 (plan switch 48)
 
 using namespace t2p;

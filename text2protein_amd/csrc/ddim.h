@@ -28,8 +28,8 @@ struct DdimUpdateArgs {
   unsigned long long seed = 0, stream_id = 0;
 };
 int launch_ddim_update(const DdimUpdateArgs& a, hipStream_t s);
-// d0[i] = src[i] and, when d1, d1[i] = src[i] (the [x ; x] input of a guided evaluation; the result copy of a run)
-int launch_ddim_mirror(const float* src, float* d0, float* d1, long n, hipStream_t s);
+// dst[i] = src[i] (the second half of the [x ; x] input of a guided evaluation; the result copy of a run)
+int launch_ddim_mirror(const float* src, float* dst, long n, hipStream_t s);
 // out[i] = ctx[i], out[n + i] = 0: the context of a guided evaluation, [ctx ; cond * 0] (diffusion_sampler.py:128)
 int launch_ddim_context2(const float* ctx, float* out, long n, hipStream_t s);
 

@@ -3,40 +3,11 @@
 // sum, the clean-sample prediction, its static clipping, the DDIM move, the conditional re-masking and the noise draw; the
 // host loop (class Ddim) evaluates the network ONCE per step on [x ; x] under the context [ctx ; 0] at batch 2B.
 #include "ddim.h"
+#include "philox.h"
 
 #include <cmath>
 
 namespace t2p {
-
-// ---- Philox4x32-10 + Box-Muller: the draw of philox_normal_kernel (kernels.hip) for quad q of stream `stream`, step word 0.
-// Kept textually the same as there so that the in-kernel noise equals t2p_op_philox_normal(seed, stream) bit for bit.
-__device__ inline void ddim_philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
-  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
-__device__ inline void ddim_philox_normal4(long q, unsigned long long seed, unsigned long long stream, float (&z)[4]) {
-  uint32_t c[4] = {(uint32_t)q, (uint32_t)((unsigned long long)q >> 32), (uint32_t)stream, 0u};
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    ddim_philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);   // (0, 1)
-    const float u2 = (float)(c[2 * h + 1] >> 8) * (1.0f / 16777216.0f);         // [0, 1)
-    const float rad = sqrtf(-2.f * logf(u1));
-    float sn, cs;
-    sincosf(6.283185307179586f * u2, &sn, &cs);
-    z[2 * h] = rad * cs;
-    z[2 * h + 1] = rad * sn;
-  }
-}
 
 // one element, rounded where the reference's float32 tensor expressions round (diffusion_sampler.py:128, 141-142, 133, 110-112)
 __device__ inline float ddim_element(const DdimUpdateArgs& a, float x, float ec, float eu, float z, float* x0_out) {
@@ -86,7 +57,12 @@ __global__ __launch_bounds__(256) void ddim_update_kernel(DdimUpdateArgs a) {
         if (a.mask) { m[k] = a.mask[i + k]; xi[k] = a.x_initial[i + k]; }
       }
     }
-    if (draw) ddim_philox_normal4(q, a.seed, a.stream_id, z);
+    if (draw) {     // the draw of t2p_op_philox_normal(seed, stream_id) for this quad (step word 0)
+      uint32_t c[4];
+      philox_counter_sampling(c, q, a.stream_id, 0u);
+      philox4x32_10(c, a.seed);
+      philox_normal4(c, z);
+    }
     alignas(16) float xn[4], x0[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -122,16 +98,12 @@ int launch_ddim_update(const DdimUpdateArgs& a, hipStream_t s) {
   return T2P_OK;
 }
 
-__global__ __launch_bounds__(256) void ddim_mirror_kernel(const float* src, float* d0, float* d1, long n) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float v = src[i];
-    d0[i] = v;
-    if (d1) d1[i] = v;
-  }
+__global__ __launch_bounds__(256) void ddim_mirror_kernel(const float* src, float* dst, long n) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) dst[i] = src[i];
 }
-int launch_ddim_mirror(const float* src, float* d0, float* d1, long n, hipStream_t s) {
-  T2P_REQUIRE(src && d0 && n > 0, "ddim_mirror arguments");
-  hipLaunchKernelGGL(ddim_mirror_kernel, dim3(ew_grid(n)), dim3(256), 0, s, src, d0, d1, n);
+int launch_ddim_mirror(const float* src, float* dst, long n, hipStream_t s) {
+  T2P_REQUIRE(src && dst && n > 0, "ddim_mirror arguments");
+  hipLaunchKernelGGL(ddim_mirror_kernel, dim3(ew_grid(n)), dim3(256), 0, s, src, dst, n);
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }
@@ -220,7 +192,7 @@ int Ddim::step(float* x, float* x0_out, const float* noise, hipStream_t s) {
   const int B = cfg_.batch;
   const bool g = guided();
   if (g && mirrored_ != x) {     // first step on this buffer: the zero-context half of the evaluation reads a copy of x
-    T2P_TRY(launch_ddim_mirror(x, x + n_, nullptr, n_, s));
+    T2P_TRY(launch_ddim_mirror(x, x + n_, n_, s));
     mirrored_ = x;
   }
   T2P_TRY(e_->score(x, labels_ + (size_t)host_step_ * 2 * B, nullptr, eps_, g ? 2 * B : B, s));
@@ -246,7 +218,7 @@ int Ddim::run(float* x, float* out, int prior_given, int n_steps, hipStream_t s)
     if (mask_) T2P_TRY(launch_apply_mask(x, mask_, x_init_, n_, s));
   }
   for (int i = 0; i < n_steps; ++i) T2P_TRY(step(x, nullptr, nullptr, s));
-  if (out != x) T2P_TRY(launch_ddim_mirror(x, out, nullptr, n_, s));
+  if (out != x) T2P_TRY(launch_ddim_mirror(x, out, n_, s));
   return T2P_OK;
 }
 

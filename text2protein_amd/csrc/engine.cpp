@@ -1,8 +1,6 @@
-// Host side of the score network (reference UNetModel, ncsnpp.py:71-263) and of the
-// predictor-corrector loop (sampling.py:245-289): builds the layer table from the flat config,
+// Host side of the score network (reference UNetModel, ncsnpp.py:71-263): builds the layer table from the flat config,
 // prepares weights (layout + dtype), and enqueues the HIP kernels of one evaluation on a stream.
-// No host synchronisation happens inside score()/step(): the Langevin step size is computed on
-// the device from device-side norm sums.
+// No host synchronisation happens inside score().
 #include "engine.h"
 
 #include <algorithm>
@@ -11,7 +9,6 @@
 #include <cstring>
 #include <map>
 #include <mutex>
-#include <set>
 #include <thread>
 
 namespace t2p {
@@ -1640,223 +1637,6 @@ int Engine::score(const float* x, const int* labels, const int* step_counter, fl
   pool_.put(scale);
   pool_.put(tb);
   tb_ = nullptr;
-  return T2P_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-Sampler::Sampler(Engine* e, const t2p_sampler_config& cfg) : e_(e), cfg_(cfg) {}
-
-int Sampler::init(const float* g_table_host, const int32_t* label_table_host) {
-  T2P_REQUIRE(cfg_.sde == T2P_SDE_VE || cfg_.sde == T2P_SDE_VP, "the fused sampler covers the VE and VP SDEs");
-  T2P_REQUIRE(cfg_.sde == T2P_SDE_VE || (g_table_host && label_table_host), "the VP SDE needs its G and label tables (t2p_sampler_create) and t2p_sampler_set_vp_tables");
-  T2P_REQUIRE(cfg_.N == e_->cfg().num_scales, "sde.N must equal model.num_scales");
-  T2P_REQUIRE(cfg_.batch > 0 && cfg_.global_batch >= cfg_.batch && cfg_.n_steps_each >= 1, "sampler config");
-  T2P_REQUIRE(cfg_.eps >= 0.0 && cfg_.eps < 1.0, "eps must lie in [0, T)");
-  const int N = cfg_.N;
-  // time label of loop step i: round((T - t_i) (N - 1)) with t = linspace(T, eps, N) (sampling.py:257,
-  // models/utils.py:159-171); equals i only for tiny eps, e.g. 499 of 1000 labels differ at eps = 1e-3
-  std::vector<int32_t> lab(N);
-  if (label_table_host) {
-    std::copy(label_table_host, label_table_host + N, lab.begin());
-  } else {
-    for (int i = 0; i < N; ++i) {
-      const double t = 1.0 + (cfg_.eps - 1.0) * (double)i / (double)(N - 1);
-      lab[i] = (int32_t)std::nearbyint((1.0 - t) * (double)(N - 1));
-    }
-  }
-  for (int i = 0; i < N; ++i) T2P_REQUIRE(lab[i] >= 0 && lab[i] < N, "time label out of range");
-  std::vector<float> g(N);
-  if (g_table_host) {
-    std::copy(g_table_host, g_table_host + N, g.begin());
-  } else {
-    // VESDE.discretize (sde_lib.py:237-245): step i uses k = N-1-i on the ascending sigmas
-    const double a = std::log(cfg_.sigma_min), b = std::log(cfg_.sigma_max);
-    auto sig = [&](int k) { return (double)(float)std::exp(a + (b - a) * (double)k / (double)(N - 1)); };
-    for (int i = 0; i < N; ++i) {
-      const int k = N - 1 - i;
-      const double sk = sig(k), sp = k == 0 ? 0.0 : sig(k - 1);
-      g[i] = (float)std::sqrt(sk * sk - sp * sp);
-    }
-  }
-  DevPool& pool = e_->pool();
-  g_table_ = (float*)pool.persistent((size_t)N * 4);
-  label_table_ = (int*)pool.persistent((size_t)N * 4);
-  step_dev_ = (int*)pool.persistent(256);
-  const t2p_model_config& m = e_->cfg();
-  per_sample_ = (long)m.num_channels * m.max_res_num * m.max_res_num;
-  n_ = per_sample_ * cfg_.batch;
-  score_ = (float*)pool.persistent((size_t)n_ * 4);
-  noise_ = (float*)pool.persistent((size_t)n_ * 4);
-  xmean_ = (float*)pool.persistent((size_t)n_ * 4);
-  sq_ws_ = (float*)pool.persistent((size_t)cfg_.batch * 64 * 2 * 4);
-  sums_ = (float*)pool.persistent(256);
-  if (!g_table_ || !label_table_ || !step_dev_ || !score_ || !noise_ || !xmean_ || !sq_ws_ || !sums_) return T2P_ERR_HIP;
-  T2P_HIP_CHECK(hipMemcpy(g_table_, g.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-  T2P_HIP_CHECK(hipMemcpy(label_table_, lab.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-  T2P_HIP_CHECK(hipMemset(step_dev_, 0, 256));
-  return T2P_OK;
-}
-
-int Sampler::reset(int step, hipStream_t s) {
-  T2P_REQUIRE(step >= 0 && step < cfg_.N, "step out of range");
-  T2P_HIP_CHECK(hipMemcpyAsync(step_dev_, &step, sizeof(int), hipMemcpyHostToDevice, s));
-  T2P_HIP_CHECK(hipStreamSynchronize(s));
-  host_step_ = step;
-  return T2P_OK;
-}
-
-int Sampler::set_vp_tables(const float* label_f, const float* score_scale, const float* x_coef, const float* corr_alpha) {
-  T2P_REQUIRE(cfg_.sde == T2P_SDE_VP, "VP tables belong to a sampler created with sde = T2P_SDE_VP");
-  T2P_REQUIRE(label_f && score_scale && x_coef && corr_alpha, "null table");
-  DevPool& pool = e_->pool();
-  const size_t bytes = (size_t)cfg_.N * 4;
-  float** dst[4] = {&vp_label_f_, &vp_score_scale_, &vp_x_coef_, &vp_alpha_};
-  const float* src[4] = {label_f, score_scale, x_coef, corr_alpha};
-  for (int i = 0; i < 4; ++i) {
-    if (!*dst[i]) *dst[i] = (float*)pool.persistent(bytes);
-    if (!*dst[i]) return T2P_ERR_HIP;
-    T2P_HIP_CHECK(hipMemcpy(*dst[i], src[i], bytes, hipMemcpyHostToDevice));
-  }
-  return T2P_OK;
-}
-
-int Sampler::set_norm_allreduce(float* sums, t2p_allreduce_fn fn, void* user) {
-  T2P_REQUIRE((sums == nullptr) == (fn == nullptr), "the sums buffer and the all-reduce callback go together");
-  sums_ext_ = sums; allreduce_ = fn; allreduce_user_ = user;
-  return T2P_OK;
-}
-
-// one iteration of the loop body of pc_sampler (sampling.py:279-285)
-int Sampler::step(float* x, float* x_mean, const float* nc, const float* np, hipStream_t s) {
-  T2P_REQUIRE(x, "x is null");
-  T2P_REQUIRE(cfg_.n_steps_each == 1 || !nc, "injected corrector noise supports n_steps_each == 1");
-  // the schedule tables hold N entries: a step past the end of the run is a caller error (t2p_sampler_reset rewinds)
-  T2P_REQUIRE(host_step_ >= 0 && host_step_ < cfg_.N, "PC step index beyond sde.N: call t2p_sampler_reset before another run");
-  // Langevin batch mean over global_batch chains (reference DataParallel run): needs the norm sums of the other
-  // processes, i.e. the all-reduce hook; without it the mean runs over this process's chains
-  T2P_REQUIRE(cfg_.global_batch == cfg_.batch || allreduce_, "global_batch > batch needs t2p_sampler_set_norm_allreduce");
-  {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (s) (void)hipStreamIsCapturing(s, &cap);
-    if (cap == hipStreamCaptureStatusNone && eager_steps_ < (1 << 30)) ++eager_steps_;     // steps that really ran (step_graph / count_dispatches ask)
-  }
-  const int B = cfg_.batch;
-  const bool vp = cfg_.sde == T2P_SDE_VP;
-  T2P_REQUIRE(!vp || vp_label_f_, "VP SDE: call t2p_sampler_set_vp_tables first");
-  float* sums = allreduce_ ? sums_ext_ : sums_;
-  // score function (models/utils.py:138-171): VE = the network output at the integer label; VP = -output / std at the fractional one
-  auto score_fn = [&]() -> int {
-    T2P_TRY(e_->score(x, nullptr, step_dev_, score_, B, s, nullptr, label_table_, vp ? vp_label_f_ : nullptr));
-    if (vp) T2P_TRY(launch_scale_by_table(score_, n_, vp_score_scale_, step_dev_, cfg_.N, s));
-    return T2P_OK;
-  };
-  for (int k = 0; k < cfg_.n_steps_each; ++k) {
-    T2P_TRY(score_fn());
-    const float* z = nc;
-    if (!z) {
-      T2P_TRY(launch_philox_normal(noise_, n_, cfg_.seed, 2ull * k + 2, step_dev_, s));
-      z = noise_;
-    }
-    T2P_TRY(launch_langevin_norms(score_, z, B, per_sample_, sq_ws_, sums, s));
-    if (allreduce_) {     // sum_b ||grad_b||, sum_b ||noise_b|| over every process's chains (SURVEY 8(e) option B)
-      const int rc = allreduce_(sums, (void*)s, allreduce_user_);
-      if (rc != 0) { set_last_error("the norm all-reduce callback failed with status " + std::to_string(rc)); return T2P_ERR_STATE; }
-    }
-    SdeUpdateArgs a;
-    a.x = x; a.score = score_; a.noise = z; a.mask = mask_; a.x_initial = x_init_; a.x_out = x; a.n = n_;
-    T2P_TRY(launch_langevin_update(a, sums, (float)(allreduce_ ? cfg_.global_batch : B), (float)cfg_.snr, 1.f, s,
-                                   vp ? vp_alpha_ : nullptr, vp ? step_dev_ : nullptr, vp ? cfg_.N : 0));
-  }
-  T2P_TRY(score_fn());
-  const float* z = np;
-  if (!z) {
-    T2P_TRY(launch_philox_normal(noise_, n_, cfg_.seed, 1, step_dev_, s));
-    z = noise_;
-  }
-  SdeUpdateArgs a;
-  a.x = x; a.score = score_; a.noise = z; a.mask = mask_; a.x_initial = x_init_; a.x_out = x;
-  a.x_mean_out = x_mean ? x_mean : xmean_; a.n = n_;
-  T2P_TRY(launch_predictor_update(a, g_table_, step_dev_, 0.f, cfg_.probability_flow, s, cfg_.N, vp ? vp_x_coef_ : nullptr));
-  T2P_TRY(launch_add_int(step_dev_, 1, s));
-  ++host_step_;
-  return T2P_OK;
-}
-
-Sampler::~Sampler() {
-  if (graph_exec_) (void)hipGraphExecDestroy(graph_exec_);
-}
-
-int Sampler::step_graph(float* x, float* x_mean, hipStream_t s) {
-  T2P_REQUIRE(x && x_mean, "step_graph needs explicit x and x_mean buffers");
-  T2P_REQUIRE(!allreduce_, "the captured step does not run the norm all-reduce hook: use t2p_sampler_step");
-  T2P_REQUIRE(host_step_ >= 0 && host_step_ < cfg_.N, "PC step index beyond sde.N: call t2p_sampler_reset before another run");
-  if (eager_steps_ < 1)              // one eager step first: fills the activation pool (no hipMalloc under capture); step() counts it
-    return step(x, x_mean, nullptr, nullptr, s);
-  if (graph_exec_ && (graph_x_ != x || graph_xm_ != x_mean || graph_mask_ != mask_ || graph_seed_ != cfg_.seed)) {
-    (void)hipGraphExecDestroy(graph_exec_);
-    graph_exec_ = nullptr;
-  }
-  if (!graph_exec_) {
-    hipGraph_t graph = nullptr;
-    T2P_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    const int step_before = host_step_;
-    const int rc = step(x, x_mean, nullptr, nullptr, s);
-    host_step_ = step_before;            // the capture enqueued nothing: the replay below is the step
-    const hipError_t ec = hipStreamEndCapture(s, &graph);
-    if (rc != T2P_OK) {                  // a partial capture is dropped, the mirror of the device counter is untouched
-      if (graph) (void)hipGraphDestroy(graph);
-      return rc;
-    }
-    T2P_HIP_CHECK(ec);
-    T2P_HIP_CHECK(hipGraphInstantiate(&graph_exec_, graph, nullptr, nullptr, 0));
-    (void)hipGraphDestroy(graph);
-    graph_x_ = x; graph_xm_ = x_mean; graph_mask_ = mask_; graph_seed_ = cfg_.seed;
-  }
-  T2P_HIP_CHECK(hipGraphLaunch(graph_exec_, s));
-  ++host_step_;
-  return T2P_OK;
-}
-
-// number of kernel / memory nodes one PC step enqueues: the step is captured into a hipGraph (nothing executes) and its nodes
-// are counted.  Needs a non-default stream and a filled activation pool (one eager step before).
-int Sampler::count_dispatches(float* x, float* x_mean, hipStream_t s, int* n_out) {
-  T2P_REQUIRE(x && x_mean && n_out, "null argument");
-  T2P_REQUIRE(eager_steps_ >= 1, "count_dispatches captures a step: run one eager step first (it sizes the pool and builds per-block weight copies)");
-  T2P_REQUIRE(!allreduce_, "the captured step does not run the norm all-reduce hook");
-  T2P_REQUIRE(host_step_ >= 0 && host_step_ < cfg_.N, "PC step index beyond sde.N: call t2p_sampler_reset before another run");
-  hipGraph_t graph = nullptr;
-  T2P_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-  const int step_before = host_step_;
-  const int rc = step(x, x_mean, nullptr, nullptr, s);
-  host_step_ = step_before;
-  const hipError_t ec = hipStreamEndCapture(s, &graph);
-  if (rc != T2P_OK) {
-    if (graph) (void)hipGraphDestroy(graph);
-    return rc;
-  }
-  T2P_HIP_CHECK(ec);
-  size_t n = 0;
-  const hipError_t eg = hipGraphGetNodes(graph, nullptr, &n);
-  (void)hipGraphDestroy(graph);
-  T2P_HIP_CHECK(eg);
-  *n_out = (int)n;
-  return T2P_OK;
-}
-
-int Sampler::run(float* x, float* out, int prior_given, int n_steps, hipStream_t s) {
-  T2P_REQUIRE(x && out, "null pointer");
-  if (n_steps <= 0 || n_steps > cfg_.N) n_steps = cfg_.N;
-  T2P_TRY(reset(0, s));
-  if (!prior_given) {
-    // VESDE.prior_sampling (sde_lib.py:229-230) then where(mask, x, x_initial)
-    T2P_TRY(launch_philox_normal(x, n_, cfg_.seed, 0, nullptr, s));
-    if (cfg_.sde == T2P_SDE_VE) T2P_TRY(launch_scale(x, n_, (float)cfg_.sigma_max, s));     // VP prior: N(0, 1) (sde_lib.py:133-134)
-    if (mask_) T2P_TRY(launch_apply_mask(x, mask_, x_init_, n_, s));
-  }
-  for (int i = 0; i < n_steps; ++i) T2P_TRY(step(x, xmean_, nullptr, nullptr, s));
-  const float* src = cfg_.denoise ? xmean_ : x;
-  T2P_HIP_CHECK(hipMemcpyAsync(out, src, (size_t)n_ * 4, hipMemcpyDeviceToDevice, s));
-  if (cfg_.denoise && mask_) T2P_TRY(launch_apply_mask(out, mask_, x_init_, n_, s));   // sampling.py:287
   return T2P_OK;
 }
 

@@ -1,6 +1,7 @@
 // HBM-bound kernels of the score network and the SDE update (gfx950).
 // All activations are NHWC ([batch][pixel][channel], channel contiguous) so that 64-lane
 // wavefronts read 16-byte vectors of consecutive channels (coalesced 1 KiB per wave-instruction).
+#include "philox.h"
 #include "t2p_kernels.h"
 
 namespace t2p {
@@ -1511,38 +1512,17 @@ int launch_scale_by_table(float* x, long n, const float* table, const int* step_
   return T2P_OK;
 }
 
-// ---- Philox4x32-10 + Box-Muller -------------------------------------------------------------------------------
-__device__ inline void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
-  const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-
+// ---- standard normals: Philox4x32-10 + Box-Muller (philox.h), sampling layout ----------------------------------
 __global__ __launch_bounds__(256) void philox_normal_kernel(float* out, long n, unsigned long long seed, unsigned long long stream,
                                                             const int* step_counter) {
   const uint32_t step = step_counter ? (uint32_t)*step_counter : 0u;
   const long nq = (n + 3) / 4;
   for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
-    uint32_t c[4] = {(uint32_t)q, (uint32_t)((unsigned long long)q >> 32), (uint32_t)stream, step};
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-      philox_round(c, k0, k1);
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
+    uint32_t c[4];
+    philox_counter_sampling(c, q, stream, step);
+    philox4x32_10(c, seed);
     float z[4];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const float u1 = ((float)(c[2 * h] >> 8) + 0.5f) * (1.0f / 16777216.0f);   // (0, 1)
-      const float u2 = (float)(c[2 * h + 1] >> 8) * (1.0f / 16777216.0f);         // [0, 1)
-      const float rad = sqrtf(-2.f * logf(u1));
-      float sn, cs;
-      sincosf(6.283185307179586f * u2, &sn, &cs);
-      z[2 * h] = rad * cs;
-      z[2 * h + 1] = rad * sn;
-    }
+    philox_normal4(c, z);
     const long i = q * 4;
     if (i + 3 < n) {
       *(float4*)(out + i) = make_float4(z[0], z[1], z[2], z[3]);

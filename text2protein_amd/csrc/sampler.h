@@ -1,0 +1,60 @@
+// Predictor-corrector sampling (score_sde_pytorch/sampling.py:213-291): the fused host-side loop over a finalized Engine; its noise streams: philox.h.
+#pragma once
+#include "engine.h"
+
+namespace t2p {
+
+class Sampler {
+ public:
+  Sampler(Engine* e, const t2p_sampler_config& cfg);
+  int init(const float* g_table_host, const int32_t* label_table_host);
+  int set_condition(const uint8_t* mask, const float* x_initial) { mask_ = mask; x_init_ = x_initial; return T2P_OK; }
+  void set_seed(uint64_t seed) { cfg_.seed = seed; }
+  // global-batch Langevin step size (reference under DataParallel, sampling.py:193-195): `sums` is a caller-owned
+  // device float[2] the norm sums of this process's chains are written to; `fn` must sum it over all processes
+  // in stream order before returning control (e.g. one RCCL all_reduce enqueued on `stream`)
+  int set_norm_allreduce(float* sums, t2p_allreduce_fn fn, void* user);
+  // VP SDE (sde_lib.py:106-157) in the fused loop: per-step host tables of N floats (see t2p_sampler_set_vp_tables)
+  int set_vp_tables(const float* label_f, const float* score_scale, const float* x_coef, const float* corr_alpha);
+  int reset(int step, hipStream_t s);
+  int step(float* x, float* x_mean, const float* nc, const float* np, hipStream_t s);
+  // step() through a captured hipGraph (device noise only): first call with a given (x, x_mean,
+  // condition) captures, later calls replay.  The step reads its index from the device counter.
+  int step_graph(float* x, float* x_mean, hipStream_t s);
+  int run(float* x, float* out, int prior_given, int n_steps, hipStream_t s);
+  int count_dispatches(float* x, float* x_mean, hipStream_t s, int* n_out);
+  ~Sampler();
+
+ private:
+  Engine* e_;
+  t2p_sampler_config cfg_;
+  const uint8_t* mask_ = nullptr;
+  const float* x_init_ = nullptr;
+  int* step_dev_ = nullptr;
+  float* g_table_ = nullptr;
+  float* score_ = nullptr;
+  float* noise_ = nullptr;
+  float* sq_ws_ = nullptr;
+  float* sums_ = nullptr;
+  float* xmean_ = nullptr;
+  int* label_table_ = nullptr;     // device int[N]: time label of loop step i
+  float* vp_label_f_ = nullptr;    // VP: device float[N] each
+  float* vp_score_scale_ = nullptr;
+  float* vp_x_coef_ = nullptr;
+  float* vp_alpha_ = nullptr;
+  int host_step_ = 0;              // host mirror of *step_dev_ (bounds check: the tables have N entries)
+  float* sums_ext_ = nullptr;
+  t2p_allreduce_fn allreduce_ = nullptr;
+  void* allreduce_user_ = nullptr;
+  uint64_t graph_seed_ = 0;
+  long n_ = 0, per_sample_ = 0;
+  hipGraphExec_t graph_exec_ = nullptr;
+  float* graph_x_ = nullptr;
+  float* graph_xm_ = nullptr;
+  const uint8_t* graph_mask_ = nullptr;
+  int eager_steps_ = 0;
+};
+
+}  // namespace t2p
+
+struct t2p_sampler { t2p::Sampler impl; t2p_sampler(t2p::Engine* e, const t2p_sampler_config& c) : impl(e, c) {} };

@@ -86,9 +86,7 @@ class Trainer {
   int conv_gemm(const float* x, int B, int H, int W, int Cin, const float* w, const void* w16, long ldb, const float* bias,
                 const float* bias_bn, int N, float* y, long ldc, const float* residual_inplace);
   // Philox stream ids of the running loss call, all under the key tc_.seed: the diffusion times t, the noise z and the dropout mask of
-  // residual block k.  Known defect, kept as it is here (the RNG stream bookkeeping of the training step): the three families overlap -- t of
-  // call 4096 n + 1 is z's stream of call n, t of call 4096 n + 16 + k is block k's mask stream of call n -- and z's id wraps at
-  // 2^20 calls in the 32-bit stream word of the normal generator.
+  // residual block k.  philox.h tabulates them with their counter layouts and records the two known defects of this numbering, kept as they are.
   unsigned long long rng_t() const { return (unsigned long long)loss_calls_; }
   unsigned long long rng_z() const { return (unsigned long long)(loss_calls_ * 4096 + 1); }
   unsigned long long rng_dropout(int k) const { return (unsigned long long)(loss_calls_ * 4096 + 16 + k); }

@@ -17,6 +17,7 @@
 
 #include <type_traits>
 
+#include "philox.h"
 #include "train_kernels.h"
 
 namespace t2p {
@@ -991,27 +992,17 @@ int launch_dropout(const float* x, const unsigned char* keep, float inv_keep, fl
   return T2P_OK;
 }
 
-__device__ inline void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, const uint32_t k0, const uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
-  c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-}
 __global__ __launch_bounds__(256) void dropout_mask_kernel(unsigned char* __restrict__ keep, const long n, const float p,
                                                            const unsigned long long seed, const unsigned long long stream_id) {
   const long nq = (n + 3) / 4;
   for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
-    uint32_t c0 = (uint32_t)q, c1 = (uint32_t)((unsigned long long)q >> 32), c2 = (uint32_t)stream_id, c3 = (uint32_t)(stream_id >> 32);
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-      philox_round(c0, c1, c2, c3, k0, k1);
-      k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    const uint32_t w[4] = {c0, c1, c2, c3};
+    uint32_t w[4];
+    philox_counter_training(w, q, stream_id);
+    philox4x32_10(w, seed);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const long i = q * 4 + j;
-      if (i < n) keep[i] = ((w[j] >> 8) * (1.0f / 16777216.0f)) >= p ? 1 : 0;
+      if (i < n) keep[i] = philox_uniform24(w[j]) >= p ? 1 : 0;
     }
   }
 }
@@ -1079,14 +1070,14 @@ __device__ inline double block_sum_256_d(double v, double* sh) {
   return r;
 }
 
-__device__ inline void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, const uint32_t k0, const uint32_t k1);
 // t[b]: given, or t = eps + (1 - eps) u with u from Philox keyed by (seed, step), counter = the sample (the same stream for every SDE)
 __device__ inline float dsm_time(const float* __restrict__ t_in, const int b, const float t_eps, const unsigned long long seed,
                                  const unsigned long long step) {
   if (t_in) return t_in[b];
-  uint32_t c0 = (uint32_t)b, c1 = 0, c2 = (uint32_t)step, c3 = (uint32_t)(step >> 32), k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-  for (int r = 0; r < 10; ++r) { philox_round(c0, c1, c2, c3, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-  return (c0 >> 8) * (1.0f / 16777216.0f) * (1.f - t_eps) + t_eps;
+  uint32_t c[4];
+  philox_counter_training(c, b, step);
+  philox4x32_10(c, seed);
+  return philox_uniform24(c[0]) * (1.f - t_eps) + t_eps;
 }
 __global__ void dsm_prepare_kernel(const float* __restrict__ t_in, const int B, const float t_eps, const float sigma_min, const float sigma_max,
                                    const int N, const float* __restrict__ inv_sigma_table, const unsigned long long seed,
@@ -1164,9 +1155,10 @@ __global__ __launch_bounds__(64) void ss_block_rows_kernel(const int* __restrict
   if (drop) {
     d = drop[k] != 0;
   } else {
-    uint32_t c0 = (uint32_t)k, c1 = 0, c2 = (uint32_t)stream_id, c3 = (uint32_t)(stream_id >> 32), k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    for (int r = 0; r < 10; ++r) { philox_round(c0, c1, c2, c3, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-    d = (c0 >> 8) * (1.0f / 16777216.0f) < p;
+    uint32_t c[4];
+    philox_counter_training(c, k, stream_id);
+    philox4x32_10(c, seed);
+    d = philox_uniform24(c[0]) < p;
   }
   if (drop_out && threadIdx.x == 0) drop_out[k] = d ? 1 : 0;
   const int b = blocks[3 * k], start = blocks[3 * k + 1], end = min(blocks[3 * k + 2], L);
