@@ -135,11 +135,24 @@ typedef int (*t2p_allreduce_fn)(float* device_sums2, void* stream, void* user);
 int t2p_sampler_set_norm_allreduce(t2p_sampler* s, float* device_sums2, t2p_allreduce_fn fn, void* user);
 /* mask: device uint8 (B,C,L,L), 1 where the chain evolves; x_initial: device fp32; both NULL = unconditional */
 int t2p_sampler_set_condition(t2p_sampler* s, const uint8_t* mask, const float* x_initial);
-/* reset the step counter to `step` (0 at the start of a run); a step at index >= N is refused */
+/* Classifier-free guidance in the PC loop (reference sampler/diffusion_sampler.py:128, a property of the network output: the
+ * reference's pc_sampler takes it as a wrapper module).  Enabled, every score of the loop is w out(ctx) + (1 - w) out(0), from ONE
+ * evaluation per score of [x ; x] under [ctx ; 0] at batch 2B; the sum (and, VP, the score scale) is formed inside the norm and
+ * update kernels.  w == 1 runs the plain path at batch B, as the DDIM loop does.  A non-finite w is refused and nothing changes.
+ * May be called between runs; drops a captured graph.  The context has to be set (again) afterwards: t2p_sampler_set_context. */
+int t2p_sampler_set_guidance(t2p_sampler* s, double w, int enabled);
+/* context: device fp32 [batch][tokens][context_dim].  Guided with w != 1: builds [ctx ; 0] on the device and projects it through
+ * the engine at batch 2B; otherwise forwards to t2p_engine_set_context at batch B.  batch != cfg.batch is refused, nothing changes.
+ * A guided step without it is refused. */
+int t2p_sampler_set_context(t2p_sampler* s, const float* context, int batch, int tokens, void* stream);
+/* reset the step counter to `step` (0 at the start of a run) for a fresh x; a step at index >= N is refused */
 int t2p_sampler_reset(t2p_sampler* s, int step, void* stream);
 /* One PC step at the current step index, in place on x (device fp32 (B,C,L,L)); x_mean receives the
  * predictor's mean.  noise_corrector / noise_predictor: device standard-normal draws to use
- * (parity runs); NULL = generate on device. */
+ * (parity runs); NULL = generate on device.
+ * Guided with w != 1 (t2p_sampler_set_guidance), here and in t2p_sampler_step_graph / _run / _count_dispatches: the state is the
+ * first (B,C,L,L) block of x and x must have room for 2B samples: the second block is the sampler's copy of the first (the [x ; x]
+ * input), written by the first step after t2p_sampler_reset and by every update.  x_mean and the noise stay (B,C,L,L). */
 int t2p_sampler_step(t2p_sampler* s, float* x, float* x_mean, const float* noise_corrector,
                      const float* noise_predictor, void* stream);
 /* The same step replayed from a captured hipGraph (on-device noise only).  The first call runs
@@ -483,6 +496,22 @@ int t2p_op_langevin_update(const float* x, const float* grad, const float* noise
 int t2p_op_predictor(const float* x, const float* score, const float* noise, const uint8_t* mask,
                      const float* x_initial, float* x_out, float* x_mean_out, int64_t n, float G,
                      int probability_flow, void* stream);
+/* The three kernels of a guided PC step as operators, every scalar by value.  The score is s = scale (w o_c + w1 o_u), each product
+ * and sum of the guidance sum rounded to float32 in this order (w1 = (float)(1 - w) as the reference rounds it; scale: 1 for VE,
+ * -1 / std for VP); o_u NULL: s = scale o_c.
+ *   norms:     sums = {sum_b ||s_b||, sum_b ||noise_b||}, workspace as t2p_op_langevin_norms
+ *   langevin:  t2p_op_langevin_update on s;   predictor: x_mean = x_coef x + G^2 s (halved under probability_flow), as t2p_op_predictor
+ * With o_u NULL and scale == 1 (and x_coef == 1) the two updates equal t2p_op_langevin_update / t2p_op_predictor bit for bit.
+ * x_out may alias x; x_out2 (optional) receives a second copy of the new state; x_mean_out is optional.  n % 4 == 0 with every
+ * pointer 16-byte aligned (the mask 4-byte) takes 16-byte accesses, anything else goes element by element. */
+int t2p_op_guided_langevin_norms(const float* o_c, const float* o_u, const float* noise, int batch, int64_t per_sample, float w, float w1,
+                                 float scale, float* workspace, float* sums, void* stream);
+int t2p_op_guided_langevin_update(const float* x, const float* o_c, const float* o_u, const float* noise, const uint8_t* mask,
+                                  const float* x_initial, float* x_out, float* x_out2, float* x_mean_out, int64_t n, float w, float w1,
+                                  float scale, const float* sums, float batch_total, float snr, float alpha, void* stream);
+int t2p_op_guided_predictor(const float* x, const float* o_c, const float* o_u, const float* noise, const uint8_t* mask,
+                            const float* x_initial, float* x_out, float* x_out2, float* x_mean_out, int64_t n, float w, float w1,
+                            float scale, float G, float x_coef, int probability_flow, void* stream);
 int t2p_op_philox_normal(float* out, int64_t n, uint64_t seed, uint64_t stream_id, void* stream);
 int t2p_op_convert(const float* in, void* out, int dtype, int64_t n, void* stream);
 /* ---- either side of the sampler ----

@@ -30,6 +30,8 @@ Differences, all at the edges of the hot path:
     (sampler/diffusion_sampler.py: strided DDIM with classifier-free guidance on the text context) instead of the
     predictor-corrector loop.  It reads the network output as a noise prediction, so the config must say ``training.sde: vpsde``.
     The conditions and the output files are the same.
+  * ``--pc_guidance_w W`` (with the default ``--sampler pc``, any config): the same guidance inside the predictor-corrector loop,
+    every score made of ``W out(text) + (1 - W) out(no text)`` from one evaluation at twice the batch.  Unset is the plain loop.
 Under ``python -m torch.distributed.run --nproc-per-node N`` (or with ``--gpus N``, which starts the N ranks
 itself) every rank samples ``--batch_size`` chains on its own GPU and rank 0 gathers them with one RCCL
 all_gather before writing (text2protein_amd/distributed.py).  ``--global_batch_norm`` reproduces the reference's
@@ -92,8 +94,18 @@ def main():
     parser.add_argument("--ddim_eta", type=float, default=1.0, help="--sampler ddim: eta in [0, 1] (0 = deterministic)")
     parser.add_argument("--guidance_w", type=float, default=0.0,
                         help="--sampler ddim: eps = w eps(text) + (1 - w) eps(no text); the reference's default is 0")
+    parser.add_argument("--pc_guidance_w", type=float, default=None,
+                        help="--sampler pc: classifier-free guidance in the predictor-corrector loop, every score made of "
+                             "w out(text) + (1 - w) out(no text) from one evaluation at twice the batch; 1 = the plain conditional "
+                             "run; unset (default) = no guidance.  (--guidance_w belongs to --sampler ddim and defaults to 0, the "
+                             "unconditional run)")
     args = parser.parse_args()
 
+    if args.pc_guidance_w is not None:                                  # before anything touches a device
+        if args.sampler == "ddim":
+            raise SystemExit("--pc_guidance_w guides the predictor-corrector loop: with --sampler ddim give --guidance_w")
+        if args.pc_guidance_w != args.pc_guidance_w or args.pc_guidance_w in (float("inf"), float("-inf")):
+            raise SystemExit("--pc_guidance_w must be finite")
     assert not (args.pdb is not None and args.select_length)
     if args.pdb is not None and args.inpaint_coords is not None:
         raise SystemExit("--pdb and --inpaint_coords both name a source of the known 6D maps: give one")
@@ -182,6 +194,8 @@ def main():
         def sampling_fn(model, condition=None, context=None):
             return ddim.ddim_sample(sampling_shape, context, condition=condition), evaluations
     else:
+        if args.pc_guidance_w is not None:
+            kw["guidance_w"] = args.pc_guidance_w
         sampling_fn = sampling.get_sampling_fn(config, sde, sampling_shape, sampling_eps, seed=D.rank_seed(args.seed, rank), **kw)
 
     caption_ids = None

@@ -85,6 +85,12 @@ SIGNATURES = {
     "t2p_sampler_run": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "t2p_sampler_set_vp_tables": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "t2p_sampler_count_dispatches": (_i, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int)]),
+    # classifier-free guidance in the PC loop
+    "t2p_sampler_set_guidance": (_i, [_vp, C.c_double, _i]),
+    "t2p_sampler_set_context": (_i, [_vp, _vp, _i, _i, _vp]),
+    "t2p_op_guided_langevin_norms": (_i, [_vp, _vp, _vp, _i, _i64, _f, _f, _f, _vp, _vp, _vp]),
+    "t2p_op_guided_langevin_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _vp, _f, _f, _f, _vp]),
+    "t2p_op_guided_predictor": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp]),
     # DDIM sampler with classifier-free guidance (csrc/ddim.hip)
     "t2p_ddim_create": (_i, [_vp, C.POINTER(DdimConfig), C.POINTER(DdimStepRow), C.POINTER(_vp)]),
     "t2p_ddim_destroy": (None, [_vp]),

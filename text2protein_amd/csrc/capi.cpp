@@ -153,6 +153,20 @@ int t2p_sampler_set_vp_tables(t2p_sampler* s, const float* label_f, const float*
   API_END
 }
 
+int t2p_sampler_set_guidance(t2p_sampler* s, double w, int enabled) {
+  API_BEGIN
+  T2P_REQUIRE(s, "null sampler");
+  return s->impl.set_guidance(w, enabled);
+  API_END
+}
+
+int t2p_sampler_set_context(t2p_sampler* s, const float* context, int batch, int tokens, void* stream) {
+  API_BEGIN
+  T2P_REQUIRE(s, "null sampler");
+  return s->impl.set_context(context, batch, tokens, (hipStream_t)stream);
+  API_END
+}
+
 int t2p_sampler_reset(t2p_sampler* s, int step, void* stream) {
   API_BEGIN
   T2P_REQUIRE(s, "null sampler");
@@ -618,6 +632,39 @@ int t2p_op_predictor(const float* x, const float* score, const float* noise, con
   a.x = x; a.score = score; a.noise = noise; a.mask = mask; a.x_initial = x_initial; a.x_out = x_out;
   a.x_mean_out = x_mean_out; a.n = n;
   return launch_predictor_update(a, nullptr, nullptr, G, probability_flow, (hipStream_t)stream);
+  API_END
+}
+
+int t2p_op_guided_langevin_norms(const float* o_c, const float* o_u, const float* noise, int batch, int64_t per_sample, float w, float w1,
+                                 float scale, float* workspace, float* sums, void* stream) {
+  API_BEGIN
+  GuidedScore g;
+  g.o_c = o_c; g.o_u = o_u; g.w = w; g.w1 = w1; g.scale = scale;
+  return launch_guided_langevin_norms(g, noise, batch, per_sample, workspace, sums, (hipStream_t)stream);
+  API_END
+}
+
+int t2p_op_guided_langevin_update(const float* x, const float* o_c, const float* o_u, const float* noise, const uint8_t* mask,
+                                  const float* x_initial, float* x_out, float* x_out2, float* x_mean_out, int64_t n, float w, float w1,
+                                  float scale, const float* sums, float batch_total, float snr, float alpha, void* stream) {
+  API_BEGIN
+  SdeUpdateArgs a;
+  a.x = x; a.noise = noise; a.mask = mask; a.x_initial = x_initial; a.x_out = x_out; a.x_mean_out = x_mean_out; a.n = n;
+  GuidedScore g;
+  g.o_c = o_c; g.o_u = o_u; g.w = w; g.w1 = w1; g.scale = scale;
+  return launch_guided_langevin_update(a, g, x_out2, sums, batch_total, snr, alpha, (hipStream_t)stream);
+  API_END
+}
+
+int t2p_op_guided_predictor(const float* x, const float* o_c, const float* o_u, const float* noise, const uint8_t* mask,
+                            const float* x_initial, float* x_out, float* x_out2, float* x_mean_out, int64_t n, float w, float w1,
+                            float scale, float G, float x_coef, int probability_flow, void* stream) {
+  API_BEGIN
+  SdeUpdateArgs a;
+  a.x = x; a.noise = noise; a.mask = mask; a.x_initial = x_initial; a.x_out = x_out; a.x_mean_out = x_mean_out; a.n = n;
+  GuidedScore g;
+  g.o_c = o_c; g.o_u = o_u; g.w = w; g.w1 = w1; g.scale = scale;
+  return launch_guided_predictor_update(a, g, x_out2, nullptr, G, probability_flow, (hipStream_t)stream, nullptr, x_coef);
   API_END
 }
 

@@ -33,6 +33,20 @@ int launch_ddim_mirror(const float* src, float* dst, long n, hipStream_t s);
 // out[i] = ctx[i], out[n + i] = 0: the context of a guided evaluation, [ctx ; cond * 0] (diffusion_sampler.py:128)
 int launch_ddim_context2(const float* ctx, float* out, long n, hipStream_t s);
 
+// The context of a guided evaluation, owned by a sampler: [ctx ; 0] built on the device and projected through the engine at batch 2B
+// (to_k / to_v have no bias, so the zero half gives zero keys and values, as `cond * 0` does).  One builder for the DDIM loop and
+// the guided predictor-corrector loop.
+class GuidedContext {
+ public:
+  ~GuidedContext();
+  // ctx: device fp32 [B][T][context_dim].  On failure the engine's text caches are in an unknown state: set again before a step.
+  int project(Engine* e, const float* ctx, int B, int T, hipStream_t s);
+
+ private:
+  float* ctx2_ = nullptr;       // device float[2 B T D]
+  size_t floats_ = 0;
+};
+
 class Ddim {
  public:
   Ddim(Engine* e, const t2p_ddim_config& cfg) : e_(e), cfg_(cfg) {}
@@ -54,8 +68,7 @@ class Ddim {
   const float* x_init_ = nullptr;
   int* labels_ = nullptr;       // device int[sampling_steps][2 batch]: the time label of loop step i for every row of the evaluation
   float* eps_ = nullptr;        // device float[2 n]: the network output, text half then zero-context half
-  float* ctx2_ = nullptr;       // device float[2 batch T D]: [ctx ; 0]
-  size_t ctx2_floats_ = 0;
+  GuidedContext ctx2_;          // [ctx ; 0]
   bool have_context_ = false;
   const float* mirrored_ = nullptr;   // the x whose second half holds a copy of the first (null after reset)
   int host_step_ = 0;

@@ -126,7 +126,21 @@ int launch_ddim_context2(const float* ctx, float* out, long n, hipStream_t s) {
 Ddim::~Ddim() {
   (void)hipFree(labels_);
   (void)hipFree(eps_);
-  (void)hipFree(ctx2_);
+}
+
+GuidedContext::~GuidedContext() { (void)hipFree(ctx2_); }
+
+int GuidedContext::project(Engine* e, const float* ctx, int B, int T, hipStream_t s) {
+  const size_t half = (size_t)B * T * e->cfg().context_dim;
+  if (2 * half > floats_) {
+    float* p = nullptr;
+    T2P_HIP_CHECK(hipMalloc((void**)&p, 2 * half * 4));
+    (void)hipFree(ctx2_);     // (waits for the work that may still read it)
+    ctx2_ = p;
+    floats_ = 2 * half;
+  }
+  T2P_TRY(launch_ddim_context2(ctx, ctx2_, (long)half, s));
+  return e->set_context(ctx2_, 2 * B, T, s);
 }
 
 int Ddim::init(const t2p_ddim_step_row* table) {
@@ -162,17 +176,8 @@ int Ddim::set_context(const float* ctx, int B, int T, hipStream_t s) {
     have_context_ = true;
     return T2P_OK;
   }
-  const size_t half = (size_t)B * T * e_->cfg().context_dim;
-  if (2 * half > ctx2_floats_) {
-    float* p = nullptr;
-    T2P_HIP_CHECK(hipMalloc((void**)&p, 2 * half * 4));
-    (void)hipFree(ctx2_);     // (waits for the work that may still read it)
-    ctx2_ = p;
-    ctx2_floats_ = 2 * half;
-  }
-  T2P_TRY(launch_ddim_context2(ctx, ctx2_, (long)half, s));
   have_context_ = false;      // a failure below leaves the engine's text caches in an unknown state
-  T2P_TRY(e_->set_context(ctx2_, 2 * B, T, s));
+  T2P_TRY(ctx2_.project(e_, ctx, B, T, s));
   have_context_ = true;
   return T2P_OK;
 }

@@ -65,6 +65,34 @@ int Sampler::reset(int step, hipStream_t s) {
   T2P_HIP_CHECK(hipMemcpyAsync(step_dev_, &step, sizeof(int), hipMemcpyHostToDevice, s));
   T2P_HIP_CHECK(hipStreamSynchronize(s));
   host_step_ = step;
+  mirrored_ = nullptr;     // a fresh x: its second block is rewritten by the next guided step
+  return T2P_OK;
+}
+
+int Sampler::set_guidance(double w, int enabled) {
+  T2P_REQUIRE(std::isfinite(w), "the guidance weight must be finite");
+  T2P_REQUIRE(enabled == 0 || enabled == 1, "enabled is 0 or 1");
+  if (enabled && w != 1.0 && !score2_) {
+    score2_ = (float*)e_->pool().persistent((size_t)n_ * 2 * 4);
+    if (!score2_) return T2P_ERR_HIP;
+  }
+  guidance_ = enabled != 0;
+  w_ = w;
+  mirrored_ = nullptr;
+  if (graph_exec_) {       // the captured step holds the weight and the batch of its evaluation
+    (void)hipGraphExecDestroy(graph_exec_);
+    graph_exec_ = nullptr;
+  }
+  return T2P_OK;
+}
+
+int Sampler::set_context(const float* ctx, int B, int T, hipStream_t s) {
+  T2P_REQUIRE(ctx && T > 0, "set_context arguments");
+  T2P_REQUIRE(B == cfg_.batch, "the context batch must equal cfg.batch");
+  have_context2_ = false;      // a failure below leaves the engine's text caches in an unknown state
+  if (!guided()) return e_->set_context(ctx, B, T, s);
+  T2P_TRY(ctx2_.project(e_, ctx, B, T, s));
+  have_context2_ = true;
   return T2P_OK;
 }
 
@@ -107,6 +135,7 @@ int Sampler::step(float* x, float* x_mean, const float* nc, const float* np, hip
   const bool vp = cfg_.sde == T2P_SDE_VP;
   T2P_REQUIRE(!vp || vp_label_f_, "VP SDE: call t2p_sampler_set_vp_tables first");
   float* sums = allreduce_ ? sums_ext_ : sums_;
+  if (guided()) return guided_step(x, x_mean, nc, np, sums, s);
   // score function (models/utils.py:138-171): VE = the network output at the integer label; VP = -output / std at the fractional one
   auto score_fn = [&]() -> int {
     T2P_TRY(e_->score(x, nullptr, step_dev_, score_, B, s, nullptr, label_table_, vp ? vp_label_f_ : nullptr));
@@ -145,6 +174,52 @@ int Sampler::step(float* x, float* x_mean, const float* nc, const float* np, hip
   return T2P_OK;
 }
 
+// the same iteration under guidance: one evaluation of [x ; x] at batch 2B per score, the guidance sum and the VP score scale
+// inside the norm and update kernels, every update written to both blocks of x
+int Sampler::guided_step(float* x, float* x_mean, const float* nc, const float* np, float* sums, hipStream_t s) {
+  T2P_REQUIRE(have_context2_, "guided sampling: call t2p_sampler_set_context first (after t2p_sampler_set_guidance)");
+  const int B = cfg_.batch;
+  const bool vp = cfg_.sde == T2P_SDE_VP;
+  if (mirrored_ != x) {     // first step on this buffer: the zero-context half of the evaluation reads a copy of x
+    T2P_TRY(launch_ddim_mirror(x, x + n_, n_, s));
+    mirrored_ = x;
+  }
+  GuidedScore g;
+  g.o_c = score2_; g.o_u = score2_ + n_; g.w = (float)w_; g.w1 = (float)(1.0 - w_);
+  g.scale_table = vp ? vp_score_scale_ : nullptr; g.step_counter = step_dev_; g.n_table = cfg_.N;
+  auto score_fn = [&]() -> int {
+    return e_->score(x, nullptr, step_dev_, score2_, 2 * B, s, nullptr, label_table_, vp ? vp_label_f_ : nullptr);
+  };
+  SdeUpdateArgs a;
+  a.x = x; a.mask = mask_; a.x_initial = x_init_; a.x_out = x; a.n = n_;
+  for (int k = 0; k < cfg_.n_steps_each; ++k) {
+    T2P_TRY(score_fn());
+    a.noise = nc;
+    if (!nc) {
+      T2P_TRY(launch_philox_normal(noise_, n_, cfg_.seed, 2ull * k + 2, step_dev_, s));
+      a.noise = noise_;
+    }
+    T2P_TRY(launch_guided_langevin_norms(g, a.noise, B, per_sample_, sq_ws_, sums, s));
+    if (allreduce_) {
+      const int rc = allreduce_(sums, (void*)s, allreduce_user_);
+      if (rc != 0) { set_last_error("the norm all-reduce callback failed with status " + std::to_string(rc)); return T2P_ERR_STATE; }
+    }
+    T2P_TRY(launch_guided_langevin_update(a, g, x + n_, sums, (float)(allreduce_ ? cfg_.global_batch : B), (float)cfg_.snr, 1.f, s,
+                                          vp ? vp_alpha_ : nullptr));
+  }
+  T2P_TRY(score_fn());
+  a.noise = np;
+  if (!np) {
+    T2P_TRY(launch_philox_normal(noise_, n_, cfg_.seed, 1, step_dev_, s));
+    a.noise = noise_;
+  }
+  a.x_mean_out = x_mean ? x_mean : xmean_;
+  T2P_TRY(launch_guided_predictor_update(a, g, x + n_, g_table_, 0.f, cfg_.probability_flow, s, vp ? vp_x_coef_ : nullptr));
+  T2P_TRY(launch_add_int(step_dev_, 1, s));
+  ++host_step_;
+  return T2P_OK;
+}
+
 Sampler::~Sampler() {
   if (graph_exec_) (void)hipGraphExecDestroy(graph_exec_);
 }
@@ -153,7 +228,9 @@ int Sampler::step_graph(float* x, float* x_mean, hipStream_t s) {
   T2P_REQUIRE(x && x_mean, "step_graph needs explicit x and x_mean buffers");
   T2P_REQUIRE(!allreduce_, "the captured step does not run the norm all-reduce hook: use t2p_sampler_step");
   T2P_REQUIRE(host_step_ >= 0 && host_step_ < cfg_.N, "PC step index beyond sde.N: call t2p_sampler_reset before another run");
-  if (eager_steps_ < 1)              // one eager step first: fills the activation pool (no hipMalloc under capture); step() counts it
+  // one eager step first: fills the activation pool (no hipMalloc under capture); step() counts it.  Guided: also the first step
+  // after a reset, which writes the second block of x once (the captured step does not)
+  if (eager_steps_ < 1 || (guided() && mirrored_ != x))
     return step(x, x_mean, nullptr, nullptr, s);
   if (graph_exec_ && (graph_x_ != x || graph_xm_ != x_mean || graph_mask_ != mask_ || graph_seed_ != cfg_.seed)) {
     (void)hipGraphExecDestroy(graph_exec_);
@@ -190,8 +267,10 @@ int Sampler::count_dispatches(float* x, float* x_mean, hipStream_t s, int* n_out
   hipGraph_t graph = nullptr;
   T2P_HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
   const int step_before = host_step_;
+  const float* mirrored_before = mirrored_;
   const int rc = step(x, x_mean, nullptr, nullptr, s);
   host_step_ = step_before;
+  mirrored_ = mirrored_before;         // a mirror launch of the first guided step was counted, not run
   const hipError_t ec = hipStreamEndCapture(s, &graph);
   if (rc != T2P_OK) {
     if (graph) (void)hipGraphDestroy(graph);

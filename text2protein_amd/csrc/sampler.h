@@ -1,5 +1,6 @@
 // Predictor-corrector sampling (score_sde_pytorch/sampling.py:213-291): the fused host-side loop over a finalized Engine; its noise streams: philox.h.
 #pragma once
+#include "ddim.h"
 #include "engine.h"
 
 namespace t2p {
@@ -16,6 +17,11 @@ class Sampler {
   int set_norm_allreduce(float* sums, t2p_allreduce_fn fn, void* user);
   // VP SDE (sde_lib.py:106-157) in the fused loop: per-step host tables of N floats (see t2p_sampler_set_vp_tables)
   int set_vp_tables(const float* label_f, const float* score_scale, const float* x_coef, const float* corr_alpha);
+  // classifier-free guidance (reference sampler/diffusion_sampler.py:128): every score of the loop becomes w out(ctx) + (1 - w) out(0),
+  // from ONE evaluation of [x ; x] under [ctx ; 0] at batch 2B.  x then has room for 2B samples (see t2p_sampler_step).
+  int set_guidance(double w, int enabled);
+  int set_context(const float* ctx, int B, int T, hipStream_t s);
+  bool guided() const { return guidance_ && w_ != 1.0; }     // w == 1: 1 a + 0 b == a, the plain path at batch B
   int reset(int step, hipStream_t s);
   int step(float* x, float* x_mean, const float* nc, const float* np, hipStream_t s);
   // step() through a captured hipGraph (device noise only): first call with a given (x, x_mean,
@@ -26,6 +32,7 @@ class Sampler {
   ~Sampler();
 
  private:
+  int guided_step(float* x, float* x_mean, const float* nc, const float* np, float* sums, hipStream_t s);
   Engine* e_;
   t2p_sampler_config cfg_;
   const uint8_t* mask_ = nullptr;
@@ -53,6 +60,12 @@ class Sampler {
   float* graph_xm_ = nullptr;
   const uint8_t* graph_mask_ = nullptr;
   int eager_steps_ = 0;
+  bool guidance_ = false;
+  double w_ = 1.0;
+  float* score2_ = nullptr;           // device float[2 n]: the network output at batch 2B, text half then zero-context half
+  GuidedContext ctx2_;                // [ctx ; 0]
+  bool have_context2_ = false;        // the engine holds the projections of ctx2_
+  const float* mirrored_ = nullptr;   // the x whose second block holds a copy of the first (null after reset)
 };
 
 }  // namespace t2p

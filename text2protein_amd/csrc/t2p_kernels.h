@@ -123,6 +123,28 @@ int launch_langevin_update(const SdeUpdateArgs& a, const float* sums, float batc
 int launch_predictor_update(const SdeUpdateArgs& a, const float* G_table, const int* step_counter, float G_value,
                             int probability_flow, hipStream_t s, int n_table = 0, const float* x_coef_table = nullptr);
 int launch_scale_by_table(float* x, long n, const float* table, const int* step_counter, int n_table, hipStream_t s);
+// ---- the same three kernels under classifier-free guidance (reference sampler/diffusion_sampler.py:128) ----
+// The score is formed per element from the two halves of one evaluation at batch 2B: s = scale (w o_c + w1 o_u), each product and
+// sum of the guidance sum rounded to float32 in this order.  o_u null: s = scale o_c, and with scale == 1 the updates reproduce
+// launch_langevin_update / launch_predictor_update bit for bit.  SdeUpdateArgs::score is not read.
+struct GuidedScore {
+  const float* o_c = nullptr;          // network output under the text context
+  const float* o_u = nullptr;          // under the zero context; null = no guidance sum
+  float w = 1.f, w1 = 0.f;             // guidance weight and (float)(1 - w) as the reference rounds it (from the double)
+  float scale = 1.f;                   // VE: 1; VP: -1 / std of the step's label ...
+  const float* scale_table = nullptr;  // ... or scale_table[*step_counter]
+  const int* step_counter = nullptr;   // device step index of every per-step table (scale, alpha, G, x_coef)
+  int n_table = 0;
+};
+// sums as launch_langevin_norms, over B samples: sum_b ||s_b||, sum_b ||noise_b||
+int launch_guided_langevin_norms(const GuidedScore& g, const float* noise, int B, long per_sample, float* sq_ws, float* sums,
+                                 hipStream_t s);
+// x_out2 (optional): a second copy of the new state, the other half of the [x ; x] input of the next evaluation
+int launch_guided_langevin_update(const SdeUpdateArgs& a, const GuidedScore& g, float* x_out2, const float* sums, float batch_total,
+                                  float snr, float alpha, hipStream_t s, const float* alpha_table = nullptr);
+// x_coef_value: the x coefficient where no table is given (the operator ABI)
+int launch_guided_predictor_update(const SdeUpdateArgs& a, const GuidedScore& g, float* x_out2, const float* G_table, float G_value,
+                                   int probability_flow, hipStream_t s, const float* x_coef_table = nullptr, float x_coef_value = 1.f);
 // noise[i] = N(0,1) from Philox4x32-10 keyed by (seed, stream); counter = element index / 4
 int launch_philox_normal(float* out, long n, unsigned long long seed, unsigned long long stream,
                          const int* step_counter, hipStream_t s);

@@ -9,6 +9,10 @@ Same names, arguments, registries and error behaviour as the reference:
   get_pc_sampler(...) -> pc_sampler(model, condition=None, context=None)     sampling.py:213-291
   get_score_fn(sde, model, train=False, continuous=False)                   models/utils.py:126-176
 
+Classifier-free guidance (``guidance_w=``, not in the reference's PC loop): the network output every score is made of becomes
+``w * model(x, t, context) + (1 - w) * model(x, t, context * 0)``, the expression of sampler/diffusion_sampler.py:128 -- what the
+reference computes when its ``pc_sampler`` is handed a module with that forward.
+
 The state update of every step (score network, noise, norms, Euler-Maruyama / Langevin update,
 conditional masking) runs in libt2p_hip.so.  torch is used for the once-per-run condition set-up
 and for (B,)-sized schedule scalars.  Two execution routes produce the same numbers:
@@ -23,6 +27,7 @@ from __future__ import annotations
 import abc
 import ctypes as C
 import functools
+import math
 
 import torch
 
@@ -57,11 +62,29 @@ get_predictor, get_corrector = _PREDICTORS.__getitem__, _CORRECTORS.__getitem__
 # ------------------------------------------------------------------------------------------------
 # score function adapter
 # ------------------------------------------------------------------------------------------------
-def get_score_fn(sde, model, train=False, continuous=False):
+_guided_ctx_cache = {"key": None, "ctx": None, "ctx2": None}
+
+
+def _guided_context(context):
+    """``[context ; context * 0]`` for one evaluation at batch 2B, rebuilt only when ``context`` changes (the engine re-projects
+    a context it has not seen; the predictor / corrector wrappers build a new score function every step)."""
+    key = (context.data_ptr(), context._version, tuple(context.shape), context.device, context.dtype)
+    c = _guided_ctx_cache
+    if c["key"] != key:
+        c["key"], c["ctx"], c["ctx2"] = key, context, torch.cat([context, context * 0]).contiguous()
+    return c["ctx2"]
+
+
+def get_score_fn(sde, model, train=False, continuous=False, guidance_w=None):
     """models/utils.py:126-176: ``score_fn(x, t, context=None)`` for ``model(x, labels, context)`` (a ``HipScoreModel`` or
     any callable with the reference signature).  VE: integer labels ``round((T - t)(N - 1))`` (noisiest level first) or,
     ``continuous``, the marginal std; the network output is the score.  VP / subVP: fractional labels ``t (N - 1)``
-    (``t * 999`` when continuous or subVP) and the output is divided by minus the marginal std."""
+    (``t * 999`` when continuous or subVP) and the output is divided by minus the marginal std.
+
+    ``guidance_w`` (not ``None``): the network output is ``w * model(x, labels, context) + (1 - w) * model(x, labels,
+    context * 0)`` (sampler/diffusion_sampler.py:128), float32 products and sum in that order.  A ``HipScoreModel`` evaluates
+    ``[x ; x]`` under ``[context ; 0]`` once at batch 2B (at batch B when ``w == 1``: 1 a + 0 b == a); any other callable is
+    called twice, with ``context * 0`` second.  This is the single place that wraps."""
     if train:
         raise T2PError("the HIP engine is inference-only (train=True is not on the sampling path)")
     ve = isinstance(sde, sde_lib.VESDE)
@@ -69,9 +92,26 @@ def get_score_fn(sde, model, train=False, continuous=False):
     if not (ve or sub or isinstance(sde, sde_lib.VPSDE)):
         raise NotImplementedError(f"SDE class {sde.__class__.__name__} not yet supported.")
 
+    if guidance_w is not None and not math.isfinite(float(guidance_w)):
+        raise T2PError("the guidance weight must be finite")
+
     def evaluate(x, labels, context):
         model.eval()
-        return model(x, labels, context)
+        if guidance_w is None:
+            return model(x, labels, context)
+        if context is None:
+            raise T2PError("classifier-free guidance needs a context")
+        w = float(guidance_w)
+        if isinstance(model, HipScoreModel):
+            if w == 1.0:
+                return model(x, labels, context)
+            B = x.shape[0]
+            out = model(torch.cat([x, x]), torch.cat([labels, labels]), _guided_context(context))
+            o_c, o_u = out[:B], out[B:]
+        else:
+            o_c = model(x, labels, context)
+            o_u = model(x, labels, context * 0)
+        return w * o_c + (1 - w) * o_u
 
     def score_ve(x, t, context=None):
         labels = sde.marginal_prob_std(t) if continuous else torch.round((sde.T - t) * (sde.N - 1)).long()
@@ -223,15 +263,15 @@ class LangevinCorrector(Corrector):
         return x, x_mean
 
 
-def shared_predictor_update_fn(x, t, context, sde, model, predictor, probability_flow):
+def shared_predictor_update_fn(x, t, context, sde, model, predictor, probability_flow, guidance_w=None):
     """A wrapper that configures and returns the update function of predictors (sampling.py:201-205)."""
-    score_fn = get_score_fn(sde, model, train=False)
+    score_fn = get_score_fn(sde, model, train=False, guidance_w=guidance_w)
     return predictor(sde, score_fn, probability_flow).update_fn(x, t, context)
 
 
-def shared_corrector_update_fn(x, t, context, sde, model, corrector, snr, n_steps):
+def shared_corrector_update_fn(x, t, context, sde, model, corrector, snr, n_steps, guidance_w=None):
     """sampling.py:207-211."""
-    score_fn = get_score_fn(sde, model, train=False)
+    score_fn = get_score_fn(sde, model, train=False, guidance_w=guidance_w)
     return corrector(sde, score_fn, snr, n_steps).update_fn(x, t, context)
 
 
@@ -270,11 +310,16 @@ class PCStepper:
     body of the reference ``pc_sampler`` (sampling.py:279-285) enqueued on the current stream."""
 
     def __init__(self, model, sde, batch, snr, n_steps=1, probability_flow=False, denoise=True, eps=1e-5, seed=0,
-                 global_batch=None, all_reduce=None):
+                 global_batch=None, all_reduce=None, guidance_w=None):
         """``global_batch`` / ``all_reduce``: the Langevin batch means run over ``global_batch`` chains spread
         over several processes (the reference's DataParallel semantics, sampling.py:193-195): ``all_reduce`` is
         called once per corrector step with a 2-float device tensor it must sum over the processes in place,
-        in stream order (``text2protein_amd.distributed.allreduce_norm_sums``)."""
+        in stream order (``text2protein_amd.distributed.allreduce_norm_sums``).
+
+        ``guidance_w`` (not ``None``): classifier-free guidance, ``w out(ctx) + (1 - w) out(0)`` from one evaluation at batch
+        2B per score.  With ``w != 1`` (``self.guided``) the ``x`` of ``step`` / ``step_graph`` / ``count_dispatches`` holds 2B
+        samples: the state is its first ``batch`` samples, the rest is the sampler's copy; the context goes through
+        ``set_context`` of this object."""
         vp = isinstance(sde, sde_lib.VPSDE)
         if not (vp or isinstance(sde, sde_lib.VESDE)):
             raise T2PError("the fused stepper covers the VE and VP SDEs; others run through the predictor/corrector classes")
@@ -311,6 +356,10 @@ class PCStepper:
             check(self.lib.t2p_sampler_set_vp_tables(h, *[C.c_void_p(t.data_ptr()) for t in vp_tables]))
         self._keep = ()
         self.N = int(sde.N)
+        self.batch = int(batch)
+        self.guided = False
+        if guidance_w is not None:
+            self.set_guidance(guidance_w)
         if all_reduce is not None:
             self._sums = torch.zeros(2, device=model.device, dtype=torch.float32)
             self._cb, self._cb_error = allreduce_trampoline(all_reduce, self._sums)   # kept alive as long as the sampler
@@ -318,6 +367,22 @@ class PCStepper:
 
     def set_seed(self, seed):
         check(self.lib.t2p_sampler_set_seed(self._h, int(seed) & _M64))
+
+    def set_guidance(self, w, enabled=True):
+        """Guidance weight of the following steps (``enabled=False``: the plain loop); the context has to be set again afterwards."""
+        check(self.lib.t2p_sampler_set_guidance(self._h, float(w), int(bool(enabled))))
+        self.guided = bool(enabled) and float(w) != 1.0
+
+    def set_context(self, context):
+        """The text context of the following steps: ``[context ; 0]`` projected at batch 2B when guided with ``w != 1``, else
+        ``context`` at batch B.  The model's own context cache no longer describes the engine afterwards and is dropped."""
+        context = context.to(self.model.device, torch.float32).contiguous()
+        B, T, D = context.shape
+        if D != self.model.config.model.context_dim:
+            raise T2PError(f"context dim {D} != model.context_dim {self.model.config.model.context_dim}")
+        self.model._ctx_key = None
+        check(self.lib.t2p_sampler_set_context(self._h, ptr(context), B, T, stream_ptr()))
+        self._ctx_ref = context
 
     def set_condition(self, mask_u8=None, x_initial=None):
         self._keep = (mask_u8, x_initial)          # the C side borrows these pointers
@@ -387,13 +452,17 @@ def apply_conditions(x, condition):
 
 
 def get_pc_sampler(sde, shape, predictor, corrector, snr, n_steps=1, probability_flow=False, denoise=True,
-                   eps=1e-3, device="cuda", seed=0, force_classes=False, global_batch=None, all_reduce=None):
+                   eps=1e-3, device="cuda", seed=0, force_classes=False, global_batch=None, all_reduce=None, guidance_w=None):
     """Create a Predictor-Corrector (PC) sampler (sampling.py:213-291).
 
     Extra keyword arguments (not in the reference): ``seed`` of the on-device noise generator;
     ``force_classes`` runs the predictor / corrector objects even where the fused route applies;
     ``global_batch`` + ``all_reduce`` give the Langevin step size the reference computes when its batch is
     spread over devices (mean norms over all ``global_batch`` chains, SURVEY.md 8(e) option B).
+    ``guidance_w`` (``None`` = the plain loop, bit for bit): classifier-free guidance on the text context, every score made of
+    ``w out(ctx) + (1 - w) out(0)`` (see ``get_score_fn``); ``w == 1`` is the plain conditional run.  The number of function
+    evaluations returned stays ``sde.N * (n_steps + 1)`` as in the reference; with ``w != 1`` each of them is one network
+    evaluation at twice the batch (two evaluations for a callable that is not a ``HipScoreModel``).
     The returned ``pc_sampler(model, condition=None, context=None, noise_fn=None, n_iter=None, call_index=None)``
     accepts ``noise_fn(shape) -> CPU tensor`` to inject the standard-normal draws in the
     reference's order (prior, then corrector and predictor of each step), and ``n_iter`` to stop
@@ -403,6 +472,8 @@ def get_pc_sampler(sde, shape, predictor, corrector, snr, n_steps=1, probability
     device = torch.device("cuda:0" if str(device) == "cuda" else device)
     if device.type != "cuda":
         raise T2PError("the HIP sampler needs a GPU device (no CPU fallback)")
+    if guidance_w is not None and not math.isfinite(float(guidance_w)):
+        raise T2PError("the guidance weight must be finite")
     fused_ok = (isinstance(sde, (sde_lib.VESDE, sde_lib.VPSDE)) and predictor is ReverseDiffusionPredictor
                 and corrector is LangevinCorrector and not force_classes)
     state = {"sampler": None, "model": None, "calls": 0}
@@ -410,7 +481,7 @@ def get_pc_sampler(sde, shape, predictor, corrector, snr, n_steps=1, probability
     def _fused_sampler(model):
         if state["sampler"] is None or state["model"] is not model:
             state["sampler"] = PCStepper(model, sde, shape[0], snr, n_steps, probability_flow, denoise, eps, seed,
-                                         global_batch=global_batch, all_reduce=all_reduce)
+                                         global_batch=global_batch, all_reduce=all_reduce, guidance_w=guidance_w)
             state["model"] = model
         return state["sampler"]
 
@@ -437,32 +508,43 @@ def get_pc_sampler(sde, shape, predictor, corrector, snr, n_steps=1, probability
             x_initial = x.detach().clone()
             conditioned = bool(condition)
             mask_u8 = conditional_mask.to(torch.uint8).contiguous() if conditioned else None
+            fused = fused_ok and isinstance(model, HipScoreModel)
+            if guidance_w is not None and context is None:
+                raise T2PError("classifier-free guidance needs a context")
             if context is not None:
                 context = context.to(device, torch.float32).contiguous()
-                if isinstance(model, HipScoreModel):
+                if isinstance(model, HipScoreModel) and (guidance_w is None or not fused):
                     model.set_context(context)
                     context = model._ctx_ref
 
-            if fused_ok and isinstance(model, HipScoreModel):
+            if fused:
                 stepper = _fused_sampler(model)
+                if guidance_w is not None:
+                    stepper.set_context(context)     # [ctx ; 0] at batch 2B (w != 1)
                 stepper.set_condition(mask_u8, x_initial if conditioned else None)
                 stepper.set_seed(run_seed)
                 stepper.reset(0)
                 x_mean = torch.empty_like(x)
+                x_buf = x
+                if stepper.guided:                   # room for the sampler's copy of the state, the [x ; x] input
+                    x_buf = torch.empty(2 * shape[0], *x.shape[1:], device=device, dtype=torch.float32)
+                    x_buf[:shape[0]] = x
+                    x = x_buf[:shape[0]]
                 for _ in range(n_iter):
                     nc = npred = None
                     if noise_fn is not None:
                         nc, npred = noise.like(x), noise.like(x)
-                    stepper.step(x, x_mean, nc, npred)
+                    stepper.step(x_buf, x_mean, nc, npred)
             else:
                 ReverseDiffusionPredictor.noise = LangevinCorrector.noise = noise
                 LangevinCorrector.all_reduce = staticmethod(all_reduce) if all_reduce is not None else None
                 LangevinCorrector.global_batch = global_batch
                 timesteps = torch.linspace(sde.T, eps, sde.N, device=device)
+                guided = {} if guidance_w is None else {"guidance_w": guidance_w}
                 predictor_update_fn = functools.partial(shared_predictor_update_fn, sde=sde, predictor=predictor,
-                                                        probability_flow=probability_flow)
+                                                        probability_flow=probability_flow, **guided)
                 corrector_update_fn = functools.partial(shared_corrector_update_fn, sde=sde, corrector=corrector,
-                                                        snr=snr, n_steps=n_steps)
+                                                        snr=snr, n_steps=n_steps, **guided)
                 x_mean = x
                 n_el = x.numel()
                 for i in range(n_iter):
