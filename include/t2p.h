@@ -248,6 +248,8 @@ int t2p_op_ddim_update(const float* x, const float* eps_c, const float* eps_u, c
  *                          optimize_fn (warm-up on state['step'], clip_grad_norm_, Adam: losses.py:41-49), step += 1, ema.update
  * t2p_train_eval_loss   <- step_fn with train=False (losses.py:177-183): the loss under the EMA weights, model in eval mode
  * t2p_train_set_ss_blocks <- block_dropout(coords_6d, batch["ss_indices"]) under the ss condition (losses.py:54-64, called at :106-107)
+ * t2p_train_set_inpaint_draw <- utils.random_mask_batch(batch, config) (utils.py:15-60), which train.py calls before every train and eval
+ *                          step (train.py:176, :193) when "inpainting" is in the condition
  * The model runs in train mode (models/utils.py:116-118): Dropout_0 of every residual block is active when dropout > 0.       */
 typedef struct t2p_train_config {
   double lr, beta1, eps, weight_decay;   /* optim.lr / beta1 / eps / weight_decay; beta2 = 0.999 as get_optimizer fixes it    */
@@ -309,6 +311,24 @@ int t2p_train_set_dropout_masks(t2p_trainer* t, const uint8_t* const* device_mas
  * wrapped: the dataset never writes one); sample < 0.  A sample >= batch shows at the pass: that pass returns an error, computes and
  * changes nothing, and the list is cleared. */
 int t2p_train_set_ss_blocks(t2p_trainer* t, const int32_t* host_blocks, int n, const uint8_t* host_drop, double p);
+/* random_mask_batch (utils.py:15-60; train.py:176, :193): the random inpainting mask of a batch that supplies none, drawn on the device.
+ * host_len_lo_hi: host int32 [B][3] = (l, lo, hi) per sample -- l valid residues, lo = int(mask_min_len l), hi = int(mask_max_len l),
+ * both products in double as Python forms them; copied at the call.  One uniform u0 per batch picks the mode: a random subset when
+ * u0 < (float)random_p, a contiguous window when u0 > (float)(1.0 - contiguous_p), else none (every residue flagged, the padding
+ * included: mask_pair removes it).  Per sample r = lo + (((w0 >> 8) (hi - lo)) >> 24) residues in [lo, hi) are flagged: the window
+ * start .. start + r with start = ((w1 >> 8) (l - r)) >> 24, or the r residues whose 32-bit keys rank lowest among the l valid ones (ties
+ * to the lower index: exactly r, every subset of that size equally likely).  mask_inpaint[b][i][j] = flag[b][i] | flag[b][j]; r = 0
+ * (lo = 0) flags nothing, that sample's num_elem is 0 and its loss term 0 / 1e-8 = 0.  All words are Philox4x32-10 under the trainer seed
+ * on a stream of its own per loss call (csrc/philox.h tabulates the counters), so the draws differ from torch's; the distribution is
+ * the reference's except that r and start come from 24-bit words.
+ * Per-batch data, like the ss block list: the NEXT t2p_train_loss / t2p_train_step / t2p_train_eval_loss whose batch->mask_inpaint is
+ * NULL draws into a trainer-owned buffer that goes where batch->mask_inpaint goes, and consumes the request; a pass whose batch
+ * supplies mask_inpaint ignores the request and clears it; B = 0 clears it.  Refused with nothing changed (a request set earlier
+ * stays): a trainer whose cond_flags lacks bit 4 or whose max_res_num exceeds 256; a probability outside [0, 1] or a sum above 1;
+ * l < 0 or l > max_res_num; lo < 0, lo >= hi or hi > l for any sample (torch.randint raises on the empty range, e.g. l = 1).  A B that
+ * differs from the pass's batch fails that pass, which computes and changes nothing, and the request is cleared.  Without a request
+ * and without mask_inpaint the pass is refused as before ("the inpainting condition needs batch.mask_inpaint"). */
+int t2p_train_set_inpaint_draw(t2p_trainer* t, const int32_t* host_len_lo_hi, int B, double random_p, double contiguous_p);
 /* loss_host: host float; score_out (optional): device fp32 (batch, C, L, L), the score the loss was computed from */
 int t2p_train_loss(t2p_trainer* t, const t2p_train_batch* batch, int backward, float* loss_host, float* score_out, void* stream);
 int t2p_train_step(t2p_trainer* t, const t2p_train_batch* batch, float* loss_host, void* stream);
@@ -339,6 +359,13 @@ int t2p_op_tgemm16(int dtype, const float* A, int64_t sAm, int64_t sAk, const fl
  * [0, batch), p outside [0, 1]. */
 int t2p_op_ss_block_dropout(const float* x, float* out, int batch, int C, int L, const int32_t* host_blocks, int n,
                             const uint8_t* host_drop, double p, uint64_t seed, uint64_t stream_id, uint8_t* drop_out_device, void* stream);
+/* the draw of t2p_train_set_inpaint_draw alone, through the same kernel: flags_out device uint8 [B][L] (1 = residue masked), pair_out
+ * device uint8 [B][L][L] = flags[b][i] | flags[b][j], mode_out_host (optional) host int = the mode used (0 none, 1 random, 2 contiguous).
+ * seed / stream_id: the Philox key and stream (the trainer's: its seed and 4096 loss_calls + 3).  force_mode: -1 = drawn from u0,
+ * 0 / 1 / 2 = that mode with the per-sample words unchanged.  L <= 256.  Refused with the outputs untouched: what
+ * t2p_train_set_inpaint_draw refuses (with L for max_res_num), B <= 0, a force_mode outside -1 .. 2. */
+int t2p_op_inpaint_mask_draw(const int32_t* host_len_lo_hi, int B, int L, double random_p, double contiguous_p, uint64_t seed, uint64_t stream_id,
+                             int force_mode, uint8_t* flags_out, uint8_t* pair_out, int* mode_out_host, void* stream);
 /* backward halves of the operators (gradients accumulate into dx / dgamma / dbeta / du) */
 int t2p_op_groupnorm_backward(const float* x, const float* dy, const float* gamma, const float* beta, int silu, int batch, int HW, int C,
                               int groups, float eps, float* dx, float* dgamma, float* dbeta, void* stream);

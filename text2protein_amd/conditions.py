@@ -3,6 +3,7 @@
   get_mask_all_lengths     utils.py:139-148   (n_lengths, B, L, L) bool; the driver indexes it with
                                               ``length_index - 1`` (sampling_6d.py:145)
   selected_mask_batch      utils.py:62-81     "1:5,10:15" -> (B, L, L) bool, inclusive 0-based ranges
+  random_mask_batch        utils.py:15-60     the random inpainting mask train.py draws before every train and eval step
   get_condition_from_batch utils.py:84-106    {"length" | "ss" | "inpainting"} from a batch of 6D maps
   get_conditions_from_pdb  utils.py:122-137   the same from one chain of a PDB file, featurised on the device
                                               (text2protein_amd/encode.py: dataset.py:114-168, :200-239, :396-450)
@@ -12,6 +13,8 @@ of the 8-channel layout (biotite's P-SEA in the reference) are an input.  ``get_
 dataset directory and stays out of scope.
 """
 from __future__ import annotations
+
+import random
 
 import numpy as np
 import torch
@@ -55,12 +58,77 @@ def selected_mask_batch(batch, mask_info, config):
     return batch
 
 
+def batch_lengths(batch):
+    """The valid residues per sample as Python ints: ``batch["lengths"]`` (what ``encode_6d_batch`` returns) or the reference's
+    ``batch["aa_str"]`` (padded with "_", utils.py:27)."""
+    if "lengths" in batch:
+        return [int(v) for v in torch.as_tensor(batch["lengths"]).reshape(-1).tolist()]
+    if "aa_str" in batch:
+        return [sum(ch != "_" for ch in s) for s in batch["aa_str"]]
+    from ._lib import T2PError
+    raise T2PError("the random inpainting mask needs the residue counts: batch['lengths'] or batch['aa_str']")
+
+
+def mask_count_range(length, inpainting_cfg, max_res_num=None):
+    """``(lo, hi)`` = ``(int(mask_min_len * l), int(mask_max_len * l))``, the bounds of ``torch.randint`` at utils.py:34 / :46.  An empty
+    range (``l = 1`` under the shipped 0.05 / 0.95) makes ``torch.randint`` raise in the reference; here it is a ``T2PError``."""
+    from ._lib import T2PError
+    l = int(length)
+    lo, hi = int(inpainting_cfg.mask_min_len * l), int(inpainting_cfg.mask_max_len * l)
+    if l < 0 or (max_res_num is not None and l > max_res_num):
+        raise T2PError(f"a sample of {l} residues lies outside [0, {max_res_num}]")
+    if not 0 <= lo < hi <= l:
+        raise T2PError(f"a sample of {l} residues has the empty or misplaced range [{lo}, {hi}) for its number of masked residues "
+                       f"(mask_min_len = {inpainting_cfg.mask_min_len}, mask_max_len = {inpainting_cfg.mask_max_len})")
+    return lo, hi
+
+
+def random_mask_batch(batch, config):
+    """utils.py:15-60, which train.py calls before every train and eval step (train.py:176, :193): adds ``mask_inpaint`` (B, N, N) bool
+    on ``config.device``; None when ``inpainting`` is not in the condition.
+
+    The calls into ``random`` and ``torch`` are the reference's, in its order, on the CPU default generator: one ``random.random()`` per
+    batch picks random / contiguous / no masking, then per sample ``torch.randint(int(min l), int(max l), (1,))`` and
+    ``torch.randperm(l)`` (random) or ``torch.randint(0, l - r, (1,))`` (contiguous).  After the same ``random.seed`` and
+    ``torch.manual_seed`` the mask is the reference's bit for bit.  Every range is checked before the first draw, so a refused batch
+    (``T2PError``) consumes no random number."""
+    if "inpainting" not in config.model.condition:
+        batch["mask_inpaint"] = None
+        return batch
+    cfg = config.model.get("inpainting")
+    if cfg is None:
+        raise ValueError("the inpainting condition needs mask_info (residue ranges such as '1:5,10:15') or, for a random mask, "
+                         "config.model.inpainting (random_mask_prob, contiguous_mask_prob, mask_min_len, mask_max_len)")
+    B, _, N, _ = batch["coords_6d"].shape
+    lengths = batch_lengths(batch)
+    if len(lengths) != B:
+        from ._lib import T2PError
+        raise T2PError(f"{len(lengths)} residue counts for a batch of {B} samples")
+    ranges = [mask_count_range(l, cfg, N) for l in lengths]
+    prob = random.random()
+    if prob < cfg.random_mask_prob:
+        mask = torch.zeros(B, N)
+        for b, (l, (lo, hi)) in enumerate(zip(lengths, ranges)):
+            r = torch.randint(lo, hi, (1,))[0]
+            mask[b, torch.randperm(l)[:r]] = 1
+    elif prob > 1 - cfg.contiguous_mask_prob:
+        mask = torch.zeros(B, N)
+        for b, (l, (lo, hi)) in enumerate(zip(lengths, ranges)):
+            r = int(torch.randint(lo, hi, (1,))[0])
+            start = int(torch.randint(0, l - r, (1,))[0])
+            mask[b, start:start + r] = 1
+    else:
+        mask = torch.ones(B, N)                       # the padding too: mask_pair removes it in the loss
+    batch["mask_inpaint"] = pair_mask(mask).to(device=config.device)
+    return batch
+
+
 def get_condition_from_batch(config, batch, mask_info=None):
     """utils.py:84-106 for a tensor batch: one entry per name in ``config.model.condition``.
 
     ``batch`` holds ``coords_6d`` (B, C, L, L) and the residue counts either as ``lengths`` (B ints) or as the
-    reference's ``aa_str`` (padded with "_").  ``inpainting`` needs ``mask_info`` (the reference's alternative, a random
-    mask drawn by ``random_mask_batch``, belongs to training)."""
+    reference's ``aa_str`` (padded with "_").  ``inpainting`` takes ``mask_info``; without it the mask is drawn by
+    ``random_mask_batch`` (utils.py:99-100), which needs ``config.model.inpainting``."""
     coords = batch["coords_6d"]
     B, L = coords.shape[0], config.data.max_res_num
     out = {}
@@ -76,8 +144,9 @@ def get_condition_from_batch(config, batch, mask_info=None):
             out[name] = coords[:, 4:7]
         elif name == "inpainting":
             if mask_info is None:
-                raise ValueError("the inpainting condition needs mask_info (residue ranges such as '1:5,10:15')")
-            out[name] = {"coords_6d": coords, "mask_inpaint": pair_mask(parse_mask_info(mask_info, B, L))}
+                out[name] = {"coords_6d": coords, "mask_inpaint": random_mask_batch(dict(batch), config)["mask_inpaint"]}
+            else:
+                out[name] = {"coords_6d": coords, "mask_inpaint": pair_mask(parse_mask_info(mask_info, B, L))}
         else:
             raise ValueError(f"unknown condition {name!r}")
     return out

@@ -17,8 +17,13 @@
 //   Trainer (train.h)         times t       trainer seed   training  rng_t()  = calls             -           sample b  word 0: t = eps + (1 - eps) u
 //                             noise z       trainer seed   sampling  rng_z()  = 4096 calls + 1    0           quad q    normals
 //                             ss blocks     trainer seed   training  rng_ss() = 4096 calls + 2    -           block k   word 0: dropped when u < p
+//                             inpaint mask  trainer seed   training  rng_inpaint() = 4096 calls + 3  -        0         word 0: the mode (random / contiguous / none)
+//                                                                                                               (b + 1) 2^32       sample b, word 0: r = lo + (((w >> 8) (hi - lo)) >> 24),
+//                                                                                                                                  word 1: start = ((w >> 8) (l - r)) >> 24
+//                                                                                                               (b + 1) 2^32 + 1 + j   word 0: the 32-bit key of residue j (the r lowest are masked)
 //                             Dropout_0 k   trainer seed   training  rng_dropout(k)               -           quad q    4 words: element 4 q + j kept
 //                                                                      = 4096 calls + 16 + k                            when u_j >= p
+//   t2p_op_inpaint_mask_draw                caller's seed  training  caller's                     -           as the trainer's inpaint mask
 //   (calls = Trainer::loss_calls_, the number of loss calls completed before the running one.)
 //
 // Two known defects, recorded here and left as they are (fixing either changes drawn bits):

@@ -291,6 +291,38 @@ int Trainer::set_ss_blocks(const int32_t* host_blocks, int n, const uint8_t* hos
   ss_n_ = n; ss_max_sample_ = max_sample; ss_given_ = host_drop != nullptr; ss_p_ = p;
   return T2P_OK;
 }
+int check_inpaint_draw(const char* who, const int32_t* host_len_lo_hi, int B, int L, double random_p, double contiguous_p) {
+  const std::string w(who);
+  T2P_REQUIRE(random_p >= 0.0 && random_p <= 1.0 && contiguous_p >= 0.0 && contiguous_p <= 1.0,
+              w + ": random_mask_prob and contiguous_mask_prob must lie in [0, 1]");
+  T2P_REQUIRE(random_p + contiguous_p <= 1.0, w + ": random_mask_prob + contiguous_mask_prob must not exceed 1");
+  for (int b = 0; b < B; ++b) {
+    const int32_t l = host_len_lo_hi[3 * b], lo = host_len_lo_hi[3 * b + 1], hi = host_len_lo_hi[3 * b + 2];
+    T2P_REQUIRE(l >= 0 && l <= L, w + ": sample " + std::to_string(b) + " has " + std::to_string(l) + " residues, outside [0, " + std::to_string(L) + "]");
+    T2P_REQUIRE(lo >= 0 && lo < hi && hi <= l, w + ": sample " + std::to_string(b) + " (" + std::to_string(l) + " residues) has the empty or misplaced range [" +
+                                                   std::to_string(lo) + ", " + std::to_string(hi) + ") for its number of masked residues (0 <= lo < hi <= l)");
+  }
+  return T2P_OK;
+}
+int Trainer::set_inpaint_draw(const int32_t* host_len_lo_hi, int B, double random_p, double contiguous_p) {
+  T2P_REQUIRE(B >= 0 && (B == 0 || host_len_lo_hi), "set_inpaint_draw arguments");
+  if (B == 0) { inp_n_ = 0; return T2P_OK; }
+  T2P_REQUIRE(tc_.cond_flags & 4, "set_inpaint_draw: this trainer was created without the inpainting condition (cond_flags bit 4)");
+  T2P_REQUIRE(mc_.max_res_num <= 256, "set_inpaint_draw: the device draw counts ranks in LDS, max_res_num <= 256");
+  T2P_TRY(check_inpaint_draw("set_inpaint_draw", host_len_lo_hi, B, mc_.max_res_num, random_p, contiguous_p));
+  // as set_ss_blocks: no pass is in flight here, the buffer is free to overwrite
+  if (B > inp_cap_) {
+    const int cap = std::max(B, 2 * inp_cap_);
+    int* nb = (int*)pool_.get((size_t)cap * 12);
+    if (!nb) return T2P_ERR_HIP;
+    if (inp_llh_) pool_.put(inp_llh_);
+    inp_llh_ = nb; inp_cap_ = cap; inp_n_ = 0;        // (the request in the old buffer goes with it)
+  }
+  inp_n_ = 0;                                         // a failed copy leaves no request
+  T2P_HIP_CHECK(hipMemcpy(inp_llh_, host_len_lo_hi, (size_t)B * 12, hipMemcpyHostToDevice));
+  inp_n_ = B; inp_p_random_ = (float)random_p; inp_contig_above_ = (float)(1.0 - contiguous_p);
+  return T2P_OK;
+}
 
 // ---- pass-local memory ------------------------------------------------------------------------------------------------------------------
 float* Trainer::tmp(size_t bytes) {
@@ -696,7 +728,7 @@ int Trainer::run_layers(const std::vector<LayerT>& ls, TT* h, TT* stemb, TT* ctx
 int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool train, bool backward, float* loss_dev, float* score_out) {
   const int B = b.batch, L = mc_.max_res_num, HW = L * L, Cx = mc_.num_channels, nf = mc_.nf;
   T2P_REQUIRE(b.coords_6d && b.mask_pair && b.context && B > 0 && b.tokens > 0, "training batch");
-  T2P_REQUIRE(!(tc_.cond_flags & 4) || b.mask_inpaint, "the inpainting condition needs batch.mask_inpaint");
+  T2P_REQUIRE(!(tc_.cond_flags & 4) || b.mask_inpaint || inp_pass_n_ > 0, "the inpainting condition needs batch.mask_inpaint");
   T2P_REQUIRE(!(tc_.cond_flags & 2) || Cx >= 7, "the ss condition needs the 8-channel layout");
   Pc_ = P;
   drop_index_ = 0;
@@ -736,7 +768,17 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool tra
     T2P_TRY(launch_ss_block_rows(ss_blocks_, ss_pass_n_, ss_given_ ? ss_drop_ : nullptr, (float)ss_p_, tc_.seed, rng_ss(), B, L, ss_rows,
                                  nullptr, s_));
   }
-  T2P_TRY(launch_dsm_perturb(b.coords_6d, z, stdv, mean_coef, b.mask_pair, b.mask_inpaint, tc_.cond_flags, B, Cx, L, perturbed, mask, num_elem, s_,
+  // random_mask_batch (utils.py:15-60; train.py:176, :193): a batch without mask_inpaint and a request for this pass -- the mask is drawn
+  // here and goes where batch.mask_inpaint goes
+  const uint8_t* mask_inpaint = b.mask_inpaint;
+  if (inp_pass_n_ > 0) {
+    uint8_t* drawn = (uint8_t*)tmp((size_t)B * L + (size_t)B * HW);      // [B][L] residue flags, then the [B][L][L] pair mask
+    if (!drawn) return T2P_ERR_HIP;
+    T2P_TRY(launch_inpaint_mask_draw(inp_llh_, B, L, inp_p_random_, inp_contig_above_, tc_.seed, rng_inpaint(), -1, drawn, drawn + (size_t)B * L,
+                                     nullptr, s_));
+    mask_inpaint = drawn + (size_t)B * L;
+  }
+  T2P_TRY(launch_dsm_perturb(b.coords_6d, z, stdv, mean_coef, b.mask_pair, mask_inpaint, tc_.cond_flags, B, Cx, L, perturbed, mask, num_elem, s_,
                              ss_rows));
 
   // UNetModel.forward (ncsnpp.py:220-263)
@@ -824,6 +866,12 @@ int Trainer::loss(const t2p_train_batch& b, bool backward, bool use_ema, float* 
   T2P_REQUIRE(loss_host, "loss output");
   ss_pass_n_ = ss_n_;                             // the block list is per-batch data: this pass consumes it, whatever becomes of the pass
   ss_n_ = 0;
+  const int inp_request = inp_n_;                 // so is the random-mask request; a batch that supplies mask_inpaint ignores it
+  inp_pass_n_ = b.mask_inpaint ? 0 : inp_n_;
+  inp_n_ = 0;
+  T2P_REQUIRE(inp_pass_n_ == 0 || inp_pass_n_ == b.batch,
+              "inpaint draw: the request holds " + std::to_string(inp_request) + " samples, the batch " + std::to_string(b.batch) +
+                  "; nothing was computed or changed and the request is cleared");
   T2P_REQUIRE(ss_pass_n_ == 0 || ss_max_sample_ < b.batch,
               "ss blocks: sample index " + std::to_string(ss_max_sample_) + " >= batch " + std::to_string(b.batch) +
                   "; nothing was computed or changed and the block list is cleared");

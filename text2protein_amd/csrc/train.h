@@ -56,6 +56,9 @@ class Trainer {
   // block_dropout (losses.py:54-64, called at :106-107) of the NEXT loss / step / eval pass: host int32 [n][3] = (sample, start, end) and
   // the per-block decisions (host uint8 [n]) or nullptr = drawn on the device at probability p.  Consumed by that pass, then cleared
   int set_ss_blocks(const int32_t* host_blocks, int n, const uint8_t* host_drop, double p);
+  // random_mask_batch (utils.py:15-60) of the NEXT loss / step / eval pass whose batch carries no mask_inpaint: host int32 [B][3] =
+  // (l, lo, hi) per sample and the two mode probabilities.  That pass draws the mask on the device and consumes the request; B = 0 clears it
+  int set_inpaint_draw(const int32_t* host_len_lo_hi, int B, double random_p, double contiguous_p);
   // loss_fn (losses.py:105-134); with `backward` also d loss / d parameters into the gradient buffer (zeroed first: optimizer.zero_grad())
   int loss(const t2p_train_batch& b, bool backward, bool use_ema, float* loss_host, float* score_out, hipStream_t s);
   // step_fn with train=True (losses.py:165-176) = loss(backward) + apply()
@@ -92,6 +95,8 @@ class Trainer {
   unsigned long long rng_dropout(int k) const { return (unsigned long long)(loss_calls_ * 4096 + 16 + k); }
   // the block-dropout decisions of the running loss call (counter = the block index); + 2 of the free ids + 2 .. + 15
   unsigned long long rng_ss() const { return (unsigned long long)(loss_calls_ * 4096 + 2); }
+  // the random inpainting mask of the running loss call (counter indices: philox.h); + 3 of the free ids
+  unsigned long long rng_inpaint() const { return (unsigned long long)(loss_calls_ * 4096 + 3); }
 
   // forward ops: each appends its backward to tape_
   TT* act(int B, int H, int W, int C, bool needs_grad = true);
@@ -146,6 +151,11 @@ class Trainer {
   bool ss_given_ = false;           // explicit decisions (else drawn on the device at ss_p_)
   double ss_p_ = 0.0;
   int ss_pass_n_ = 0;               // the running pass: how many blocks it took over (0: none, the kernels of a pass without blocks)
+  // random inpainting mask of the next pass (set_inpaint_draw): device int32 [cap][3] = (l, lo, hi)
+  int* inp_llh_ = nullptr;
+  int inp_cap_ = 0, inp_n_ = 0;     // inp_n_: the batch size of the request, 0 = none
+  float inp_p_random_ = 0.f, inp_contig_above_ = 1.f;   // (float)random_p, (float)(1.0 - contiguous_p)
+  int inp_pass_n_ = 0;              // the running pass: the request it took over (0: none, or the batch supplies mask_inpaint)
 
   DevPool pool_;
   hipStream_t s_ = nullptr;
@@ -154,6 +164,10 @@ class Trainer {
   std::vector<void*> live_;
   std::vector<std::function<int()>> tape_;
 };
+
+// the refusals of t2p_train_set_inpaint_draw / t2p_op_inpaint_mask_draw: probabilities in [0, 1] with a sum <= 1; per sample
+// 0 <= l <= L and 0 <= lo < hi <= l (torch.randint(lo, hi) raises on an empty range: utils.py:34)
+int check_inpaint_draw(const char* who, const int32_t* host_len_lo_hi, int B, int L, double random_p, double contiguous_p);
 
 }  // namespace t2p
 

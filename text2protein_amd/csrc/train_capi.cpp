@@ -123,6 +123,13 @@ int t2p_train_set_ss_blocks(t2p_trainer* t, const int32_t* host_blocks, int n, c
   API_END
 }
 
+int t2p_train_set_inpaint_draw(t2p_trainer* t, const int32_t* host_len_lo_hi, int B, double random_p, double contiguous_p) {
+  API_BEGIN
+  T2P_REQUIRE(t, "null trainer");
+  return t->impl.set_inpaint_draw(host_len_lo_hi, B, random_p, contiguous_p);
+  API_END
+}
+
 int t2p_train_loss(t2p_trainer* t, const t2p_train_batch* batch, int backward, float* loss_host, float* score_out, void* stream) {
   API_BEGIN
   T2P_REQUIRE(t && batch, "null argument");
@@ -237,6 +244,42 @@ int t2p_op_ss_block_dropout(const float* x, float* out, int batch, int C, int L,
   (void)hipStreamSynchronize(s);                                         // host_blocks / host_drop and the scratch are free after the call
   (void)hipFree(ws);
   return rc;
+  API_END
+}
+
+// random_mask_batch's draw alone, through the kernel of the training pass.  Drawn into scratch and copied out after the kernel completed, so
+// a call that fails leaves flags_out / pair_out / mode_out_host as they were
+int t2p_op_inpaint_mask_draw(const int32_t* host_len_lo_hi, int B, int L, double random_p, double contiguous_p, uint64_t seed, uint64_t stream_id,
+                             int force_mode, uint8_t* flags_out, uint8_t* pair_out, int* mode_out_host, void* stream) {
+  API_BEGIN
+  T2P_REQUIRE(host_len_lo_hi && B > 0 && B <= 65535 && L > 0 && flags_out && pair_out, "inpaint_mask_draw arguments");
+  T2P_REQUIRE(L <= 256, "inpaint_mask_draw: the device draw counts ranks in LDS, L <= 256");
+  T2P_REQUIRE(force_mode >= -1 && force_mode <= 2, "inpaint_mask_draw: force_mode is -1 (drawn), 0 (none), 1 (random) or 2 (contiguous)");
+  T2P_TRY(check_inpaint_draw("inpaint_mask_draw", host_len_lo_hi, B, L, random_p, contiguous_p));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n_flags = (size_t)B * L, n_pair = n_flags * L, o_flags = 16, o_pair = o_flags + ((n_flags + 15) & ~(size_t)15),
+               o_llh = o_pair + ((n_pair + 15) & ~(size_t)15), total = o_llh + (size_t)B * 12;     // [mode | flags | pair | (l, lo, hi)]
+  char* ws = nullptr;
+  T2P_HIP_CHECK(hipMalloc(&ws, total));
+  int rc = T2P_OK, mode = -1;
+  hipError_t e = hipMemcpyAsync(ws + o_llh, host_len_lo_hi, (size_t)B * 12, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) {
+    rc = launch_inpaint_mask_draw((const int*)(ws + o_llh), B, L, (float)random_p, (float)(1.0 - contiguous_p), seed, stream_id, force_mode,
+                                  (unsigned char*)(ws + o_flags), (unsigned char*)(ws + o_pair), (int*)ws, s);
+    if (rc == T2P_OK) e = hipMemcpyAsync(&mode, ws, 4, hipMemcpyDeviceToHost, s);
+    if (rc == T2P_OK && e == hipSuccess) e = hipStreamSynchronize(s);
+    if (rc == T2P_OK && e == hipSuccess) e = hipMemcpyAsync(flags_out, ws + o_flags, n_flags, hipMemcpyDeviceToDevice, s);
+    if (rc == T2P_OK && e == hipSuccess) e = hipMemcpyAsync(pair_out, ws + o_pair, n_pair, hipMemcpyDeviceToDevice, s);
+  }
+  const hipError_t e2 = hipStreamSynchronize(s);                         // host_len_lo_hi and the scratch are free after the call
+  (void)hipFree(ws);
+  if (rc != T2P_OK) return rc;
+  if (e != hipSuccess || e2 != hipSuccess) {
+    set_last_error(std::string("inpaint_mask_draw: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+    return T2P_ERR_HIP;
+  }
+  if (mode_out_host) *mode_out_host = mode;
+  return T2P_OK;
   API_END
 }
 

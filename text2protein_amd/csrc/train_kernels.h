@@ -113,6 +113,16 @@ int launch_dsm_perturb(const float* x, const float* z, const float* std, const f
 // with counter k, stream id stream_id and key seed (the uniform of dsm_prepare's t).  drop_out (optional, [n]): the decisions used
 int launch_ss_block_rows(const int* blocks, int n, const unsigned char* drop, float p, unsigned long long seed, unsigned long long stream_id,
                          int B, int L, unsigned char* rows, unsigned char* drop_out, hipStream_t s);
+// random_mask_batch (utils.py:15-60) drawn on the device: flags [B][L] uint8 (1 = residue masked) and pair [B][L][L] uint8 =
+// flags[b][i] | flags[b][j], one workgroup per sample.  llh: device int32 [B][3] = (l, lo, hi), l valid residues, lo = int(min l),
+// hi = int(max l) from the host; the callers guarantee 0 <= lo < hi <= l <= L <= 256.  mode: force_mode when >= 0, else drawn from one
+// uniform u0: 1 (random subset) when u0 < p_random, 2 (contiguous window) when u0 > contig_above, else 0 (none: flags = 1 for all L,
+// the padding included).  Counter indices within stream_id (training layout, key seed): philox.h's table.  Per sample
+// r = lo + (((w0 >> 8) (hi - lo)) >> 24) residues are masked: the window start .. start + r with start = ((w1 >> 8) (l - r)) >> 24, or
+// the r residues whose 32-bit keys rank lowest among the l (ties to the lower index).  mode_out (optional): device int, the mode used
+int launch_inpaint_mask_draw(const int* llh, int B, int L, float p_random, float contig_above, unsigned long long seed,
+                             unsigned long long stream_id, int force_mode, unsigned char* flags, unsigned char* pair, int* mode_out,
+                             hipStream_t s);
 // o: the head convolution's output NHWC [B][L L][ldo]; scale[b]: the signed per-sample output scale of dsm_prepare; score = scale[b] o;
 // r = score std[b] + z; loss_sum[b] += sum mask r^2 (double);  d_o [B][L L][ld_do] = 2 r mask std scale / ((num_elem + 1e-8) B), pad columns zero
 int launch_dsm_loss(const float* o, long ldo, const float* z, const float* std, const float* scale, const unsigned char* mask,

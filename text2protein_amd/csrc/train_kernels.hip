@@ -1174,6 +1174,86 @@ int launch_ss_block_rows(const int* blocks, int n, const unsigned char* drop, fl
   return T2P_OK;
 }
 
+// ---- random inpainting mask (utils.py:15-60, called by train.py before every train and eval step) ----------------------------------------
+// grid B, 256 threads: thread j is residue j of sample blockIdx.x (L <= 256).  Counter indices within the stream (training layout):
+// 0 the mode (word 0); (b + 1) 2^32 sample b's count and window start (words 0, 1); (b + 1) 2^32 + 1 + j residue j's key (word 0).
+// Random subset: residue j is masked iff fewer than r of the l keys sort before its own (ties to the lower index), counted from LDS --
+// exactly r residues, every subset of that size equally likely.  PAIR4: L % 4 == 0 and pair 4-byte aligned, four pixels per store
+template <bool PAIR4>
+__global__ __launch_bounds__(256) void inpaint_mask_draw_kernel(const int* __restrict__ llh, const int L, const float p_random,
+                                                                const float contig_above, const unsigned long long seed,
+                                                                const unsigned long long stream_id, const int force_mode,
+                                                                unsigned char* __restrict__ flags, unsigned char* __restrict__ pair,
+                                                                int* __restrict__ mode_out) {
+  __shared__ uint32_t keys[256];
+  __shared__ __align__(4) unsigned char fl[256];
+  const int b = blockIdx.x, j = threadIdx.x;
+  int mode = force_mode;
+  uint32_t c[4];
+  if (mode < 0) {
+    philox_counter_training(c, 0, stream_id);
+    philox4x32_10(c, seed);
+    const float u0 = philox_uniform24(c[0]);
+    mode = u0 < p_random ? 1 : u0 > contig_above ? 2 : 0;
+  }
+  if (mode_out && b == 0 && j == 0) *mode_out = mode;
+  const int l = llh[3 * b], lo = llh[3 * b + 1], hi = llh[3 * b + 2];
+  const long base = (long)(b + 1) << 32;
+  philox_counter_training(c, base, stream_id);
+  philox4x32_10(c, seed);
+  const int r = lo + (int)(((unsigned long long)(c[0] >> 8) * (unsigned long long)(hi - lo)) >> 24);
+  const int start = (int)(((unsigned long long)(c[1] >> 8) * (unsigned long long)(l - r)) >> 24);
+  uint32_t key = 0;
+  if (mode == 1 && j < l) {
+    philox_counter_training(c, base + 1 + j, stream_id);
+    philox4x32_10(c, seed);
+    key = c[0];
+  }
+  keys[j] = key;
+  __syncthreads();
+  bool f = mode == 0;
+  if (mode == 2) f = j >= start && j < start + r;
+  if (mode == 1 && j < l) {
+    int rank = 0;
+    for (int i = 0; i < l; ++i) {
+      const uint32_t ki = keys[i];
+      rank += (ki < key || (ki == key && i < j)) ? 1 : 0;
+    }
+    f = rank < r;
+  }
+  fl[j] = f ? 1 : 0;
+  if (j < L) flags[(long)b * L + j] = f ? 1 : 0;
+  __syncthreads();
+  const int HW = L * L;
+  if (PAIR4) {
+    uint32_t* __restrict__ out = reinterpret_cast<uint32_t*>(pair + (long)b * HW);
+    const uint32_t* fl4 = reinterpret_cast<const uint32_t*>(fl);
+    for (int q = j; q < HW / 4; q += 256) {
+      const int row = (4 * q) / L, col4 = (4 * q - row * L) >> 2;     // L % 4 == 0: the four pixels share a row
+      out[q] = (fl[row] ? 0x01010101u : 0u) | fl4[col4];
+    }
+  } else {
+    for (int p = j; p < HW; p += 256) {
+      const int row = p / L;
+      pair[(long)b * HW + p] = fl[row] | fl[p - row * L];
+    }
+  }
+}
+int launch_inpaint_mask_draw(const int* llh, int B, int L, float p_random, float contig_above, unsigned long long seed,
+                             unsigned long long stream_id, int force_mode, unsigned char* flags, unsigned char* pair, int* mode_out,
+                             hipStream_t s) {
+  T2P_REQUIRE(llh && flags && pair && B > 0 && B <= 65535 && L > 0 && force_mode >= -1 && force_mode <= 2, "inpaint_mask_draw arguments");
+  T2P_REQUIRE(L <= 256, "inpaint_mask_draw: one thread per residue, ranks counted in LDS: max_res_num <= 256");
+  if (L % 4 == 0 && ((uintptr_t)pair & 3) == 0)
+    hipLaunchKernelGGL(inpaint_mask_draw_kernel<true>, dim3(B), dim3(256), 0, s, llh, L, p_random, contig_above, seed, stream_id, force_mode, flags,
+                       pair, mode_out);
+  else
+    hipLaunchKernelGGL(inpaint_mask_draw_kernel<false>, dim3(B), dim3(256), 0, s, llh, L, p_random, contig_above, seed, stream_id, force_mode, flags,
+                       pair, mode_out);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+
 // SS of dsm_perturb_kernel: the residue flags of the dropped blocks (SsRows), or none (NoSs: the kernel as it is without block dropout)
 struct NoSs {};
 struct SsRows { const unsigned char* rows; int L; };

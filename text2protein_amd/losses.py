@@ -96,6 +96,28 @@ def _check_draw(draw):
         raise ValueError(f"block_dropout_draw must be 'host' or 'device', not {draw!r}")
 
 
+def _check_inpaint_draw(draw):
+    if draw not in (None, "host", "device"):
+        raise ValueError(f"inpaint_mask_draw must be None, 'host' or 'device', not {draw!r}")
+
+
+def _draw_batch_inpaint_mask(model, batch, condition, draw):
+    """train.py:176 / :193: under the ``inpainting`` condition a batch WITHOUT ``mask_inpaint`` gets the reference's random mask --
+    ``"host"``: ``conditions.random_mask_batch`` on a copy of the batch (the reference's draws in its order); ``"device"``: the request of
+    ``set_inpaint_draw``, consumed by the pass that follows.  ``None``, another condition or a supplied mask: the batch as it is."""
+    if draw is None or "inpainting" not in (condition or []) or batch.get("mask_inpaint") is not None:
+        return batch
+    from . import conditions
+    try:
+        if draw == "host":
+            return conditions.random_mask_batch(dict(batch), model.config)
+        model.set_inpaint_draw(conditions.batch_lengths(batch), model.config.model.get("inpainting"))
+    except Exception:
+        model.set_ss_blocks([])                # no pass follows: a block list set for this batch must not reach the next one
+        raise
+    return batch
+
+
 class HipTrainModel:
     """The score network in training form: ``UNetModel`` + its optimizer state + its EMA, resident on one GPU.
 
@@ -249,6 +271,26 @@ class HipTrainModel:
         check(self.lib.t2p_train_set_ss_blocks(self._h, C.c_void_p(arr.ctypes.data) if n else None, n,
                                                C.c_void_p(d.ctypes.data) if d is not None and n else None, float(p)))
 
+    def set_inpaint_draw(self, lengths, inpainting_cfg):
+        """``random_mask_batch`` (utils.py:15-60) on the device for the NEXT ``loss`` / ``step`` / ``eval_loss`` whose batch carries no
+        ``mask_inpaint``; that pass consumes the request.  ``lengths``: the valid residues per sample; ``inpainting_cfg``:
+        ``config.model.inpainting`` (random_mask_prob, contiguous_mask_prob, mask_min_len, mask_max_len).  The number of masked residues
+        lies in ``[int(mask_min_len l), int(mask_max_len l))`` as in the reference; an empty range (``l = 1``) raises ``T2PError``.  The
+        draws come from the trainer's Philox, not from torch.  ``None`` / ``[]`` clears the request."""
+        from .conditions import mask_count_range
+        lengths = [] if lengths is None else [int(v) for v in torch.as_tensor(lengths).reshape(-1).tolist()]
+        if not lengths:
+            check(self.lib.t2p_train_set_inpaint_draw(self._h, None, 0, 0.0, 0.0))
+            return
+        if inpainting_cfg is None:
+            raise T2PError("set_inpaint_draw needs config.model.inpainting (random_mask_prob, contiguous_mask_prob, mask_min_len, mask_max_len)")
+        if max(abs(l) for l in lengths) > 2 ** 31 - 1:
+            raise T2PError("residue count out of the int32 range")
+        L = int(self.config.data.max_res_num)
+        arr = np.ascontiguousarray([(l,) + mask_count_range(l, inpainting_cfg, L) for l in lengths], dtype=np.int32)
+        check(self.lib.t2p_train_set_inpaint_draw(self._h, C.c_void_p(arr.ctypes.data), arr.shape[0], float(inpainting_cfg.random_mask_prob),
+                                                  float(inpainting_cfg.contiguous_mask_prob)))
+
     def _batch(self, batch, t=None, z=None):
         dev = self.device
         hold = [batch["coords_6d"].to(dev, torch.float32).contiguous(), batch["mask_pair"].to(dev, torch.uint8).contiguous(),
@@ -266,14 +308,15 @@ class HipTrainModel:
         return tb, hold
 
     def _pass_inputs(self, batch, t, z, need_weights=True):
-        """``_batch`` for a pass.  A pass that fails here never reaches the library, so a block list set for it (``set_ss_blocks``) is
-        cleared: it is this batch's data and must not reach whichever pass comes next."""
+        """``_batch`` for a pass.  A pass that fails here never reaches the library, so a block list (``set_ss_blocks``) or a random-mask
+        request (``set_inpaint_draw``) set for it is cleared: it is this batch's data and must not reach whichever pass comes next."""
         try:
             if need_weights and not self._loaded:
                 raise T2PError("load weights before training")
             return self._batch(batch, t, z)
         except Exception:
             self.lib.t2p_train_set_ss_blocks(self._h, None, 0, None, 0.0)
+            self.lib.t2p_train_set_inpaint_draw(self._h, None, 0, 0.0, 0.0)
             raise
 
     def loss(self, batch, t=None, z=None, backward=False, return_score=False):
@@ -448,16 +491,23 @@ class ExponentialMovingAverage:
         self.model.set_step(cur[0], ema_updates=int(state_dict["num_updates"]))
 
 
-def get_sde_loss_fn(sde, train, eps=1e-5, block_dropout=0.2, block_dropout_draw="host"):
+def get_sde_loss_fn(sde, train, eps=1e-5, block_dropout=0.2, block_dropout_draw="host", inpaint_mask_draw=None):
     """losses.py:66-136 for ``sde`` = VESDE, VPSDE or subVPSDE (the model takes the SDE on first use and keeps it).  ``batch["context"]`` holds the caption embedding (B, T, context_dim); with raw captions pass
     ``llm_components`` = a callable ``captions -> embedding`` (text2protein_amd.text_context.TextContextProducer).
 
     With ``"ss"`` in ``condition`` and ``batch["ss_indices"]`` present, every block is dropped with probability ``block_dropout``
     (losses.py:54-64, :106-107; train and eval alike).  ``block_dropout_draw="host"``: ``random.random()`` once per block in the
     reference's order, so the same ``random.seed`` drops the same blocks; ``"device"``: drawn on the GPU from the trainer seed.  A batch
-    without ``ss_indices`` has nothing dropped (the reference would raise ``KeyError``)."""
+    without ``ss_indices`` has nothing dropped (the reference would raise ``KeyError``).
+
+    ``inpaint_mask_draw``: with ``"inpainting"`` in ``condition`` and no ``batch["mask_inpaint"]``, the random mask that train.py draws
+    before every train and eval step (``utils.random_mask_batch``, train.py:176, :193) from ``config.model.inpainting`` and the residue
+    counts ``batch["lengths"]`` / ``batch["aa_str"]``.  ``"host"``: ``conditions.random_mask_batch``, the reference's ``random`` / ``torch``
+    draws in its order (the same seeds give its mask); ``"device"``: drawn on the GPU from the trainer seed
+    (``HipTrainModel.set_inpaint_draw``).  None (the default): no mask is drawn and such a batch is refused."""
     _sde_key(sde)
     _check_draw(block_dropout_draw)
+    _check_inpaint_draw(inpaint_mask_draw)
 
     def loss_fn(model, batch, condition=None, llm_components=None, t=None, z=None):
         model.set_sde(sde)
@@ -468,6 +518,7 @@ def get_sde_loss_fn(sde, train, eps=1e-5, block_dropout=0.2, block_dropout_draw=
                 raise T2PError("the batch holds no `context`; pass llm_components=TextContextProducer(...)")
             batch = dict(batch, context=llm_components(batch["caption"]))
         _set_batch_ss_blocks(model, batch, condition, block_dropout, block_dropout_draw)
+        batch = _draw_batch_inpaint_mask(model, batch, condition, inpaint_mask_draw)
         if train:
             return model.loss(batch, t=t, z=z, backward=False)
         return model.eval_loss(batch, t=t, z=z)
@@ -475,14 +526,15 @@ def get_sde_loss_fn(sde, train, eps=1e-5, block_dropout=0.2, block_dropout_draw=
     return loss_fn
 
 
-def get_step_fn(sde, train, optimize_fn=None, dist=None, block_dropout=0.2, block_dropout_draw="host"):
-    """losses.py:140-186.  ``block_dropout`` / ``block_dropout_draw``: as in ``get_sde_loss_fn`` (each rank drops the blocks of its shard).  ``dist`` (an initialised ``torch.distributed`` module, text2protein_amd.distributed.init_process_group):
+def get_step_fn(sde, train, optimize_fn=None, dist=None, block_dropout=0.2, block_dropout_draw="host", inpaint_mask_draw=None):
+    """losses.py:140-186.  ``block_dropout`` / ``block_dropout_draw`` / ``inpaint_mask_draw``: as in ``get_sde_loss_fn`` (each rank drops the blocks and draws the mask of its shard).  ``dist`` (an initialised ``torch.distributed`` module, text2protein_amd.distributed.init_process_group):
     data-parallel training, one process per GPU -- each rank takes its shard of the batch, the flat gradient buffer is averaged over
     the ranks with ONE all-reduce (RCCL over xGMI) and every rank applies the same update; the returned loss is the mean over the
     ranks.  With equal shards this is the reference's DataParallel step on the concatenated batch (the loss is a mean of per-sample
     terms, losses.py:128-131)."""
     _sde_key(sde)
     _check_draw(block_dropout_draw)
+    _check_inpaint_draw(inpaint_mask_draw)
     world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
 
     def step_fn(state, batch, condition=None, t=None, z=None):
@@ -499,6 +551,7 @@ def get_step_fn(sde, train, optimize_fn=None, dist=None, block_dropout=0.2, bloc
             if optimize_fn is not None:
                 optimize_fn(state["optimizer"], model.parameters(), step=state["step"])
             _set_batch_ss_blocks(model, batch, condition, block_dropout, block_dropout_draw)
+            batch = _draw_batch_inpaint_mask(model, batch, condition, inpaint_mask_draw)
             prev = model.get_step()
             model.set_step(state["step"])
             if world == 1:
@@ -524,6 +577,7 @@ def get_step_fn(sde, train, optimize_fn=None, dist=None, block_dropout=0.2, bloc
             state["step"] += 1
             return loss
         _set_batch_ss_blocks(model, batch, condition, block_dropout, block_dropout_draw)
+        batch = _draw_batch_inpaint_mask(model, batch, condition, inpaint_mask_draw)
         return model.eval_loss(batch, t=t, z=z)                  # ema.store / copy_to / loss / restore (losses.py:177-183)
 
     return step_fn

@@ -1,11 +1,17 @@
 """Time the training step (t2p_train_step: loss + backward + Adam + EMA) at a BASELINE model size.
 
     python tools/bench_train.py --config cond_length.yml --batch 8 --steps 5 [--tokens 64] [--dropout 0.1] [--dtype f32|f16|bf16] [--sde ve|vp|subvp]
-                                [--condition length,ss [--ss-blocks 64]]
+                                [--condition length,ss [--ss-blocks 64]] [--inpaint_draw host|device [--rounds 5]]
 
 --ss-blocks N: N synthetic secondary-structure blocks per step (8 residues each, spread over the samples and the 100 valid residues),
 dropped on the device at the reference's p = 0.2; needs the `ss` condition, which needs an 8-channel configuration
 (cond_length_inpainting.yml with --condition length,ss).
+
+--inpaint_draw host|device: the batch carries NO mask_inpaint; the random mask of the reference's training loop (utils.random_mask_batch,
+from config.model.inpainting and 100 valid residues per sample) is drawn before every step, on the host in the reference's order or on the
+device from the trainer's Philox; needs the `inpainting` condition (cond_length_inpainting.yml).  With --rounds R the same process times R
+rounds of --steps steps WITH A SUPPLIED MASK and R rounds with the drawn one, alternating, and reports every round of both
+(`supplied_ms_rounds`, `drawn_ms_rounds`); `ms_per_step` is then the median drawn round.
 
 Prints one JSON line: ms per step, samples/s, the loss sequence, device memory, and the achieved matrix rate against the peak of the
 compute dtype's MFMA (157.3 TFLOP/s f32, 2500 TFLOP/s f16 / bf16), counting a step as 3 x the forward pass AS EXECUTED (the text K / V projections are inside a training
@@ -39,6 +45,8 @@ def main():
     ap.add_argument("--sde", default="ve", choices=["ve", "vp", "subvp"], help="the SDE of the loss")
     ap.add_argument("--condition", default="", help="override model.condition, comma-separated (e.g. length,ss)")
     ap.add_argument("--ss-blocks", type=int, default=0, help="synthetic secondary-structure blocks per step, drawn on the device")
+    ap.add_argument("--inpaint_draw", default=None, choices=["host", "device"], help="draw the random inpainting mask before every step")
+    ap.add_argument("--rounds", type=int, default=1, help="with --inpaint_draw: rounds of supplied-mask steps and drawn-mask steps, alternating")
     a = ap.parse_args()
     from text2protein_amd import losses, sde_lib, synth
     from text2protein_amd.config import load_config
@@ -68,7 +76,10 @@ def main():
         sde = sde_lib.VESDE(sigma_min=cfg.model.sigma_min, sigma_max=cfg.model.sigma_max, N=cfg.model.num_scales)
     else:
         sde = (sde_lib.VPSDE if a.sde == "vp" else sde_lib.subVPSDE)(beta_min=cfg.model.beta_min, beta_max=cfg.model.beta_max, N=cfg.model.num_scales)
-    step_fn = losses.get_step_fn(sde, train=True, optimize_fn=losses.optimization_manager(cfg))
+    if a.inpaint_draw and "inpainting" not in (cfg.model.condition or []):
+        raise SystemExit("--inpaint_draw needs the inpainting condition (cond_length_inpainting.yml)")
+    step_fn = losses.get_step_fn(sde, train=True, optimize_fn=losses.optimization_manager(cfg), inpaint_mask_draw=a.inpaint_draw)
+    drawn_batch = dict({k: v for k, v in batch.items() if k != "mask_inpaint"}, lengths=[100] * B)      # no mask: the step draws it
     state = dict(model=model, optimizer=losses.get_optimizer(cfg, model.parameters()),
                  ema=losses.ExponentialMovingAverage(model.parameters(), decay=cfg.model.ema_rate), step=5000)
     blocks = [(k % B, (8 * (k // B)) % 96, (8 * (k // B)) % 96 + 8) for k in range(a.ss_blocks)]
@@ -78,21 +89,38 @@ def main():
     def one_step():
         if blocks:
             model.set_ss_blocks(blocks, drop=None, p=0.2)       # per-batch data: set before every step, consumed by it
-        return step_fn(state, batch, condition=cfg.model.condition)
+        return step_fn(state, drawn_batch if a.inpaint_draw else batch, condition=cfg.model.condition)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.time()
+        out = [fn() for _ in range(a.steps)]
+        torch.cuda.synchronize()
+        return (time.time() - t0) / a.steps, out
 
     seq = []
     for _ in range(a.warmup):
         seq.append(one_step())
-    torch.cuda.synchronize()
-    t0 = time.time()
-    for _ in range(a.steps):
-        seq.append(one_step())
-    torch.cuda.synchronize()
-    dt = (time.time() - t0) / a.steps
+    extra = {}
+    if a.inpaint_draw and a.rounds > 1:
+        for _ in range(a.warmup):
+            step_fn(state, batch, condition=cfg.model.condition)
+        supplied, drawn = [], []
+        for _ in range(a.rounds):
+            supplied.append(timed(lambda: step_fn(state, batch, condition=cfg.model.condition))[0] * 1e3)
+            d, out = timed(one_step)
+            drawn.append(d * 1e3)
+            seq += out
+        dt = sorted(drawn)[len(drawn) // 2] / 1e3
+        extra = {"supplied_ms_rounds": supplied, "drawn_ms_rounds": drawn, "supplied_median_ms": sorted(supplied)[len(supplied) // 2]}
+    else:
+        dt, out = timed(one_step)
+        seq += out
     gf = FWD_GFLOP.get(a.config, 0.0) * 3 * B
     out = {"metric": f"training step ({'fp32' if a.dtype == 'f32' else a.dtype})", "dtype": a.dtype, "sde": a.sde, "config": a.config, "batch": B, "L": L,
            "tokens": a.tokens, "ms_per_step": dt * 1e3, "samples_per_s": B / dt, "losses": [round(v, 5) for v in seq],
-           "device_GiB": model.device_bytes() / 2 ** 30, "channels": C, "condition": list(cfg.model.condition or []), "ss_blocks": len(blocks)}
+           "device_GiB": model.device_bytes() / 2 ** 30, "channels": C, "condition": list(cfg.model.condition or []), "ss_blocks": len(blocks),
+           "inpaint_draw": a.inpaint_draw, **extra}
     tf = gf / dt / 1e3
     if a.dtype == "f32":
         out.update(tflops_f32=tf, frac_of_f32_peak=tf / PEAK_TFLOPS["f32"])
