@@ -105,7 +105,8 @@ def test_update_operators_are_the_formula_bit_for_bit(n):
     (scale, alpha, x_coef) on and off x probability_flow, bit for bit against the float32 formula evaluated on the host in the
     stated rounding order.  n sits below, at and across the access width (4) and the block (256 threads x 4); an odd n makes the
     second destination, which starts at element n of the same allocation, unaligned (the element-by-element branch).  Then x_out
-    aliasing x, and o_u NULL against t2p_op_langevin_update / t2p_op_predictor."""
+    aliasing x, o_u NULL against t2p_op_langevin_update / t2p_op_predictor, and those two (the same kernels since the plain and
+    guided families became one) against the formula with s = o_c."""
     from text2protein_amd import _lib
     from text2protein_amd._lib import check, ptr, stream_ptr
     lib = _lib.load()
@@ -164,6 +165,23 @@ def test_update_operators_are_the_formula_bit_for_bit(n):
                                               1.0, 3.7, 1.0, pf, stream_ptr()))
             check(lib.t2p_op_predictor(ptr(dev["x"]), ptr(dev["oc"]), ptr(dev["z"]), m, xi, ptr(b), ptr(bm), n, 3.7, pf, stream_ptr()))
             assert torch.equal(bits(a), bits(b)) and torch.equal(bits(am), bits(bm)), (n, use_mask, pf)
+    # ... which now compares one kernel with itself: t2p_op_langevin_update / t2p_op_predictor against the formula with s = o_c,
+    # with and without the mask, and x_initial without a mask (accepted and ignored: the no-mask result)
+    plain = [("langevin", None, langevin_formula(h["x"], h["oc"], h["z"], [3.25, 71.5], bt, snr, 0.93))]
+    plain += [("predictor", pf, predictor_formula(h["x"], h["oc"], h["z"], 3.7, 1.0, pf)) for pf in (0, 1)]
+    for (kind, pf, (want, want_m)), (use_mask, use_xi) in itertools.product(plain, ((False, False), (True, True), (False, True))):
+        m, xi = ptr(dev["mask"]) if use_mask else None, ptr(dev["xi"]) if use_xi else None
+        b, bm = torch.full((n + 8,), SENT, device="cuda"), torch.full((n + 8,), SENT, device="cuda")
+        if kind == "langevin":
+            check(lib.t2p_op_langevin_update(ptr(dev["x"]), ptr(dev["oc"]), ptr(dev["z"]), m, xi, ptr(b), ptr(bm), n, ptr(sums), bt, snr, 0.93,
+                                             stream_ptr()))
+        else:
+            check(lib.t2p_op_predictor(ptr(dev["x"]), ptr(dev["oc"]), ptr(dev["z"]), m, xi, ptr(b), ptr(bm), n, 3.7, pf, stream_ptr()))
+        tag = (n, kind, pf, use_mask, use_xi)
+        want = np.where(free, want, h["xi"]) if use_mask else want
+        assert torch.equal(bits(b[:n]), bits(torch.from_numpy(want))), tag
+        assert torch.equal(bits(bm[:n]), bits(torch.from_numpy(want_m))), tag
+        assert bool((b[n:] == SENT).all()) and bool((bm[n:] == SENT).all()), tag
 
 
 @pytest.mark.parametrize("per_sample", [7, 1280, 16385])

@@ -586,6 +586,20 @@ int t2p_op_attention_qkv(int dtype, const void* qkv, int64_t ld, void* out, int 
   API_END
 }
 
+// the score block of the entries without guidance: s = grad (scale 1 is exact)
+static GuidedScore plain_score(const float* grad) {
+  GuidedScore g;
+  g.o_c = grad;
+  return g;
+}
+// their update arguments; x_initial without a mask was accepted and ignored before the update kernels required the pair
+static SdeUpdateArgs update_args(const float* x, const float* noise, const uint8_t* mask, const float* x_initial, float* x_out,
+                                 float* x_mean_out, int64_t n) {
+  SdeUpdateArgs a;
+  a.x = x; a.noise = noise; a.mask = mask; a.x_initial = mask ? x_initial : nullptr; a.x_out = x_out; a.x_mean_out = x_mean_out; a.n = n;
+  return a;
+}
+
 int t2p_op_langevin(const float* x, const float* grad, const float* noise, const uint8_t* mask, const float* x_initial,
                     float* x_out, float* x_mean_out, int batch, int64_t per_sample, float snr, float alpha,
                     float* sums_out, void* stream) {
@@ -594,13 +608,10 @@ int t2p_op_langevin(const float* x, const float* grad, const float* noise, const
   float* ws = nullptr;
   T2P_HIP_CHECK(hipMalloc((void**)&ws, ((size_t)batch * 64 * 2 + 64) * 4));
   float* sums = sums_out ? sums_out : ws + (size_t)batch * 64 * 2;
-  int rc = launch_langevin_norms(grad, noise, batch, per_sample, ws, sums, s);
-  if (rc == T2P_OK) {
-    SdeUpdateArgs a;
-    a.x = x; a.score = grad; a.noise = noise; a.mask = mask; a.x_initial = x_initial; a.x_out = x_out;
-    a.x_mean_out = x_mean_out; a.n = per_sample * batch;
-    rc = launch_langevin_update(a, sums, (float)batch, snr, alpha, s);
-  }
+  int rc = launch_langevin_norms(plain_score(grad), noise, batch, per_sample, ws, sums, 1, s);
+  if (rc == T2P_OK)
+    rc = launch_langevin_update(update_args(x, noise, mask, x_initial, x_out, x_mean_out, per_sample * batch), plain_score(grad), nullptr,
+                                sums, (float)batch, snr, alpha, s);
   (void)hipStreamSynchronize(s);
   (void)hipFree(ws);
   return rc;
@@ -610,7 +621,7 @@ int t2p_op_langevin(const float* x, const float* grad, const float* noise, const
 int t2p_op_langevin_norms(const float* grad, const float* noise, int batch, int64_t per_sample, float* workspace,
                           float* sums, void* stream) {
   API_BEGIN
-  return launch_langevin_norms(grad, noise, batch, per_sample, workspace, sums, (hipStream_t)stream);
+  return launch_langevin_norms(plain_score(grad), noise, batch, per_sample, workspace, sums, 1, (hipStream_t)stream);
   API_END
 }
 
@@ -618,20 +629,16 @@ int t2p_op_langevin_update(const float* x, const float* grad, const float* noise
                            const float* x_initial, float* x_out, float* x_mean_out, int64_t n, const float* sums,
                            float batch_total, float snr, float alpha, void* stream) {
   API_BEGIN
-  SdeUpdateArgs a;
-  a.x = x; a.score = grad; a.noise = noise; a.mask = mask; a.x_initial = x_initial; a.x_out = x_out;
-  a.x_mean_out = x_mean_out; a.n = n;
-  return launch_langevin_update(a, sums, batch_total, snr, alpha, (hipStream_t)stream);
+  return launch_langevin_update(update_args(x, noise, mask, x_initial, x_out, x_mean_out, n), plain_score(grad), nullptr, sums,
+                                batch_total, snr, alpha, (hipStream_t)stream);
   API_END
 }
 
 int t2p_op_predictor(const float* x, const float* score, const float* noise, const uint8_t* mask, const float* x_initial,
                      float* x_out, float* x_mean_out, int64_t n, float G, int probability_flow, void* stream) {
   API_BEGIN
-  SdeUpdateArgs a;
-  a.x = x; a.score = score; a.noise = noise; a.mask = mask; a.x_initial = x_initial; a.x_out = x_out;
-  a.x_mean_out = x_mean_out; a.n = n;
-  return launch_predictor_update(a, nullptr, nullptr, G, probability_flow, (hipStream_t)stream);
+  return launch_predictor_update(update_args(x, noise, mask, x_initial, x_out, x_mean_out, n), plain_score(score), nullptr, nullptr, G,
+                                 probability_flow, (hipStream_t)stream);
   API_END
 }
 
@@ -640,7 +647,7 @@ int t2p_op_guided_langevin_norms(const float* o_c, const float* o_u, const float
   API_BEGIN
   GuidedScore g;
   g.o_c = o_c; g.o_u = o_u; g.w = w; g.w1 = w1; g.scale = scale;
-  return launch_guided_langevin_norms(g, noise, batch, per_sample, workspace, sums, (hipStream_t)stream);
+  return launch_langevin_norms(g, noise, batch, per_sample, workspace, sums, 4, (hipStream_t)stream);
   API_END
 }
 
@@ -652,7 +659,7 @@ int t2p_op_guided_langevin_update(const float* x, const float* o_c, const float*
   a.x = x; a.noise = noise; a.mask = mask; a.x_initial = x_initial; a.x_out = x_out; a.x_mean_out = x_mean_out; a.n = n;
   GuidedScore g;
   g.o_c = o_c; g.o_u = o_u; g.w = w; g.w1 = w1; g.scale = scale;
-  return launch_guided_langevin_update(a, g, x_out2, sums, batch_total, snr, alpha, (hipStream_t)stream);
+  return launch_langevin_update(a, g, x_out2, sums, batch_total, snr, alpha, (hipStream_t)stream);
   API_END
 }
 
@@ -664,7 +671,7 @@ int t2p_op_guided_predictor(const float* x, const float* o_c, const float* o_u, 
   a.x = x; a.noise = noise; a.mask = mask; a.x_initial = x_initial; a.x_out = x_out; a.x_mean_out = x_mean_out; a.n = n;
   GuidedScore g;
   g.o_c = o_c; g.o_u = o_u; g.w = w; g.w1 = w1; g.scale = scale;
-  return launch_guided_predictor_update(a, g, x_out2, nullptr, G, probability_flow, (hipStream_t)stream, nullptr, x_coef);
+  return launch_predictor_update(a, g, x_out2, nullptr, G, probability_flow, (hipStream_t)stream, nullptr, x_coef);
   API_END
 }
 

@@ -3,20 +3,16 @@
 // sum, the clean-sample prediction, its static clipping, the DDIM move, the conditional re-masking and the noise draw; the
 // host loop (class Ddim) evaluates the network ONCE per step on [x ; x] under the context [ctx ; 0] at batch 2B.
 #include "ddim.h"
-#include "philox.h"
+#include "update_loop.h"
 
 #include <cmath>
 
 namespace t2p {
 
-// one element, rounded where the reference's float32 tensor expressions round (diffusion_sampler.py:128, 141-142, 133, 110-112)
-__device__ inline float ddim_element(const DdimUpdateArgs& a, float x, float ec, float eu, float z, float* x0_out) {
+// one element, rounded where the reference's float32 tensor expressions round (diffusion_sampler.py:141-142, 133, 110-112); eps is
+// the guidance sum w eps_c + w1 eps_u of update_loop.h's guided_score at scale 1 (diffusion_sampler.py:128)
+__device__ inline float ddim_element(const DdimUpdateArgs& a, float x, float eps, float z, float* x0_out) {
 #pragma clang fp contract(off)
-  float eps = ec;
-  if (a.eps_u) {
-    const float pc = a.w * ec, pu = a.w1 * eu;
-    eps = pc + pu;
-  }
   const float px = a.sqrt_recip * x, pe = a.sqrt_recipm1 * eps;
   float x0 = px - pe;
   if (a.clip) x0 = x0 < -1.f ? -1.f : (x0 > 1.f ? 1.f : x0);     // torch.clamp: a NaN stays a NaN
@@ -27,60 +23,18 @@ __device__ inline float ddim_element(const DdimUpdateArgs& a, float x, float ec,
   return s01 + t2;
 }
 
-// One thread per quad of consecutive elements (the unit of a Philox draw).  VEC: every pointer is 16-byte aligned (the mask
-// 4-byte) and n % 4 == 0, so the quad moves as one 16-byte access per tensor; otherwise element by element, bounded by n.
+// The quad loop of update_loop.h with ddim_element as its update and x0 as its second output.  z: the given draws; nothing on the
+// last step; else drawn in the loop, unless sigma == 0 (the term is sigma * 0, nothing is drawn).
 template <bool VEC>
 __global__ __launch_bounds__(256) void ddim_update_kernel(DdimUpdateArgs a) {
-  const long nq = (a.n + 3) / 4;
-  const bool mid = !a.last;
-  const bool draw = mid && !a.z && a.sigma != 0.f;     // sigma == 0: the term is sigma * 0, nothing is drawn
-  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
-    const long i = q * 4;
-    const int cnt = VEC ? 4 : (int)(a.n - i < 4 ? a.n - i : 4);
-    alignas(16) float x[4], ec[4], eu[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f}, xi[4] = {0.f, 0.f, 0.f, 0.f};
-    alignas(4) unsigned char m[4] = {1, 1, 1, 1};
-    if (VEC) {
-      *(float4*)x = *(const float4*)(a.x + i);
-      *(float4*)ec = *(const float4*)(a.eps_c + i);
-      if (a.eps_u) *(float4*)eu = *(const float4*)(a.eps_u + i);
-      if (mid && a.z) *(float4*)z = *(const float4*)(a.z + i);
-      if (a.mask) {
-        *(uchar4*)m = *(const uchar4*)(a.mask + i);
-        *(float4*)xi = *(const float4*)(a.x_initial + i);
-      }
-    } else {
-      for (int k = 0; k < cnt; ++k) {
-        x[k] = a.x[i + k];
-        ec[k] = a.eps_c[i + k];
-        if (a.eps_u) eu[k] = a.eps_u[i + k];
-        if (mid && a.z) z[k] = a.z[i + k];
-        if (a.mask) { m[k] = a.mask[i + k]; xi[k] = a.x_initial[i + k]; }
-      }
-    }
-    if (draw) {     // the draw of t2p_op_philox_normal(seed, stream_id) for this quad (step word 0)
-      uint32_t c[4];
-      philox_counter_sampling(c, q, a.stream_id, 0u);
-      philox4x32_10(c, a.seed);
-      philox_normal4(c, z);
-    }
-    alignas(16) float xn[4], x0[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      xn[k] = ddim_element(a, x[k], ec[k], eu[k], z[k], &x0[k]);
-      if (!m[k]) xn[k] = xi[k];
-    }
-    if (VEC) {
-      *(float4*)(a.x_out + i) = *(const float4*)xn;
-      if (a.x_out2) *(float4*)(a.x_out2 + i) = *(const float4*)xn;
-      if (a.x0_out) *(float4*)(a.x0_out + i) = *(const float4*)x0;
-    } else {
-      for (int k = 0; k < cnt; ++k) {
-        a.x_out[i + k] = xn[k];
-        if (a.x_out2) a.x_out2[i + k] = xn[k];
-        if (a.x0_out) a.x0_out[i + k] = x0[k];
-      }
-    }
-  }
+  SdeUpdateArgs u;
+  u.x = a.x; u.noise = a.last ? nullptr : a.z; u.mask = a.mask; u.x_initial = a.x_initial; u.x_out = a.x_out; u.x_mean_out = a.x0_out;
+  u.n = a.n;
+  GuidedScore g;
+  g.o_c = a.eps_c; g.o_u = a.eps_u; g.w = a.w; g.w1 = a.w1;
+  QuadDraw d;
+  d.on = !a.last && !a.z && a.sigma != 0.f; d.seed = a.seed; d.stream_id = a.stream_id;
+  update_loop<VEC, true>(u, g, a.x_out2, d, [=](float x, float eps, float z, float* x0) { return ddim_element(a, x, eps, z, x0); });
 }
 
 int launch_ddim_update(const DdimUpdateArgs& a, hipStream_t s) {
@@ -88,12 +42,11 @@ int launch_ddim_update(const DdimUpdateArgs& a, hipStream_t s) {
   T2P_REQUIRE((a.mask == nullptr) == (a.x_initial == nullptr), "mask and x_initial go together");
   T2P_REQUIRE(a.clip == 0 || a.clip == 1, "clip is 0 or 1");
   T2P_REQUIRE(a.last == 0 || a.last == 1, "last is 0 or 1");
-  auto al = [](const void* p, uintptr_t k) { return ((uintptr_t)p % k) == 0; };   // a null pointer counts as aligned
-  const bool vec = a.n % 4 == 0 && al(a.x, 16) && al(a.eps_c, 16) && al(a.eps_u, 16) && al(a.z, 16) && al(a.mask, 4) &&
-                   al(a.x_initial, 16) && al(a.x_out, 16) && al(a.x_out2, 16) && al(a.x0_out, 16);
   const dim3 grid(ew_grid((a.n + 3) / 4));
-  if (vec) hipLaunchKernelGGL(ddim_update_kernel<true>, grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(ddim_update_kernel<false>, grid, dim3(256), 0, s, a);
+  if (quad_vec_ok(a.n, {a.x, a.eps_c, a.eps_u, a.z, a.x_initial, a.x_out, a.x_out2, a.x0_out}, a.mask))
+    hipLaunchKernelGGL(ddim_update_kernel<true>, grid, dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL(ddim_update_kernel<false>, grid, dim3(256), 0, s, a);
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }

@@ -3,8 +3,7 @@
 // wavefronts read 16-byte vectors of consecutive channels (coalesced 1 KiB per wave-instruction).
 #include "philox.h"
 #include "t2p_kernels.h"
-
-#include <initializer_list>
+#include "update_loop.h"
 
 namespace t2p {
 
@@ -1395,18 +1394,50 @@ int launch_small_linear(const float* in, const float* W, const float* bias, floa
 }
 
 // ================================== SDE update ===============================================================
+// Every kernel here reads the score as s = scale (w o_c + w1 o_u) (GuidedScore; update_loop.h), formed per element: o_u null and
+// scale 1 is the network output itself, the plain VE step; the VP scale (-1 / std) and the guidance sum ride in the same kernels.
 static constexpr int NORM_BLOCKS = 64;   // partial blocks per sample
 
-__global__ __launch_bounds__(256) void langevin_sq_kernel(const float* grad, const float* noise, long per_sample, float* sq_ws) {
+// per-sample squared norms of s and z: thread t of block blk sums the groups of W consecutive elements at group indices
+// blk * 256 + t + j * 16384, in that order, one FMA per element.  Both traversals are observable in the last bits of the Langevin
+// step size and each is pinned by recorded fixtures: W = 1 by the runs of the plain sampler (tests/golden/cli_default_parent.npz,
+// pc_update_parent.npz), W = 4 by the guided ones (pc_update_parent.npz).  VEC (W = 4): one 16-byte load per tensor and group.
+template <int W, bool VEC>
+__global__ __launch_bounds__(256) void langevin_sq_kernel(GuidedScore g, const float* noise, long per_sample, float* sq_ws) {
+  static_assert(W == 1 || W == 4, "group width");
+  static_assert(!VEC || W == 4, "the 16-byte path moves quads");
   __shared__ float red[2][4];
   const int b = blockIdx.y, blk = blockIdx.x;
-  const float* g = grad + (long)b * per_sample;
+  const float* oc = g.o_c + (long)b * per_sample;
+  const float* ou = g.o_u ? g.o_u + (long)b * per_sample : nullptr;
   const float* z = noise + (long)b * per_sample;
+  const float scale = guided_scale(g);
+  const long nq = (per_sample + W - 1) / W;
   float sg = 0.f, sz = 0.f;
-  for (long i = (long)blk * 256 + threadIdx.x; i < per_sample; i += (long)NORM_BLOCKS * 256) {
-    const float a = g[i], c = z[i];
-    sg += a * a;
-    sz += c * c;
+  for (long q = (long)blk * 256 + threadIdx.x; q < nq; q += (long)NORM_BLOCKS * 256) {
+    const long i = q * W;
+    const int cnt = (VEC || W == 1) ? W : (int)(per_sample - i < W ? per_sample - i : W);
+    alignas(16) float c[W] = {}, u[W] = {}, n[W] = {};
+    if constexpr (VEC) {
+      *(float4*)c = *(const float4*)(oc + i);
+      if (ou) *(float4*)u = *(const float4*)(ou + i);
+      *(float4*)n = *(const float4*)(z + i);
+    } else {
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        if (k < cnt) {
+          c[k] = oc[i + k];
+          if (ou) u[k] = ou[i + k];
+          n[k] = z[i + k];
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < W; ++k) {     // the padding of a short tail group is zero: it adds nothing
+      const float sk = k < cnt ? guided_score(c[k], u[k], ou != nullptr, g.w, g.w1, scale) : 0.f;
+      sg = __builtin_fmaf(sk, sk, sg);
+      sz = __builtin_fmaf(n[k], n[k], sz);
+    }
   }
   sg = wave_sum(sg);
   sz = wave_sum(sz);
@@ -1433,282 +1464,82 @@ __global__ __launch_bounds__(64) void langevin_norm_finalize_kernel(const float*
   if (lane == 0) { sums[0] = (float)tg; sums[1] = (float)tz; }
 }
 
-int launch_langevin_norms(const float* grad, const float* noise, int B, long per_sample, float* sq_ws, float* sums,
+int launch_langevin_norms(const GuidedScore& g, const float* noise, int B, long per_sample, float* sq_ws, float* sums, int width,
                           hipStream_t s) {
-  T2P_REQUIRE(grad && noise && sq_ws && sums && B > 0 && per_sample > 0, "langevin_norms arguments");
-  static_assert(NORM_BLOCKS == 64, "finalize assumes one partial per lane");
-  hipLaunchKernelGGL(langevin_sq_kernel, dim3(NORM_BLOCKS, B), dim3(256), 0, s, grad, noise, per_sample, sq_ws);
-  hipLaunchKernelGGL(langevin_norm_finalize_kernel, dim3(1), dim3(64), 0, s, sq_ws, B, sums);
-  T2P_HIP_CHECK(hipGetLastError());
-  return T2P_OK;
-}
-
-__global__ __launch_bounds__(256) void langevin_update_kernel(SdeUpdateArgs a, const float* sums, float batch_total, float snr,
-                                                              float alpha, const float* alpha_table, const int* step_counter, int n_table) {
-  // step_size = (snr * noise_norm / grad_norm)^2 * 2 * alpha   (sampling.py:195); VP: alpha = sde.alphas[timestep] (sampling.py:184-186)
-  if (alpha_table) alpha = alpha_table[min(max(*step_counter, 0), n_table - 1)];
-  const float gn = sums[0] / batch_total, nn = sums[1] / batch_total;
-  const float r = snr * nn / gn;
-  const float step = r * r * 2.f * alpha;
-  const float nscale = sqrtf(step * 2.f);
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (long)gridDim.x * blockDim.x) {
-    const float x = a.x[i];
-    const float xm = x + step * a.score[i];
-    float xn = xm + nscale * a.noise[i];
-    if (a.mask && !a.mask[i]) xn = a.x_initial[i];
-    a.x_out[i] = xn;
-    if (a.x_mean_out) a.x_mean_out[i] = xm;
-  }
-}
-
-int launch_langevin_update(const SdeUpdateArgs& a, const float* sums, float batch_total, float snr, float alpha,
-                           hipStream_t s, const float* alpha_table, const int* step_counter, int n_table) {
-  T2P_REQUIRE(!alpha_table || (step_counter && n_table > 0), "alpha_table needs the step counter and its length");
-  T2P_REQUIRE(a.x && a.score && a.noise && a.x_out && sums && a.n > 0, "langevin_update arguments");
-  T2P_REQUIRE(!a.mask || a.x_initial, "mask needs x_initial");
-  hipLaunchKernelGGL(langevin_update_kernel, dim3(ew_grid(a.n)), dim3(256), 0, s, a, sums, batch_total, snr, alpha, alpha_table, step_counter, n_table);
-  T2P_HIP_CHECK(hipGetLastError());
-  return T2P_OK;
-}
-
-__global__ __launch_bounds__(256) void predictor_update_kernel(SdeUpdateArgs a, const float* G_table, const int* step_counter,
-                                                               float G_value, int probability_flow, int n_table, const float* x_coef_table) {
-  // the host refuses steps >= N (Sampler::step); the clamp is a second guard against reading past the table
-  const int si = G_table ? min(max(*step_counter, 0), n_table - 1) : 0;
-  const float G = G_table ? G_table[si] : G_value;
-  const float g2 = G * G * (probability_flow ? 0.5f : 1.f);
-  const float gz = probability_flow ? 0.f : G;
-  // VP (sde_lib.py:148-157): f = (sqrt(alpha) - 1) x, so x - f = (2 - sqrt(alpha)) x: the coefficient comes from a per-step table
-  const float xc = x_coef_table ? x_coef_table[si] : 1.f;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (long)gridDim.x * blockDim.x) {
-    // rev_f = f - G^2 * score ; x_mean = x - rev_f ; x = x_mean + G z   (sde_lib.py:96-101, sampling.py:162-167)
-    const float xm = xc * a.x[i] + g2 * a.score[i];
-    float xn = xm + gz * a.noise[i];
-    if (a.mask && !a.mask[i]) xn = a.x_initial[i];
-    a.x_out[i] = xn;
-    if (a.x_mean_out) a.x_mean_out[i] = xm;
-  }
-}
-
-int launch_predictor_update(const SdeUpdateArgs& a, const float* G_table, const int* step_counter, float G_value,
-                            int probability_flow, hipStream_t s, int n_table, const float* x_coef_table) {
-  T2P_REQUIRE(!x_coef_table || G_table, "the x coefficient table goes with the G table");
-  T2P_REQUIRE(a.x && a.score && a.noise && a.x_out && a.n > 0, "predictor_update arguments");
-  T2P_REQUIRE(!a.mask || a.x_initial, "mask needs x_initial");
-  T2P_REQUIRE(!G_table || (step_counter && n_table > 0), "G_table needs the step counter and its length");
-  hipLaunchKernelGGL(predictor_update_kernel, dim3(ew_grid(a.n)), dim3(256), 0, s, a, G_table, step_counter, G_value,
-                     probability_flow, n_table, x_coef_table);
-  T2P_HIP_CHECK(hipGetLastError());
-  return T2P_OK;
-}
-
-// ---- classifier-free guidance in the PC loop ----------------------------------------------------------------
-// One evaluation at batch 2B leaves o_c (text context) and o_u (zero context); the score every update reads is
-//   s = scale (w o_c + w1 o_u)     (reference sampler/diffusion_sampler.py:128; scale: 1 for VE, -1 / std for VP)
-// formed per element inside the three kernels that read the score anyway.  Each product and sum of the guidance sum rounds to
-// float32 in this order; the rest of each update is the arithmetic of the kernels above, FMAs written out.
-__device__ inline float guided_score(float oc, float ou, bool guided, float w, float w1, float scale) {
-#pragma clang fp contract(off)
-  float o = oc;
-  if (guided) {
-    const float pc = w * oc, pu = w1 * ou;
-    o = pc + pu;
-  }
-  return o * scale;
-}
-// a b + c d with both products rounded: what predictor_update_kernel's x_mean compiles to (the Langevin update and both noise terms
-// are FMAs there, and are written as such below)
-__device__ inline float sum_of_products(float a, float b, float c, float d) {
-#pragma clang fp contract(off)
-  const float ab = a * b, cd = c * d;
-  return ab + cd;
-}
-__device__ inline float guided_scale(const GuidedScore& g) {
-  return g.scale_table ? g.scale_table[min(max(*g.step_counter, 0), g.n_table - 1)] : g.scale;
-}
-
-// the 16-byte path of the guided kernels: n % 4 == 0 and every pointer 16-byte aligned (the mask 4-byte); null counts as aligned
-static bool guided_vec_ok(long n, std::initializer_list<const void*> p16, const void* mask) {
-  bool ok = n % 4 == 0 && ((uintptr_t)mask % 4) == 0;
-  for (const void* p : p16) ok = ok && ((uintptr_t)p % 16) == 0;
-  return ok;
-}
-
-// per-sample squared norms of s and z: the block / workspace layout of langevin_sq_kernel, one quad of consecutive elements per
-// thread and trip
-template <bool VEC>
-__global__ __launch_bounds__(256) void guided_langevin_sq_kernel(GuidedScore g, const float* noise, long per_sample, float* sq_ws) {
-  __shared__ float red[2][4];
-  const int b = blockIdx.y, blk = blockIdx.x;
-  const float* oc = g.o_c + (long)b * per_sample;
-  const float* ou = g.o_u ? g.o_u + (long)b * per_sample : nullptr;
-  const float* z = noise + (long)b * per_sample;
-  const float scale = guided_scale(g);
-  const long nq = (per_sample + 3) / 4;
-  float sg = 0.f, sz = 0.f;
-  for (long q = (long)blk * 256 + threadIdx.x; q < nq; q += (long)NORM_BLOCKS * 256) {
-    const long i = q * 4;
-    const int cnt = VEC ? 4 : (int)(per_sample - i < 4 ? per_sample - i : 4);
-    alignas(16) float c[4] = {0.f, 0.f, 0.f, 0.f}, u[4] = {0.f, 0.f, 0.f, 0.f}, n[4] = {0.f, 0.f, 0.f, 0.f};
-    if (VEC) {
-      *(float4*)c = *(const float4*)(oc + i);
-      if (ou) *(float4*)u = *(const float4*)(ou + i);
-      *(float4*)n = *(const float4*)(z + i);
-    } else {
-      for (int k = 0; k < cnt; ++k) {
-        c[k] = oc[i + k];
-        if (ou) u[k] = ou[i + k];
-        n[k] = z[i + k];
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {     // the padding of a short tail quad is zero: it adds nothing
-      const float sk = k < cnt ? guided_score(c[k], u[k], ou != nullptr, g.w, g.w1, scale) : 0.f;
-      sg = __builtin_fmaf(sk, sk, sg);
-      sz = __builtin_fmaf(n[k], n[k], sz);
-    }
-  }
-  sg = wave_sum(sg);
-  sz = wave_sum(sz);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) { red[0][w] = sg; red[1][w] = sz; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    sq_ws[((long)b * NORM_BLOCKS + blk) * 2 + 0] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    sq_ws[((long)b * NORM_BLOCKS + blk) * 2 + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-  }
-}
-
-int launch_guided_langevin_norms(const GuidedScore& g, const float* noise, int B, long per_sample, float* sq_ws, float* sums,
-                                 hipStream_t s) {
-  T2P_REQUIRE(g.o_c && noise && sq_ws && sums && B > 0 && per_sample > 0, "guided_langevin_norms arguments");
+  T2P_REQUIRE(g.o_c && noise && sq_ws && sums && B > 0 && per_sample > 0, "langevin_norms arguments");
+  T2P_REQUIRE(width == 1 || width == 4, "langevin_norms: the group width is 1 or 4");
   T2P_REQUIRE(!g.scale_table || (g.step_counter && g.n_table > 0), "scale_table needs the step counter and its length");
-  if (guided_vec_ok(per_sample, {g.o_c, g.o_u, noise}, nullptr))
-    hipLaunchKernelGGL(guided_langevin_sq_kernel<true>, dim3(NORM_BLOCKS, B), dim3(256), 0, s, g, noise, per_sample, sq_ws);
+  static_assert(NORM_BLOCKS == 64, "finalize assumes one partial per lane");
+  const dim3 grid(NORM_BLOCKS, B);
+  if (width == 1)
+    hipLaunchKernelGGL((langevin_sq_kernel<1, false>), grid, dim3(256), 0, s, g, noise, per_sample, sq_ws);
+  else if (quad_vec_ok(per_sample, {g.o_c, g.o_u, noise}, nullptr))
+    hipLaunchKernelGGL((langevin_sq_kernel<4, true>), grid, dim3(256), 0, s, g, noise, per_sample, sq_ws);
   else
-    hipLaunchKernelGGL(guided_langevin_sq_kernel<false>, dim3(NORM_BLOCKS, B), dim3(256), 0, s, g, noise, per_sample, sq_ws);
+    hipLaunchKernelGGL((langevin_sq_kernel<4, false>), grid, dim3(256), 0, s, g, noise, per_sample, sq_ws);
   hipLaunchKernelGGL(langevin_norm_finalize_kernel, dim3(1), dim3(64), 0, s, sq_ws, B, sums);
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }
 
-// the quad loop both guided updates share: loads, s per element, UPDATE(x, s, z, &x_mean) -> x_next, the mask, the stores
-template <bool VEC, typename Update>
-__device__ inline void guided_update_loop(const SdeUpdateArgs& a, const GuidedScore& g, float* x_out2, Update update) {
-  const float scale = guided_scale(g);
-  const long nq = (a.n + 3) / 4;
-  for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
-    const long i = q * 4;
-    const int cnt = VEC ? 4 : (int)(a.n - i < 4 ? a.n - i : 4);
-    alignas(16) float x[4], c[4], u[4] = {0.f, 0.f, 0.f, 0.f}, z[4], xi[4] = {0.f, 0.f, 0.f, 0.f};
-    alignas(4) unsigned char m[4] = {1, 1, 1, 1};
-    if (VEC) {
-      *(float4*)x = *(const float4*)(a.x + i);
-      *(float4*)c = *(const float4*)(g.o_c + i);
-      if (g.o_u) *(float4*)u = *(const float4*)(g.o_u + i);
-      *(float4*)z = *(const float4*)(a.noise + i);
-      if (a.mask) {
-        *(uchar4*)m = *(const uchar4*)(a.mask + i);
-        *(float4*)xi = *(const float4*)(a.x_initial + i);
-      }
-    } else {
-      for (int k = 0; k < 4; ++k) x[k] = c[k] = z[k] = 0.f;
-      for (int k = 0; k < cnt; ++k) {
-        x[k] = a.x[i + k];
-        c[k] = g.o_c[i + k];
-        if (g.o_u) u[k] = g.o_u[i + k];
-        z[k] = a.noise[i + k];
-        if (a.mask) { m[k] = a.mask[i + k]; xi[k] = a.x_initial[i + k]; }
-      }
-    }
-    alignas(16) float xn[4], xm[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      xn[k] = update(x[k], guided_score(c[k], u[k], g.o_u != nullptr, g.w, g.w1, scale), z[k], &xm[k]);
-      if (!m[k]) xn[k] = xi[k];
-    }
-    if (VEC) {
-      *(float4*)(a.x_out + i) = *(const float4*)xn;
-      if (x_out2) *(float4*)(x_out2 + i) = *(const float4*)xn;
-      if (a.x_mean_out) *(float4*)(a.x_mean_out + i) = *(const float4*)xm;
-    } else {
-      for (int k = 0; k < cnt; ++k) {
-        a.x_out[i + k] = xn[k];
-        if (x_out2) x_out2[i + k] = xn[k];
-        if (a.x_mean_out) a.x_mean_out[i + k] = xm[k];
-      }
-    }
-  }
-}
-
 template <bool VEC>
-__global__ __launch_bounds__(256) void guided_langevin_update_kernel(SdeUpdateArgs a, GuidedScore g, float* x_out2, const float* sums,
-                                                                     float batch_total, float snr, float alpha, const float* alpha_table) {
-  // the step size of langevin_update_kernel
+__global__ __launch_bounds__(256) void langevin_update_kernel(SdeUpdateArgs a, GuidedScore g, float* x_out2, const float* sums,
+                                                              float batch_total, float snr, float alpha, const float* alpha_table) {
+  // step_size = (snr * noise_norm / grad_norm)^2 * 2 * alpha   (sampling.py:195); VP: alpha = sde.alphas[timestep] (sampling.py:184-186)
   if (alpha_table) alpha = alpha_table[min(max(*g.step_counter, 0), g.n_table - 1)];
   const float gn = sums[0] / batch_total, nn = sums[1] / batch_total;
   const float r = snr * nn / gn;
   const float step = r * r * 2.f * alpha;
   const float nscale = sqrtf(step * 2.f);
-  guided_update_loop<VEC>(a, g, x_out2, [=](float x, float s, float z, float* xm) {
+  update_loop<VEC, false>(a, g, x_out2, QuadDraw(), [=](float x, float s, float z, float* xm) {
     *xm = __builtin_fmaf(step, s, x);
     return __builtin_fmaf(nscale, z, *xm);
   });
 }
 
-int launch_guided_langevin_update(const SdeUpdateArgs& a, const GuidedScore& g, float* x_out2, const float* sums, float batch_total,
-                                  float snr, float alpha, hipStream_t s, const float* alpha_table) {
-  T2P_REQUIRE(a.x && g.o_c && a.noise && a.x_out && sums && a.n > 0, "guided_langevin_update arguments");
+int launch_langevin_update(const SdeUpdateArgs& a, const GuidedScore& g, float* x_out2, const float* sums, float batch_total,
+                           float snr, float alpha, hipStream_t s, const float* alpha_table) {
+  T2P_REQUIRE(a.x && g.o_c && a.noise && a.x_out && sums && a.n > 0, "langevin_update arguments");
   T2P_REQUIRE((a.mask == nullptr) == (a.x_initial == nullptr), "mask and x_initial go together");
   T2P_REQUIRE((!g.scale_table && !alpha_table) || (g.step_counter && g.n_table > 0), "a per-step table needs the step counter and its length");
   const dim3 grid(ew_grid((a.n + 3) / 4));
-  if (guided_vec_ok(a.n, {a.x, g.o_c, g.o_u, a.noise, a.x_initial, a.x_out, x_out2, a.x_mean_out}, a.mask))
-    hipLaunchKernelGGL(guided_langevin_update_kernel<true>, grid, dim3(256), 0, s, a, g, x_out2, sums, batch_total, snr, alpha, alpha_table);
+  if (quad_vec_ok(a.n, {a.x, g.o_c, g.o_u, a.noise, a.x_initial, a.x_out, x_out2, a.x_mean_out}, a.mask))
+    hipLaunchKernelGGL(langevin_update_kernel<true>, grid, dim3(256), 0, s, a, g, x_out2, sums, batch_total, snr, alpha, alpha_table);
   else
-    hipLaunchKernelGGL(guided_langevin_update_kernel<false>, grid, dim3(256), 0, s, a, g, x_out2, sums, batch_total, snr, alpha, alpha_table);
+    hipLaunchKernelGGL(langevin_update_kernel<false>, grid, dim3(256), 0, s, a, g, x_out2, sums, batch_total, snr, alpha, alpha_table);
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(256) void guided_predictor_update_kernel(SdeUpdateArgs a, GuidedScore g, float* x_out2, const float* G_table,
-                                                                      float G_value, int probability_flow, const float* x_coef_table,
-                                                                      float x_coef_value) {
-  // the coefficients of predictor_update_kernel
+__global__ __launch_bounds__(256) void predictor_update_kernel(SdeUpdateArgs a, GuidedScore g, float* x_out2, const float* G_table,
+                                                               float G_value, int probability_flow, const float* x_coef_table,
+                                                               float x_coef_value) {
+  // the host refuses steps >= N (Sampler::step); the clamp is a second guard against reading past the table
   const int si = G_table ? min(max(*g.step_counter, 0), g.n_table - 1) : 0;
   const float G = G_table ? G_table[si] : G_value;
   const float g2 = G * G * (probability_flow ? 0.5f : 1.f);
   const float gz = probability_flow ? 0.f : G;
+  // VP (sde_lib.py:148-157): f = (sqrt(alpha) - 1) x, so x - f = (2 - sqrt(alpha)) x: the coefficient comes from a per-step table
   const float xc = x_coef_table ? x_coef_table[si] : x_coef_value;
-  guided_update_loop<VEC>(a, g, x_out2, [=](float x, float s, float z, float* xm) {
+  // rev_f = f - G^2 * score ; x_mean = x - rev_f ; x = x_mean + G z   (sde_lib.py:96-101, sampling.py:162-167)
+  update_loop<VEC, false>(a, g, x_out2, QuadDraw(), [=](float x, float s, float z, float* xm) {
     *xm = sum_of_products(xc, x, g2, s);
     return __builtin_fmaf(gz, z, *xm);
   });
 }
 
-int launch_guided_predictor_update(const SdeUpdateArgs& a, const GuidedScore& g, float* x_out2, const float* G_table, float G_value,
-                                   int probability_flow, hipStream_t s, const float* x_coef_table, float x_coef_value) {
+int launch_predictor_update(const SdeUpdateArgs& a, const GuidedScore& g, float* x_out2, const float* G_table, float G_value,
+                            int probability_flow, hipStream_t s, const float* x_coef_table, float x_coef_value) {
   T2P_REQUIRE(!x_coef_table || G_table, "the x coefficient table goes with the G table");
-  T2P_REQUIRE(a.x && g.o_c && a.noise && a.x_out && a.n > 0, "guided_predictor_update arguments");
+  T2P_REQUIRE(a.x && g.o_c && a.noise && a.x_out && a.n > 0, "predictor_update arguments");
   T2P_REQUIRE((a.mask == nullptr) == (a.x_initial == nullptr), "mask and x_initial go together");
   T2P_REQUIRE((!g.scale_table && !G_table) || (g.step_counter && g.n_table > 0), "a per-step table needs the step counter and its length");
   const dim3 grid(ew_grid((a.n + 3) / 4));
-  if (guided_vec_ok(a.n, {a.x, g.o_c, g.o_u, a.noise, a.x_initial, a.x_out, x_out2, a.x_mean_out}, a.mask))
-    hipLaunchKernelGGL(guided_predictor_update_kernel<true>, grid, dim3(256), 0, s, a, g, x_out2, G_table, G_value, probability_flow, x_coef_table, x_coef_value);
+  if (quad_vec_ok(a.n, {a.x, g.o_c, g.o_u, a.noise, a.x_initial, a.x_out, x_out2, a.x_mean_out}, a.mask))
+    hipLaunchKernelGGL(predictor_update_kernel<true>, grid, dim3(256), 0, s, a, g, x_out2, G_table, G_value, probability_flow, x_coef_table, x_coef_value);
   else
-    hipLaunchKernelGGL(guided_predictor_update_kernel<false>, grid, dim3(256), 0, s, a, g, x_out2, G_table, G_value, probability_flow, x_coef_table, x_coef_value);
-  T2P_HIP_CHECK(hipGetLastError());
-  return T2P_OK;
-}
-
-// x *= table[*step]   (VP score: -model / std of the step's time label, models/utils.py:153-157)
-__global__ __launch_bounds__(256) void scale_by_table_kernel(float* x, long n, const float* table, const int* step_counter, int n_table) {
-  const float a = table[min(max(*step_counter, 0), n_table - 1)];
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) x[i] *= a;
-}
-int launch_scale_by_table(float* x, long n, const float* table, const int* step_counter, int n_table, hipStream_t s) {
-  T2P_REQUIRE(x && table && step_counter && n > 0 && n_table > 0, "scale_by_table arguments");
-  hipLaunchKernelGGL(scale_by_table_kernel, dim3(ew_grid(n)), dim3(256), 0, s, x, n, table, step_counter, n_table);
+    hipLaunchKernelGGL(predictor_update_kernel<false>, grid, dim3(256), 0, s, a, g, x_out2, G_table, G_value, probability_flow, x_coef_table, x_coef_value);
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }

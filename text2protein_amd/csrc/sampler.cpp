@@ -1,5 +1,7 @@
-// Host side of the predictor-corrector loop (sampling.py:245-289).  No host synchronisation happens inside step(): the Langevin
-// step size is computed on the device from device-side norm sums.
+// Host side of the predictor-corrector loop (sampling.py:245-289).  One step() serves the plain and the guided loop under the VE and
+// the VP SDE: guidance changes the batch of the evaluation and adds a second destination, the score itself (guidance sum, VP scale)
+// is formed inside the update kernels.  No host synchronisation happens inside step(): the Langevin step size is computed on the
+// device from device-side norm sums.
 #include "sampler.h"
 
 #include <algorithm>
@@ -135,63 +137,25 @@ int Sampler::step(float* x, float* x_mean, const float* nc, const float* np, hip
   const bool vp = cfg_.sde == T2P_SDE_VP;
   T2P_REQUIRE(!vp || vp_label_f_, "VP SDE: call t2p_sampler_set_vp_tables first");
   float* sums = allreduce_ ? sums_ext_ : sums_;
-  if (guided()) return guided_step(x, x_mean, nc, np, sums, s);
-  // score function (models/utils.py:138-171): VE = the network output at the integer label; VP = -output / std at the fractional one
-  auto score_fn = [&]() -> int {
-    T2P_TRY(e_->score(x, nullptr, step_dev_, score_, B, s, nullptr, label_table_, vp ? vp_label_f_ : nullptr));
-    if (vp) T2P_TRY(launch_scale_by_table(score_, n_, vp_score_scale_, step_dev_, cfg_.N, s));
-    return T2P_OK;
-  };
-  for (int k = 0; k < cfg_.n_steps_each; ++k) {
-    T2P_TRY(score_fn());
-    const float* z = nc;
-    if (!z) {
-      T2P_TRY(launch_philox_normal(noise_, n_, cfg_.seed, 2ull * k + 2, step_dev_, s));
-      z = noise_;
-    }
-    T2P_TRY(launch_langevin_norms(score_, z, B, per_sample_, sq_ws_, sums, s));
-    if (allreduce_) {     // sum_b ||grad_b||, sum_b ||noise_b|| over every process's chains (SURVEY 8(e) option B)
-      const int rc = allreduce_(sums, (void*)s, allreduce_user_);
-      if (rc != 0) { set_last_error("the norm all-reduce callback failed with status " + std::to_string(rc)); return T2P_ERR_STATE; }
-    }
-    SdeUpdateArgs a;
-    a.x = x; a.score = score_; a.noise = z; a.mask = mask_; a.x_initial = x_init_; a.x_out = x; a.n = n_;
-    T2P_TRY(launch_langevin_update(a, sums, (float)(allreduce_ ? cfg_.global_batch : B), (float)cfg_.snr, 1.f, s,
-                                   vp ? vp_alpha_ : nullptr, vp ? step_dev_ : nullptr, vp ? cfg_.N : 0));
-  }
-  T2P_TRY(score_fn());
-  const float* z = np;
-  if (!z) {
-    T2P_TRY(launch_philox_normal(noise_, n_, cfg_.seed, 1, step_dev_, s));
-    z = noise_;
-  }
-  SdeUpdateArgs a;
-  a.x = x; a.score = score_; a.noise = z; a.mask = mask_; a.x_initial = x_init_; a.x_out = x;
-  a.x_mean_out = x_mean ? x_mean : xmean_; a.n = n_;
-  T2P_TRY(launch_predictor_update(a, g_table_, step_dev_, 0.f, cfg_.probability_flow, s, cfg_.N, vp ? vp_x_coef_ : nullptr));
-  T2P_TRY(launch_add_int(step_dev_, 1, s));
-  ++host_step_;
-  return T2P_OK;
-}
-
-// the same iteration under guidance: one evaluation of [x ; x] at batch 2B per score, the guidance sum and the VP score scale
-// inside the norm and update kernels, every update written to both blocks of x
-int Sampler::guided_step(float* x, float* x_mean, const float* nc, const float* np, float* sums, hipStream_t s) {
-  T2P_REQUIRE(have_context2_, "guided sampling: call t2p_sampler_set_context first (after t2p_sampler_set_guidance)");
-  const int B = cfg_.batch;
-  const bool vp = cfg_.sde == T2P_SDE_VP;
-  if (mirrored_ != x) {     // first step on this buffer: the zero-context half of the evaluation reads a copy of x
+  // Under guidance: one evaluation of [x ; x] at batch 2B per score, every update written to both blocks of x, the norms summed in
+  // quads.  Nothing else differs: the guidance sum and the VP score scale are formed inside the norm and update kernels.
+  const bool gd = guided();
+  T2P_REQUIRE(!gd || have_context2_, "guided sampling: call t2p_sampler_set_context first (after t2p_sampler_set_guidance)");
+  if (gd && mirrored_ != x) {     // first step on this buffer: the zero-context half of the evaluation reads a copy of x
     T2P_TRY(launch_ddim_mirror(x, x + n_, n_, s));
     mirrored_ = x;
   }
+  float* out = gd ? score2_ : score_;
+  float* x2 = gd ? x + n_ : nullptr;
+  // score function (models/utils.py:138-171): VE = the network output at the integer label; VP = -output / std at the fractional one
   GuidedScore g;
-  g.o_c = score2_; g.o_u = score2_ + n_; g.w = (float)w_; g.w1 = (float)(1.0 - w_);
+  g.o_c = out; g.o_u = gd ? out + n_ : nullptr; g.w = (float)w_; g.w1 = (float)(1.0 - w_);
   g.scale_table = vp ? vp_score_scale_ : nullptr; g.step_counter = step_dev_; g.n_table = cfg_.N;
   auto score_fn = [&]() -> int {
-    return e_->score(x, nullptr, step_dev_, score2_, 2 * B, s, nullptr, label_table_, vp ? vp_label_f_ : nullptr);
+    return e_->score(x, nullptr, step_dev_, out, gd ? 2 * B : B, s, nullptr, label_table_, vp ? vp_label_f_ : nullptr);
   };
   SdeUpdateArgs a;
-  a.x = x; a.mask = mask_; a.x_initial = x_init_; a.x_out = x; a.n = n_;
+  a.x = x; a.mask = mask_; a.x_initial = mask_ ? x_init_ : nullptr; a.x_out = x; a.n = n_;     // x_initial alone was always ignored
   for (int k = 0; k < cfg_.n_steps_each; ++k) {
     T2P_TRY(score_fn());
     a.noise = nc;
@@ -199,13 +163,13 @@ int Sampler::guided_step(float* x, float* x_mean, const float* nc, const float* 
       T2P_TRY(launch_philox_normal(noise_, n_, cfg_.seed, 2ull * k + 2, step_dev_, s));
       a.noise = noise_;
     }
-    T2P_TRY(launch_guided_langevin_norms(g, a.noise, B, per_sample_, sq_ws_, sums, s));
-    if (allreduce_) {
+    T2P_TRY(launch_langevin_norms(g, a.noise, B, per_sample_, sq_ws_, sums, gd ? 4 : 1, s));
+    if (allreduce_) {     // sum_b ||grad_b||, sum_b ||noise_b|| over every process's chains (SURVEY 8(e) option B)
       const int rc = allreduce_(sums, (void*)s, allreduce_user_);
       if (rc != 0) { set_last_error("the norm all-reduce callback failed with status " + std::to_string(rc)); return T2P_ERR_STATE; }
     }
-    T2P_TRY(launch_guided_langevin_update(a, g, x + n_, sums, (float)(allreduce_ ? cfg_.global_batch : B), (float)cfg_.snr, 1.f, s,
-                                          vp ? vp_alpha_ : nullptr));
+    T2P_TRY(launch_langevin_update(a, g, x2, sums, (float)(allreduce_ ? cfg_.global_batch : B), (float)cfg_.snr, 1.f, s,
+                                   vp ? vp_alpha_ : nullptr));
   }
   T2P_TRY(score_fn());
   a.noise = np;
@@ -214,7 +178,7 @@ int Sampler::guided_step(float* x, float* x_mean, const float* nc, const float* 
     a.noise = noise_;
   }
   a.x_mean_out = x_mean ? x_mean : xmean_;
-  T2P_TRY(launch_guided_predictor_update(a, g, x + n_, g_table_, 0.f, cfg_.probability_flow, s, vp ? vp_x_coef_ : nullptr));
+  T2P_TRY(launch_predictor_update(a, g, x2, g_table_, 0.f, cfg_.probability_flow, s, vp ? vp_x_coef_ : nullptr));
   T2P_TRY(launch_add_int(step_dev_, 1, s));
   ++host_step_;
   return T2P_OK;

@@ -32,7 +32,6 @@ class Sampler {
   ~Sampler();
 
  private:
-  int guided_step(float* x, float* x_mean, const float* nc, const float* np, float* sums, hipStream_t s);
   Engine* e_;
   t2p_sampler_config cfg_;
   const uint8_t* mask_ = nullptr;

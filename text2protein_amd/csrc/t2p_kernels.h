@@ -99,52 +99,44 @@ static inline int ew_grid(long total, int block = 256) {
 }
 
 // ---- reverse-diffusion predictor + Langevin corrector (sampling.py:157-199) ------------------------
-// sums[0] = sum_b ||grad_b||_2, sums[1] = sum_b ||noise_b||_2  (per-sample norms, summed over b)
-int launch_langevin_norms(const float* grad, const float* noise, int B, long per_sample, float* sq_ws,
-                          float* sums, hipStream_t s);
+// One set of kernels for the plain and the guided loop, under the VE and the VP SDE.  The score every kernel reads is formed per
+// element, s = scale (w o_c + w1 o_u) (classifier-free guidance, reference sampler/diffusion_sampler.py:128): each product and sum
+// of the guidance sum rounds to float32 in this order, then the scale multiplies.  o_u null: s = scale o_c; with scale == 1 that is
+// the network output itself.  The rest of each update states its rounding too: x_mean of the predictor is two rounded products and
+// their sum, the Langevin update and both noise terms are FMAs (update_loop.h, kernels.hip).
+struct GuidedScore {
+  const float* o_c = nullptr;          // network output (under the text context)
+  const float* o_u = nullptr;          // under the zero context; null = no guidance sum
+  float w = 1.f, w1 = 0.f;             // guidance weight and (float)(1 - w) as the reference rounds it (from the double)
+  float scale = 1.f;                   // VE: 1; VP: -1 / std of the step's label (models/utils.py:153-157) ...
+  const float* scale_table = nullptr;  // ... or scale_table[*step_counter]
+  const int* step_counter = nullptr;   // device step index of every per-step table (scale, alpha, G, x_coef)
+  int n_table = 0;
+};
 struct SdeUpdateArgs {
   const float* x = nullptr;        // current state (B, C, L, L) fp32
-  const float* score = nullptr;    // network output
   const float* noise = nullptr;    // standard normal draws
-  const unsigned char* mask = nullptr;  // conditional_mask (1 = free), may be null
+  const unsigned char* mask = nullptr;  // conditional_mask (1 = free); null together with x_initial
   const float* x_initial = nullptr;
   float* x_out = nullptr;
   float* x_mean_out = nullptr;     // un-masked x_mean (masking of the final x_mean: sampling.py:287)
   long n = 0;                      // total elements
 };
+// sums[0] = sum_b ||s_b||_2, sums[1] = sum_b ||noise_b||_2  (per-sample norms over B samples, summed over b).  width: consecutive
+// elements a thread sums per trip, 1 (the plain loop and t2p_op_langevin*) or 4 (the guided loop): the order of the float32 sums
+int launch_langevin_norms(const GuidedScore& g, const float* noise, int B, long per_sample, float* sq_ws, float* sums, int width,
+                          hipStream_t s);
 // corrector: step = (snr * mean_norm_noise / mean_norm_grad)^2 * 2 * alpha, with the two means
 // = sums[] / batch_total (batch_total may exceed the local batch: global-batch semantics)
 // alpha_table (optional): alpha = alpha_table[*step_counter] (VP: sde.alphas[timestep], sampling.py:184-186)
-int launch_langevin_update(const SdeUpdateArgs& a, const float* sums, float batch_total, float snr, float alpha,
-                           hipStream_t s, const float* alpha_table = nullptr, const int* step_counter = nullptr, int n_table = 0);
-// predictor: x_mean = x + G^2 * score * (0.5 if probability_flow); x = x_mean + (0 if pf else G) z
+// x_out2 (optional): a second copy of the new state, the other half of the [x ; x] input of the next guided evaluation
+int launch_langevin_update(const SdeUpdateArgs& a, const GuidedScore& g, float* x_out2, const float* sums, float batch_total,
+                           float snr, float alpha, hipStream_t s, const float* alpha_table = nullptr);
+// predictor: x_mean = x_coef x + G^2 * s * (0.5 if probability_flow); x = x_mean + (0 if pf else G) z
 // G = G_table[*step_counter] when G_table != null, else G_value
-// x_coef_table (optional, with G_table): x_mean = x_coef[step] x + ... (VP: 2 - sqrt(alpha), sde_lib.py:148-157)
-int launch_predictor_update(const SdeUpdateArgs& a, const float* G_table, const int* step_counter, float G_value,
-                            int probability_flow, hipStream_t s, int n_table = 0, const float* x_coef_table = nullptr);
-int launch_scale_by_table(float* x, long n, const float* table, const int* step_counter, int n_table, hipStream_t s);
-// ---- the same three kernels under classifier-free guidance (reference sampler/diffusion_sampler.py:128) ----
-// The score is formed per element from the two halves of one evaluation at batch 2B: s = scale (w o_c + w1 o_u), each product and
-// sum of the guidance sum rounded to float32 in this order.  o_u null: s = scale o_c, and with scale == 1 the updates reproduce
-// launch_langevin_update / launch_predictor_update bit for bit.  SdeUpdateArgs::score is not read.
-struct GuidedScore {
-  const float* o_c = nullptr;          // network output under the text context
-  const float* o_u = nullptr;          // under the zero context; null = no guidance sum
-  float w = 1.f, w1 = 0.f;             // guidance weight and (float)(1 - w) as the reference rounds it (from the double)
-  float scale = 1.f;                   // VE: 1; VP: -1 / std of the step's label ...
-  const float* scale_table = nullptr;  // ... or scale_table[*step_counter]
-  const int* step_counter = nullptr;   // device step index of every per-step table (scale, alpha, G, x_coef)
-  int n_table = 0;
-};
-// sums as launch_langevin_norms, over B samples: sum_b ||s_b||, sum_b ||noise_b||
-int launch_guided_langevin_norms(const GuidedScore& g, const float* noise, int B, long per_sample, float* sq_ws, float* sums,
-                                 hipStream_t s);
-// x_out2 (optional): a second copy of the new state, the other half of the [x ; x] input of the next evaluation
-int launch_guided_langevin_update(const SdeUpdateArgs& a, const GuidedScore& g, float* x_out2, const float* sums, float batch_total,
-                                  float snr, float alpha, hipStream_t s, const float* alpha_table = nullptr);
-// x_coef_value: the x coefficient where no table is given (the operator ABI)
-int launch_guided_predictor_update(const SdeUpdateArgs& a, const GuidedScore& g, float* x_out2, const float* G_table, float G_value,
-                                   int probability_flow, hipStream_t s, const float* x_coef_table = nullptr, float x_coef_value = 1.f);
+// x_coef_table (optional, with G_table): VP, 2 - sqrt(alpha) (sde_lib.py:148-157); x_coef_value: the coefficient where no table is given
+int launch_predictor_update(const SdeUpdateArgs& a, const GuidedScore& g, float* x_out2, const float* G_table, float G_value,
+                            int probability_flow, hipStream_t s, const float* x_coef_table = nullptr, float x_coef_value = 1.f);
 // noise[i] = N(0,1) from Philox4x32-10 keyed by (seed, stream); counter = element index / 4
 int launch_philox_normal(float* out, long n, unsigned long long seed, unsigned long long stream,
                          const int* step_counter, hipStream_t s);
