@@ -67,6 +67,15 @@ int t2p_engine_num_params(const t2p_engine* e);
 int t2p_engine_param_info(const t2p_engine* e, int i, const char** name, int64_t shape[4], int* ndim);
 int t2p_engine_load_param(t2p_engine* e, const char* name, const float* host_data, const int64_t* shape, int ndim);
 int t2p_engine_finalize(t2p_engine* e);
+/* The weights from a flat fp32 DEVICE buffer in parameters() order (n = the table's total element count, else refused with nothing
+ * changed), packed into the engine's layouts by kernels on `stream`: bit for bit what t2p_engine_load_param of the same numbers +
+ * t2p_engine_finalize leave.  Any number of times, on an engine loaded either way: a later call overwrites the same buffers in place
+ * (no allocation, no pointer changes: captured step graphs stay valid, t2p_engine_device_bytes is unchanged) and drops the cached text
+ * projections, so t2p_engine_score is refused until t2p_engine_set_context ran again.  Does not wait for the stream. */
+int t2p_engine_load_flat(t2p_engine* e, const float* device_flat, int64_t n, void* stream);
+/* The last weight load, host or device: bytes its packings read, bytes they wrote, and how many packings it ran (for a device load:
+ * the launches it enqueued).  tools/bench_refresh.py sets the refresh time against these. */
+int t2p_engine_load_stats(const t2p_engine* e, int64_t out3[3]);
 /* context: device fp32 [batch][tokens][context_dim] */
 int t2p_engine_set_context(t2p_engine* e, const float* context, int batch, int tokens, void* stream);
 /* x: device fp32 (batch, C, L, L); labels: device int32 [batch] time labels (index into the
@@ -338,6 +347,16 @@ int t2p_train_step(t2p_trainer* t, const t2p_train_batch* batch, float* loss_hos
  * ema.update on it.  t2p_train_step = t2p_train_loss(backward = 1) + t2p_train_apply. */
 int t2p_train_grad_buffer(t2p_trainer* t, float** device_ptr, int64_t* n);
 int t2p_train_apply(t2p_trainer* t, void* stream);
+/* The flat fp32 device buffers (parameters() order, owned by the trainer): which = 0 parameters, 2 EMA shadow (t2p_train_read's numbers) */
+int t2p_train_buffer(t2p_trainer* t, int which, float** device_ptr, int64_t* n);
+/* ema.store / ema.copy_to / ema.restore (models/ema.py:51-84) as device-to-device copies of the flat buffers on `stream`: dst <- src is
+ * exactly one of 5 <- 0 (store: 5 is a stash, allocated by the first store and counted in t2p_train_device_bytes), 0 <- 2 (copy_to) or
+ * 0 <- 5 (restore; refused before any store).  A copy into the parameters also renews the trainer's kernel-layout weight copies. */
+int t2p_train_copy(t2p_trainer* t, int dst, int src, void* stream);
+/* t2p_train_buffer + t2p_engine_load_flat: the sampling engine takes the trainer's parameters (which = 0) or EMA (2) without leaving the
+ * device; the compute dtypes of the two may differ.  Refused with nothing changed (the engine keeps its weights and still scores), each
+ * with its own message: parameter tables that differ in count, a name or a shape; different devices; any other `which`. */
+int t2p_engine_load_from_trainer(t2p_engine* e, t2p_trainer* t, int which, void* stream);
 int t2p_train_eval_loss(t2p_trainer* t, const t2p_train_batch* batch, float* loss_host, void* stream);
 int64_t t2p_train_device_bytes(const t2p_trainer* t);
 /* the strided fp32 GEMM of the backward pass: C[z][m][n] = alpha sum_k A(z,m,k) B(z,k,n) + beta C, element strides as given
@@ -541,6 +560,20 @@ int t2p_op_guided_predictor(const float* x, const float* o_c, const float* o_u, 
                             float scale, float G, float x_coef, int probability_flow, void* stream);
 int t2p_op_philox_normal(float* out, int64_t n, uint64_t seed, uint64_t stream_id, void* stream);
 int t2p_op_convert(const float* in, void* out, int dtype, int64_t n, void* stream);
+/* One weight packing of t2p_engine_load_flat on caller-supplied device buffers: fp32 sources -> dst in `dtype`.  kind / dims (a pitch or
+ * cin_pad of 0 = dense):
+ *   0 copy     src0|src1|src2 concatenated            n0, n1, n2
+ *   1 rows     (rows, rowlen) -> dst[r ld + j]        rows, rowlen, ld
+ *   2 conv3    (N, Ci, 3, 3) -> [N][tap][cin_pad]     N, Ci, cin_pad, ld          channels past Ci zero
+ *   3 conv3_t  (N, C, 3, 3) -> [tap][C][N]            N, C
+ *   4 nin      one / two (K, N) -> [nsrc N][K]        K, N, nsrc
+ *   5 geglu    (2 inner, rowlen), rows interleaved    inner, rowlen               (value_j, gate_j)
+ *   6 up4      (co, ci, 3, 3) -> [4][co][4][ci]       co, ci                      taps summed in fp32 in (kh, kw) order
+ *   7 add      src0 + src1                            n
+ *   8 product  src0 (M, K) src1 (K, N) [+ src2 (N)]   M, K, N, transposed, ld     fp32, ascending k, product and add each rounded
+ *   9 dot64    src2[n] + sum_j src0[n][j] src1[j]     N, K                        accumulated in double, rounded once */
+int t2p_op_weight_pack(int kind, const float* src0, const float* src1, const float* src2, void* dst, const int64_t* dims, int ndims, int dtype,
+                       void* stream);
 /* ---- either side of the sampler ----
  * 6D decode of finished samples, sampling_rosetta.py:69-96: x = (batch, channels, L, L) fp32 with the padding mask in
  * the last channel.  lengths[b] = sqrt(#(round(mask) == 1)) or -1 when that count is not a perfect square (the

@@ -68,6 +68,8 @@ SIGNATURES = {
     "t2p_engine_param_info": (_i, [_vp, _i, C.POINTER(C.c_char_p), C.POINTER(_i64), C.POINTER(_i)]),
     "t2p_engine_load_param": (_i, [_vp, C.c_char_p, _vp, C.POINTER(_i64), _i]),
     "t2p_engine_finalize": (_i, [_vp]),
+    "t2p_engine_load_flat": (_i, [_vp, _vp, _i64, _vp]),
+    "t2p_engine_load_stats": (_i, [_vp, C.POINTER(_i64)]),
     "t2p_engine_set_context": (_i, [_vp, _vp, _i, _i, _vp]),
     "t2p_engine_score": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
     "t2p_engine_score_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp]),
@@ -143,6 +145,7 @@ SIGNATURES = {
     "t2p_profile_layers_begin": (_i, []),
     "t2p_profile_layers_end": (_i, [C.c_char_p, C.c_int]),
     "t2p_op_convert": (_i, [_vp, _vp, _i, _i64, _vp]),
+    "t2p_op_weight_pack": (_i, [_i, _vp, _vp, _vp, _vp, C.POINTER(_i64), _i, _i, _vp]),
     # training step
     "t2p_train_create": (_i, [C.POINTER(ModelConfig), C.POINTER(TrainConfig), C.POINTER(_vp)]),
     "t2p_train_destroy": (None, [_vp]),
@@ -162,6 +165,9 @@ SIGNATURES = {
     "t2p_train_eval_loss": (_i, [_vp, C.POINTER(TrainBatch), C.POINTER(_f), _vp]),
     "t2p_train_apply": (_i, [_vp, _vp]),
     "t2p_train_grad_buffer": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i64)]),
+    "t2p_train_buffer": (_i, [_vp, _i, C.POINTER(_vp), C.POINTER(_i64)]),
+    "t2p_train_copy": (_i, [_vp, _i, _i, _vp]),
+    "t2p_engine_load_from_trainer": (_i, [_vp, _vp, _i, _vp]),
     "t2p_train_device_bytes": (_i64, [_vp]),
     "t2p_op_tgemm": (_i, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i, _i, _i, _i, _i64, _i64, _i64, _f, _f, _vp, _i, _i, _i, _i, _i, _vp]),
     "t2p_op_tgemm16": (_i, [_i, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i, _i, _i, _i, _i64, _i64, _i64, _f, _f, _vp, _i, _i, _i, _i, _i,

@@ -81,6 +81,32 @@ int t2p_engine_finalize(t2p_engine* e) {
   API_END
 }
 
+int t2p_engine_load_flat(t2p_engine* e, const float* device_flat, int64_t n, void* stream) {
+  API_BEGIN
+  T2P_REQUIRE(e, "null engine");
+  return e->impl.load_flat(device_flat, n, (hipStream_t)stream);
+  API_END
+}
+
+int t2p_engine_load_stats(const t2p_engine* e, int64_t out3[3]) {
+  API_BEGIN
+  T2P_REQUIRE(e && out3, "null argument");
+  for (int i = 0; i < 3; ++i) out3[i] = e->impl.load_stats()[i];
+  return T2P_OK;
+  API_END
+}
+
+int t2p_op_weight_pack(int kind, const float* src0, const float* src1, const float* src2, void* dst, const int64_t* dims, int ndims, int dtype,
+                       void* stream) {
+  API_BEGIN
+  T2P_REQUIRE(dims && ndims >= 1 && ndims <= 6, "weight_pack: 1 to 6 dimensions");
+  WeightPack p;
+  p.kind = kind; p.src[0] = src0; p.src[1] = src1; p.src[2] = src2; p.dst = dst; p.dtype = dtype;
+  for (int i = 0; i < ndims; ++i) p.d[i] = dims[i];
+  return launch_weight_pack(p, (hipStream_t)stream);
+  API_END
+}
+
 int t2p_engine_set_context(t2p_engine* e, const float* context, int batch, int tokens, void* stream) {
   API_BEGIN
   T2P_REQUIRE(e, "null engine");

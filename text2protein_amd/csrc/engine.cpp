@@ -303,7 +303,18 @@ int NetArch::build(const t2p_model_config& c) {
   return T2P_OK;
 }
 
-int Engine::build() { return arch_.build(cfg_); }
+int Engine::build() {
+  T2P_TRY(arch_.build(cfg_));
+  total_ = 0;
+  for (const ParamInfo& p : arch_.params) {
+    int64_t n = 1;
+    for (int64_t d : p.shape) n *= d;
+    poff_[p.name] = {total_, n};
+    total_ += n;
+  }
+  T2P_HIP_CHECK(hipGetDevice(&device_));
+  return T2P_OK;
+}
 
 int Engine::load_param(const char* name, const float* data, const int64_t* shape, int ndim) {
   T2P_REQUIRE(name && data && shape && ndim >= 1 && ndim <= 4, "load_param arguments");
@@ -330,35 +341,19 @@ int Engine::load_param(const char* name, const float* data, const int64_t* shape
   return T2P_OK;
 }
 
-const HostTensor* Engine::host(const std::string& name, std::vector<int64_t> shape) {
-  auto it = host_.find(name);
-  if (it == host_.end()) {
-    set_last_error("parameter not loaded: " + name);
-    return nullptr;
-  }
-  if (it->second.shape != shape) {
-    set_last_error("unexpected shape for " + name);
-    return nullptr;
-  }
-  return &it->second;
-}
+// ---- weights ------------------------------------------------------------------------------------------------------------------------
+// Engine::pack_weights is the one walk over the network that knows which persistent weight buffers exist, where they live, which
+// packing (t2p_kernels.h: WeightPack) fills each and which dtype / width gates apply.  It has two executors that differ only in who runs
+// a packing: finalize() runs it on the host from the tensors load_param collected (weight_pack_host below, then an upload);
+// load_flat() launches the same packing on the device from a flat fp32 parameter buffer (weightpack.hip).  Both produce the same bits.
 
-int Engine::upload_f32(const std::vector<float>& v, float** out) {
-  float* d = (float*)pool_.persistent(v.size() * 4);
-  if (!d) return T2P_ERR_HIP;
-  T2P_HIP_CHECK(hipMemcpy(d, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-  *out = d;
-  return T2P_OK;
-}
-
-static int upload_matrix(DevPool& pool, const std::vector<float>& m, int dtype, void** out) {
-  const size_t n = m.size();
-  void* d = pool.persistent(n * dtype_size(dtype));
-  if (!d) return T2P_ERR_HIP;
-  if (dtype == DT_F32) {
-    T2P_HIP_CHECK(hipMemcpy(d, m.data(), n * 4, hipMemcpyHostToDevice));
-  } else {
-    std::vector<uint16_t> h(n);
+// dense [rows][width] fp32 block -> dst at pitch ld, in dtype
+static int upload_block(const std::vector<float>& m, int dtype, void* dst, int64_t rows, int64_t width, int64_t ld) {
+  const size_t n = m.size(), es = dtype_size(dtype);
+  const void* src = m.data();
+  std::vector<uint16_t> h;
+  if (dtype != DT_F32) {
+    h.resize(n);
     if (dtype == DT_BF16) {
       for (size_t i = 0; i < n; ++i) h[i] = f32_to_bf16_bits(m[i]);
     } else {
@@ -367,33 +362,11 @@ static int upload_matrix(DevPool& pool, const std::vector<float>& m, int dtype, 
         std::memcpy(&h[i], &x, 2);
       }
     }
-    T2P_HIP_CHECK(hipMemcpy(d, h.data(), n * 2, hipMemcpyHostToDevice));
+    src = h.data();
   }
-  *out = d;
+  if (rows == 1 || ld == width) T2P_HIP_CHECK(hipMemcpy(dst, src, n * es, hipMemcpyHostToDevice));
+  else T2P_HIP_CHECK(hipMemcpy2D(dst, (size_t)ld * es, src, (size_t)width * es, (size_t)width * es, (size_t)rows, hipMemcpyHostToDevice));
   return T2P_OK;
-}
-
-// [N][K] matrix in the layout the GEMM wants, from a reference tensor:
-//   Linear / 1x1 conv : (N, K[,1,1])  as is          NIN : (K, N) transposed
-//   3x3 conv          : (N, Cin, 3, 3) -> [N][kh*3+kw][Cin (padded to cin_pad)]
-static std::vector<float> to_nk(const HostTensor& t, bool conv3x3, bool nin, int cin_pad = 0) {
-  if (conv3x3) {
-    const int64_t N = t.shape[0], ci = t.shape[1];
-    const int64_t cp = cin_pad ? cin_pad : ci;
-    std::vector<float> m((size_t)N * 9 * cp, 0.f);
-    for (int64_t n = 0; n < N; ++n)
-      for (int64_t c = 0; c < ci; ++c)
-        for (int tap = 0; tap < 9; ++tap) m[(n * 9 + tap) * cp + c] = t.data[(n * ci + c) * 9 + tap];
-    return m;
-  }
-  if (nin) {
-    const int64_t K = t.shape[0], N = t.shape[1];
-    std::vector<float> m((size_t)N * K);
-    for (int64_t k = 0; k < K; ++k)
-      for (int64_t n = 0; n < N; ++n) m[n * K + k] = t.data[k * N + n];
-    return m;
-  }
-  return t.data;
 }
 
 // out[M][N] = A[M][K] B[K][N] (row-major fp32; weight products formed once at load time), rows spread over a few threads
@@ -416,69 +389,378 @@ static std::vector<float> host_matmul(const float* A, const float* B, int64_t M,
   return out;
 }
 
-int Engine::upload_linear(const std::string& wname, const std::string& bname, int N, int K, DevLinear* out,
-                          bool conv3x3, bool nin, int force_dtype) {
-  std::vector<int64_t> shape;
-  int cin_pad = 0;
-  if (conv3x3) {
-    const int ci = K / 9;
-    shape = {N, ci, 3, 3};
-    if (wname == "pre_conv.weight") { shape = {N, cfg_.num_channels, 3, 3}; cin_pad = cpad_; }
-  } else if (nin) {
-    shape = {K, N};
-  } else {
-    shape = {N, K};
+// host twin of launch_weight_pack: the dense block of packing p (p.src = host pointers; p checked by weight_pack_shape).
+//   Linear / 1x1 conv : (N, K[,1,1]) as is          NIN : (K, N) transposed
+//   3x3 conv          : (N, Cin, 3, 3) -> [N][kh*3+kw][Cin (padded to cin_pad)]
+static void weight_pack_host(const WeightPack& p, std::vector<float>* out) {
+  const int64_t* d = p.d;
+  const float* const* s = p.src;
+  std::vector<float>& m = *out;
+  switch (p.kind) {
+    case WP_COPY:
+      m.assign(s[0], s[0] + d[0]);
+      if (d[1]) m.insert(m.end(), s[1], s[1] + d[1]);
+      if (d[2]) m.insert(m.end(), s[2], s[2] + d[2]);
+      break;
+    case WP_ROWS:
+      m.assign(s[0], s[0] + d[0] * d[1]);
+      break;
+    case WP_CONV3: {
+      const int64_t N = d[0], ci = d[1], cp = d[2];
+      m.assign((size_t)N * 9 * cp, 0.f);
+      for (int64_t n = 0; n < N; ++n)
+        for (int64_t c = 0; c < ci; ++c)
+          for (int tap = 0; tap < 9; ++tap) m[(n * 9 + tap) * cp + c] = s[0][(n * ci + c) * 9 + tap];
+      break;
+    }
+    case WP_CONV3_T: {                                         // [tap][C][N]: lanes (= output channels) read contiguously
+      const int64_t N = d[0], C = d[1];
+      m.resize((size_t)9 * C * N);
+      for (int64_t n = 0; n < N; ++n)
+        for (int64_t c = 0; c < C; ++c)
+          for (int tap = 0; tap < 9; ++tap) m[(tap * C + c) * N + n] = s[0][(n * C + c) * 9 + tap];
+      break;
+    }
+    case WP_NIN: {
+      const int64_t K = d[0], N = d[1];
+      m.resize((size_t)d[2] * N * K);
+      for (int64_t z = 0; z < d[2]; ++z)
+        for (int64_t k = 0; k < K; ++k)
+          for (int64_t n = 0; n < N; ++n) m[z * N * K + n * K + k] = s[z][k * N + n];
+      break;
+    }
+    case WP_GEGLU: {                                           // rows interleaved (value_j, gate_j) so the GEMM epilogue can gate in registers
+      const int64_t inner = d[0], rl = d[1];
+      m.resize((size_t)2 * inner * rl);
+      for (int64_t j = 0; j < inner; ++j) {
+        std::copy(s[0] + j * rl, s[0] + (j + 1) * rl, m.begin() + (2 * j) * rl);
+        std::copy(s[0] + (inner + j) * rl, s[0] + (inner + j + 1) * rl, m.begin() + (2 * j + 1) * rl);
+      }
+      break;
+    }
+    case WP_UP4: {
+      // conv0 of an up block reads the 2x nearest-up-sampled map (layers.py:306-308): output phase (py, px) of pixel
+      // (2 yl + py, 2 xl + px) sees source pixel yl + floor((py + kh - 1) / 2) for kernel row kh, i.e. two source rows per
+      // phase; the taps that read the same source pixel are summed here (in fp32, before the one rounding to the compute
+      // dtype): four 2x2 convolutions on the source map with 4 / 9 of the multiplications
+      const int64_t co = d[0], ci = d[1];
+      m.assign((size_t)4 * co * 4 * ci, 0.f);
+      auto fl2 = [](int f) { return f >= 0 ? f / 2 : -((-f + 1) / 2); };
+      for (int py = 0; py < 2; ++py)
+        for (int px = 0; px < 2; ++px)
+          for (int kh = 0; kh < 3; ++kh)
+            for (int kw = 0; kw < 3; ++kw) {
+              const int ty = fl2(py + kh - 1) + 1 - py, tx = fl2(px + kw - 1) + 1 - px;     // 0 or 1
+              const size_t ph = (size_t)(py * 2 + px), tap = (size_t)(ty * 2 + tx);
+              for (int64_t n = 0; n < co; ++n)
+                for (int64_t c = 0; c < ci; ++c)
+                  m[((ph * co + n) * 4 + tap) * ci + c] += s[0][(((size_t)n * ci + c) * 3 + kh) * 3 + kw];
+            }
+      break;
+    }
+    case WP_ADD:
+      m.resize((size_t)d[0]);
+      for (int64_t i = 0; i < d[0]; ++i) m[i] = s[0][i] + s[1][i];
+      break;
+    case WP_PRODUCT: {
+      const int64_t M = d[0], K = d[1], N = d[2];
+      m = host_matmul(s[0], s[1], M, K, N);
+      if (s[2])
+        for (int64_t i = 0; i < M; ++i)
+          for (int64_t n = 0; n < N; ++n) m[i * N + n] += s[2][n];
+      if (d[3]) {
+        std::vector<float> t((size_t)M * N);
+        for (int64_t i = 0; i < M; ++i)
+          for (int64_t n = 0; n < N; ++n) t[n * M + i] = m[i * N + n];
+        m.swap(t);
+      }
+      break;
+    }
+    case WP_DOT64: {
+      const int64_t N = d[0], K = d[1];
+      m.resize((size_t)N);
+      for (int64_t n = 0; n < N; ++n) {
+        double acc = s[2][n];
+        for (int64_t j = 0; j < K; ++j) acc += (double)s[0][n * K + j] * s[1][j];
+        m[n] = (float)acc;
+      }
+      break;
+    }
   }
-  const HostTensor* w = host(wname, shape);
-  if (!w && !conv3x3 && !nin) {   // 1x1 convolution weights are (N, K, 1, 1)
-    w = host(wname, {N, K, 1, 1});
+}
+
+// the persistent buffer behind *slot: allocated by the first load, reused in place by every later one
+int Engine::dest(void** slot, size_t bytes) {
+  if (!*slot) *slot = pool_.persistent(bytes);
+  return *slot ? T2P_OK : T2P_ERR_HIP;
+}
+
+// one parameter tensor as the running executor reads it: a host pointer (finalize) or a slice of the flat device buffer (load_flat)
+const float* Engine::psrc(const std::string& name, int64_t numel) {
+  auto it = poff_.find(name);
+  if (it == poff_.end() || it->second.second != numel) {
+    set_last_error((it == poff_.end() ? "no parameter " : "unexpected shape for ") + name);
+    return nullptr;
   }
-  if (!w) return T2P_ERR_STATE;
-  std::vector<float> m = to_nk(*w, conv3x3, nin, cin_pad);
-  T2P_TRY(upload_matrix(pool_, m, force_dtype >= 0 ? force_dtype : cfg_.compute_dtype, &out->w));
+  if (flat_) return flat_ + it->second.first;
+  auto h = host_.find(name);
+  if (h == host_.end() || (int64_t)h->second.data.size() != numel) {
+    set_last_error("parameter not loaded: " + name);
+    return nullptr;
+  }
+  return h->second.data.data();
+}
+#define T2P_SRC(var, name, numel)                         \
+  const float* var = psrc((name), (int64_t)(numel));      \
+  if (!var) return T2P_ERR_STATE;
+
+int Engine::pack(int kind, void* dst, int64_t off, int dtype, std::initializer_list<const float*> srcs, std::initializer_list<int64_t> dims) {
+  WeightPack p;
+  p.kind = kind; p.dtype = dtype; p.dst = (char*)dst + (size_t)off * dtype_size(dtype);
+  int i = 0;
+  for (const float* s : srcs) p.src[i++] = s;
+  i = 0;
+  for (int64_t d : dims) p.d[i++] = d;
+  int64_t rows = 0, width = 0, ld = 0, rd = 0, wr = 0;
+  T2P_TRY(weight_pack_shape(p, &rows, &width, &ld));
+  weight_pack_bytes(p, rows, width, &rd, &wr);
+  load_stats_[0] += rd; load_stats_[1] += wr; load_stats_[2] += 1;
+  if (flat_) return launch_weight_pack(p, pack_stream_);
+  std::vector<float> m;
+  weight_pack_host(p, &m);
+  return upload_block(m, dtype, p.dst, rows, width, ld);
+}
+
+// fragment-major copy of a packed 16-bit matrix (stfuse.hip), on the stream of the running load
+int Engine::pack_frag(void** slot, const void* w, int N, int K) {
+  T2P_TRY(dest(slot, (size_t)N * K * 2));
+  load_stats_[0] += (int64_t)N * K * 2; load_stats_[1] += (int64_t)N * K * 2; load_stats_[2] += 1;
+  return launch_sf_frag_major(cfg_.compute_dtype, w, *slot, N, K, pack_stream_);
+}
+
+int Engine::pack_linear(const std::string& wname, const std::string& bname, int N, int K, DevLinear* out, bool conv3x3, bool nin,
+                        int force_dtype, int cin_pad) {
+  const int dt = force_dtype >= 0 ? force_dtype : cfg_.compute_dtype;
+  const int ci = K / 9, cp = cin_pad ? cin_pad : ci;
+  const int Kd = conv3x3 ? 9 * cp : K;
+  T2P_SRC(w, wname, (int64_t)N * K);
+  T2P_TRY(dest(&out->w, (size_t)N * Kd * dtype_size(dt)));
+  if (conv3x3) T2P_TRY(pack(WP_CONV3, out->w, 0, dt, {w}, {N, ci, cp, 0}));
+  else if (nin) T2P_TRY(pack(WP_NIN, out->w, 0, dt, {w}, {K, N, 1}));
+  else T2P_TRY(pack(WP_COPY, out->w, 0, dt, {w}, {(int64_t)N * K}));       // Linear (N, K) and 1x1 convolution (N, K, 1, 1): as they are
   out->N = N;
-  out->K = (int)(m.size() / N);
-  out->b = nullptr;
+  out->K = Kd;
   if (!bname.empty()) {
-    const HostTensor* b = host(bname, {N});
-    if (!b) return T2P_ERR_STATE;
-    T2P_TRY(upload_f32(b->data, &out->b));
+    T2P_SRC(b, bname, N);
+    T2P_TRY(dest((void**)&out->b, (size_t)N * 4));
+    T2P_TRY(pack(WP_COPY, out->b, 0, DT_F32, {b}, {N}));
   }
   return T2P_OK;
 }
 
-int Engine::upload_stack2(const std::string& w0, const std::string& b0, const std::string& w1, const std::string& b1,
-                          int N, int K, bool nin, bool has_bias, DevLinear* out) {
-  const std::vector<int64_t> shape = nin ? std::vector<int64_t>{K, N} : std::vector<int64_t>{N, K};
-  const HostTensor* t0 = host(w0, shape);
-  const HostTensor* t1 = host(w1, shape);
-  if (!t0 || !t1) return T2P_ERR_STATE;
-  std::vector<float> m = to_nk(*t0, false, nin);
-  std::vector<float> m1 = to_nk(*t1, false, nin);
-  m.insert(m.end(), m1.begin(), m1.end());
-  T2P_TRY(upload_matrix(pool_, m, cfg_.compute_dtype, &out->w));
+int Engine::pack_stack2(const std::string& w0, const std::string& b0, const std::string& w1, const std::string& b1,
+                        int N, int K, bool nin, bool has_bias, DevLinear* out) {
+  const int dt = cfg_.compute_dtype;
+  T2P_SRC(t0, w0, (int64_t)N * K);
+  T2P_SRC(t1, w1, (int64_t)N * K);
+  T2P_TRY(dest(&out->w, (size_t)2 * N * K * dtype_size(dt)));
+  if (nin) T2P_TRY(pack(WP_NIN, out->w, 0, dt, {t0, t1}, {K, N, 2}));
+  else T2P_TRY(pack(WP_COPY, out->w, 0, dt, {t0, t1}, {(int64_t)N * K, (int64_t)N * K}));
   out->N = 2 * N;
   out->K = K;
-  out->b = nullptr;
   if (has_bias) {
-    const HostTensor* c0 = host(b0, {N});
-    const HostTensor* c1 = host(b1, {N});
-    if (!c0 || !c1) return T2P_ERR_STATE;
-    std::vector<float> b = c0->data;
-    b.insert(b.end(), c1->data.begin(), c1->data.end());
-    T2P_TRY(upload_f32(b, &out->b));
+    T2P_SRC(c0, b0, N);
+    T2P_SRC(c1, b1, N);
+    T2P_TRY(dest((void**)&out->b, (size_t)2 * N * 4));
+    T2P_TRY(pack(WP_COPY, out->b, 0, DT_F32, {c0, c1}, {N, N}));
   }
   return T2P_OK;
 }
 
-int Engine::upload_norm(const std::string& prefix, int C, int G, DevNorm* out) {
-  const HostTensor* g = host(prefix + ".weight", {C});
-  const HostTensor* b = host(prefix + ".bias", {C});
-  if (!g || !b) return T2P_ERR_STATE;
-  T2P_TRY(upload_f32(g->data, &out->gamma));
-  T2P_TRY(upload_f32(b->data, &out->beta));
+int Engine::pack_norm(const std::string& prefix, int C, int G, DevNorm* out) {
+  T2P_SRC(g, prefix + ".weight", C);
+  T2P_SRC(b, prefix + ".bias", C);
+  T2P_TRY(dest((void**)&out->gamma, (size_t)C * 4));
+  T2P_TRY(dest((void**)&out->beta, (size_t)C * 4));
+  T2P_TRY(pack(WP_COPY, out->gamma, 0, DT_F32, {g}, {C}));
+  T2P_TRY(pack(WP_COPY, out->beta, 0, DT_F32, {b}, {C}));
   out->C = C;
   out->G = G;
+  return T2P_OK;
+}
+
+int Engine::pack_weights() {
+  load_stats_[0] = load_stats_[1] = load_stats_[2] = 0;
+  const int td = arch_.temb_dim, dt = cfg_.compute_dtype, nf = arch_.nf, Cx = cfg_.num_channels;
+  const size_t es = dtype_size(dt);
+  T2P_TRY(pack_linear("pre_blocks.0.weight", "pre_blocks.0.bias", td, nf, &pre0_, false, false, DT_F32));
+  T2P_TRY(pack_linear("pre_blocks.1.weight", "pre_blocks.1.bias", td, td, &pre1_, false, false, DT_F32));
+  T2P_TRY(pack_linear("pre_conv.weight", "pre_conv.bias", nf, 9 * Cx, &pre_conv_, true, false, DT_F32, cpad_));
+  {
+    T2P_SRC(w, "pre_conv.weight", (int64_t)nf * Cx * 9);
+    T2P_TRY(dest((void**)&pre_conv_direct_, (size_t)9 * Cx * nf * 4));
+    T2P_TRY(pack(WP_CONV3_T, pre_conv_direct_, 0, DT_F32, {w}, {nf, Cx}));       // [tap][C][nf], unpadded
+    // the same weights split into two f16 terms each, for the input convolution on the 16-bit matrix pipe (pre_conv_split_kernel).
+    // The split form needs |x| inside the f16 range: the state of a VE run stays within a few sigma_max
+    if (dt != DT_F32 && (Cx == 5 || Cx == 8) && cfg_.sigma_max <= 4096.0) {
+      T2P_TRY(dest(&pre_conv_split_, pre_conv_split_weight_bytes(Cx, nf)));
+      T2P_TRY(launch_pre_conv_split_weights(pre_conv_direct_, pre_conv_split_, Cx, nf, pack_stream_));
+      load_stats_[0] += (int64_t)9 * Cx * nf * 4; load_stats_[1] += (int64_t)pre_conv_split_weight_bytes(Cx, nf); load_stats_[2] += 1;
+    }
+  }
+  // the time-embedding table: Dense_0 of every residual block, concatenated (one GEMM per evaluation)
+  T2P_TRY(dest(&dense_all_.w, (size_t)arch_.temb_total * td * 4));
+  T2P_TRY(dest((void**)&dense_all_.b, (size_t)arch_.temb_total * 4));
+  dense_all_.N = arch_.temb_total;
+  dense_all_.K = td;
+  auto each_layer = [&](auto&& fn) -> int {
+    for (Stage& st : arch_.input_stages) for (Layer& l : st.layers) T2P_TRY(fn(l));
+    for (Layer& l : arch_.mid_stage.layers) T2P_TRY(fn(l));
+    for (Stage& st : arch_.out_stages) for (Layer& l : st.layers) T2P_TRY(fn(l));
+    return T2P_OK;
+  };
+  T2P_TRY(each_layer([&](Layer& l) -> int {
+    const std::string& p = l.prefix;
+    const int ci = l.in_ch, co = l.out_ch;
+    if (l.kind == 0) {
+      T2P_TRY(pack_norm(p + ".GroupNorm_0", ci, gn_groups(ci), &l.gn0));
+      T2P_TRY(pack_norm(p + ".GroupNorm_1", co, gn_groups(co), &l.gn1));
+      T2P_TRY(pack_linear(p + ".Conv_0.weight", p + ".Conv_0.bias", co, 9 * ci, &l.conv0, true));
+      if (l.up && dt != DT_F32) {                   // conv0 as four 2x2 phase convolutions (WP_UP4)
+        T2P_SRC(w, p + ".Conv_0.weight", (int64_t)co * ci * 9);
+        T2P_TRY(dest(&l.conv0_up4, (size_t)16 * co * ci * es));
+        T2P_TRY(pack(WP_UP4, l.conv0_up4, 0, dt, {w}, {co, ci}));
+      }
+      T2P_TRY(pack_linear(p + ".Conv_1.weight", p + ".Conv_1.bias", co, 9 * co, &l.conv1, true));
+      if (l.has_conv2) T2P_TRY(pack_linear(p + ".Conv_2.weight", p + ".Conv_2.bias", co, ci, &l.conv2));
+      if (l.has_conv2 && !l.up && dt != DT_F32 && ci % 64 == 0 && co % 64 == 0) {
+        // h + shortcut(x) = [conv1 | conv2] applied to [3x3 window of a1 | x] (layers.py:322-327): one K loop, one fp32 sum
+        T2P_SRC(w1, p + ".Conv_1.weight", (int64_t)co * co * 9);
+        T2P_SRC(w2, p + ".Conv_2.weight", (int64_t)co * ci);
+        T2P_SRC(b1, p + ".Conv_1.bias", co);
+        T2P_SRC(b2, p + ".Conv_2.bias", co);
+        const int64_t K1 = (int64_t)9 * co, Kx = K1 + ci;
+        T2P_TRY(dest(&l.conv1x.w, (size_t)co * Kx * es));
+        T2P_TRY(dest((void**)&l.conv1x.b, (size_t)co * 4));
+        T2P_TRY(pack(WP_CONV3, l.conv1x.w, 0, dt, {w1}, {co, co, co, Kx}));
+        T2P_TRY(pack(WP_ROWS, l.conv1x.w, K1, dt, {w2}, {co, ci, Kx}));
+        T2P_TRY(pack(WP_ADD, l.conv1x.b, 0, DT_F32, {b1, b2}, {co}));
+        l.conv1x.N = co; l.conv1x.K = (int)Kx;
+      }
+      T2P_SRC(w, p + ".Dense_0.weight", (int64_t)co * td);
+      T2P_SRC(b, p + ".Dense_0.bias", co);
+      T2P_TRY(pack(WP_COPY, dense_all_.w, (int64_t)l.temb_off * td, DT_F32, {w}, {(int64_t)co * td}));
+      T2P_TRY(pack(WP_COPY, dense_all_.b, l.temb_off, DT_F32, {b}, {co}));
+      // fragment-major copies for the small-map convolution kernel: res_block makes them at the block's first use; a later load renews them
+      if (l.fm_conv0) {
+        const DevLinear& c1 = l.has_conv2 ? l.conv1x : l.conv1;
+        T2P_TRY(pack_frag(&l.fm_conv0, l.conv0.w, co, l.conv0.K));
+        T2P_TRY(pack_frag(&l.fm_conv1, c1.w, co, c1.K));
+      }
+    } else if (l.kind == 1) {
+      T2P_TRY(pack_norm(p + ".GroupNorm_0", ci, gn_groups(ci), &l.gn0));
+      T2P_TRY(pack_stack2(p + ".NIN_0.W", p + ".NIN_0.b", p + ".NIN_1.W", p + ".NIN_1.b", ci, ci, true, true, &l.qk));
+      T2P_TRY(pack_linear(p + ".NIN_2.W", p + ".NIN_2.b", ci, ci, &l.v, false, true));
+      T2P_TRY(pack_linear(p + ".NIN_3.W", p + ".NIN_3.b", ci, ci, &l.out, false, true));
+      if (dt != DT_F32) {
+        T2P_SRC(w2, p + ".NIN_2.W", (int64_t)ci * ci);      // NIN: [in][out]
+        T2P_SRC(w3, p + ".NIN_3.W", (int64_t)ci * ci);
+        T2P_SRC(b2, p + ".NIN_2.b", ci);
+        T2P_SRC(b3, p + ".NIN_3.b", ci);
+        T2P_TRY(dest(&l.v3.w, (size_t)ci * ci * es));
+        T2P_TRY(dest((void**)&l.v3.b, (size_t)ci * 4));
+        T2P_TRY(pack(WP_PRODUCT, l.v3.w, 0, dt, {w2, w3}, {ci, ci, ci, 1, 0}));              // (W2 W3)^T
+        T2P_TRY(pack(WP_PRODUCT, l.v3.b, 0, DT_F32, {b2, w3, b3}, {1, ci, ci, 0, 0}));       // b2 W3 + b3
+        l.v3.N = ci; l.v3.K = ci;
+        if (ci == 256 && l.qk.w && l.qk.b) {
+          T2P_TRY(pack_frag(&l.fm_qk, l.qk.w, 2 * ci, ci));
+          T2P_TRY(pack_frag(&l.fm_v3, l.v3.w, ci, ci));
+        }
+      }
+    } else {
+      const std::string t = p + ".transformer_blocks.0";
+      const int ctx = cfg_.context_dim;
+      T2P_TRY(pack_norm(p + ".norm", ci, 32, &l.gn0));
+      T2P_TRY(pack_linear(p + ".proj_in.weight", p + ".proj_in.bias", ci, ci, &l.proj_in));
+      T2P_TRY(pack_linear(p + ".proj_out.weight", p + ".proj_out.bias", ci, ci, &l.proj_out));
+      T2P_TRY(pack_stack2(t + ".attn1.to_q.weight", "", t + ".attn1.to_k.weight", "", ci, ci, false, false, &l.a1_qk));
+      T2P_TRY(pack_linear(t + ".attn1.to_v.weight", "", ci, ci, &l.a1_v));
+      if (dt != DT_F32) {      // the fused attention kernel reads V row-major: q | k | v from one GEMM
+        const int64_t cc = (int64_t)ci * ci;
+        T2P_SRC(wq, t + ".attn1.to_q.weight", cc);
+        T2P_SRC(wk, t + ".attn1.to_k.weight", cc);
+        T2P_SRC(wv, t + ".attn1.to_v.weight", cc);
+        T2P_TRY(dest(&l.a1_qkv.w, (size_t)3 * cc * es));
+        T2P_TRY(pack(WP_COPY, l.a1_qkv.w, 0, dt, {wq, wk, wv}, {cc, cc, cc}));
+        l.a1_qkv.N = 3 * ci; l.a1_qkv.K = ci; l.a1_qkv.b = nullptr;
+      }
+      T2P_TRY(pack_linear(t + ".attn1.to_out.0.weight", t + ".attn1.to_out.0.bias", ci, ci, &l.a1_out));
+      T2P_TRY(pack_linear(t + ".attn2.to_q.weight", "", ci, ci, &l.a2_q));
+      T2P_TRY(pack_linear(t + ".attn2.to_k.weight", "", ci, ctx, &l.a2_k));
+      T2P_TRY(pack_linear(t + ".attn2.to_v.weight", "", ci, ctx, &l.a2_v));
+      T2P_TRY(pack_linear(t + ".attn2.to_out.0.weight", t + ".attn2.to_out.0.bias", ci, ci, &l.a2_out));
+      {   // GEGLU projection with rows interleaved (value_j, gate_j) so the GEMM epilogue can gate in registers
+        const int64_t inner = 4 * ci;
+        T2P_SRC(w, t + ".ff.net.0.proj.weight", 2 * inner * ci);
+        T2P_SRC(b, t + ".ff.net.0.proj.bias", 2 * inner);
+        T2P_TRY(dest(&l.ff1.w, (size_t)2 * inner * ci * es));
+        T2P_TRY(dest((void**)&l.ff1.b, (size_t)2 * inner * 4));
+        T2P_TRY(pack(WP_GEGLU, l.ff1.w, 0, dt, {w}, {inner, ci}));
+        T2P_TRY(pack(WP_GEGLU, l.ff1.b, 0, DT_F32, {b}, {inner, 1}));
+        l.ff1.N = 8 * ci;
+        l.ff1.K = ci;
+      }
+      T2P_TRY(pack_linear(t + ".ff.net.2.weight", t + ".ff.net.2.bias", ci, 4 * ci, &l.ff2));
+      // (C = 512: the chains stream 4x the bytes per workgroup and measured equal to the separate launches: not built, DESIGN.md section 8)
+      if (dt != DT_F32 && ci == 256 && l.a1_qkv.w) {
+        // fragment-major copies of the row-chain kernel's weights (1 KiB contiguous per MFMA fragment)
+        T2P_TRY(pack_frag(&l.fm_in, l.proj_in.w, ci, ci));
+        T2P_TRY(pack_frag(&l.fm_qkv, l.a1_qkv.w, 3 * ci, ci));
+        T2P_TRY(pack_frag(&l.fm_out1, l.a1_out.w, ci, ci));
+        T2P_TRY(pack_frag(&l.fm_q2, l.a2_q.w, ci, ci));
+        if (ci == 256) {                        // (the chains through the feed-forward exist at C = 256 only)
+          T2P_TRY(pack_frag(&l.fm_out2, l.a2_out.w, ci, ci));
+          T2P_TRY(pack_frag(&l.fm_ff1, l.ff1.w, 8 * ci, ci));
+        }
+      }
+      if (dt != DT_F32 && ci % 64 == 0) {
+        // proj_out(t + ff2(g)) = [W_po W_ff2 | W_po] [g ; t] + (W_po b_ff2 + b_po), the bias accumulated in double
+        T2P_SRC(wpo, p + ".proj_out.weight", (int64_t)ci * ci);
+        T2P_SRC(bpo, p + ".proj_out.bias", ci);
+        T2P_SRC(wf, t + ".ff.net.2.weight", (int64_t)ci * 4 * ci);
+        T2P_SRC(bf, t + ".ff.net.2.bias", ci);
+        T2P_TRY(dest(&l.ffpo.w, (size_t)ci * 5 * ci * es));
+        T2P_TRY(dest((void**)&l.ffpo.b, (size_t)ci * 4));
+        T2P_TRY(pack(WP_PRODUCT, l.ffpo.w, 0, dt, {wpo, wf}, {ci, ci, 4 * ci, 0, 5 * ci}));  // [C][4 C | .]
+        T2P_TRY(pack(WP_ROWS, l.ffpo.w, 4 * ci, dt, {wpo}, {ci, ci, 5 * ci}));               // [C][. | C]
+        T2P_TRY(pack(WP_DOT64, l.ffpo.b, 0, DT_F32, {wpo, bf, bpo}, {ci, ci}));
+        l.ffpo.N = ci; l.ffpo.K = 5 * ci;
+        if (ci == 256 && l.fm_in) T2P_TRY(pack_frag(&l.fm_ffpo, l.ffpo.w, ci, 5 * ci));      // the row-chain kernel's third product
+      }
+      T2P_TRY(pack_norm(t + ".norm1", ci, 1, &l.ln1));
+      T2P_TRY(pack_norm(t + ".norm2", ci, 1, &l.ln2));
+      T2P_TRY(pack_norm(t + ".norm3", ci, 1, &l.ln3));
+    }
+    return T2P_OK;
+  }));
+  T2P_TRY(pack_norm("out.0", arch_.final_ch, gn_groups(arch_.final_ch), &head_norm_));
+  T2P_TRY(pack_linear("out.2.weight", "out.2.bias", Cx, 9 * arch_.final_ch, &head_conv_, true));
+
+  if (!inv_sigma_) {                       // tables of the config, not of the weights: made by the first load only
+    // 1 / sigmas[label]: sigmas = exp(linspace(log sigma_max, log sigma_min, N)) in float64
+    // (models/utils.py:50-60); the reference divides by the float64 value (ncsnpp.py:259-261).
+    const int N = cfg_.num_scales;
+    std::vector<float> inv(N);
+    const double a = std::log(cfg_.sigma_max), b = std::log(cfg_.sigma_min);
+    for (int i = 0; i < N; ++i) {
+      const double s = std::exp(a + (b - a) * (double)i / (double)(N - 1));
+      inv[i] = (float)(1.0 / s);
+    }
+    T2P_TRY(dest((void**)&inv_sigma_, (size_t)N * 4));
+    T2P_TRY(dest((void**)&unit_scale_, (size_t)N * 4));
+    T2P_TRY(upload_block(inv, DT_F32, inv_sigma_, 1, N, N));
+    T2P_TRY(upload_block(std::vector<float>(N, 1.f), DT_F32, unit_scale_, 1, N, N));
+  }
   return T2P_OK;
 }
 
@@ -490,232 +772,33 @@ int Engine::finalize() {
       return T2P_ERR_STATE;
     }
   }
-  const int td = arch_.temb_dim;
-  T2P_TRY(upload_linear("pre_blocks.0.weight", "pre_blocks.0.bias", td, arch_.nf, &pre0_, false, false, DT_F32));
-  T2P_TRY(upload_linear("pre_blocks.1.weight", "pre_blocks.1.bias", td, td, &pre1_, false, false, DT_F32));
-  T2P_TRY(upload_linear("pre_conv.weight", "pre_conv.bias", arch_.nf, 9 * cfg_.num_channels, &pre_conv_, true, false, DT_F32));
-  {
-    const HostTensor* w = host("pre_conv.weight", {arch_.nf, cfg_.num_channels, 3, 3});
-    if (!w) return T2P_ERR_STATE;
-    std::vector<float> m = to_nk(*w, true, false, 0);      // [nf][tap][C], unpadded
-    const int K9 = 9 * cfg_.num_channels;
-    std::vector<float> mt((size_t)K9 * arch_.nf);                // [tap][C][nf]: lanes (= output channels) read contiguously
-    for (int n = 0; n < arch_.nf; ++n)
-      for (int k = 0; k < K9; ++k) mt[(size_t)k * arch_.nf + n] = m[(size_t)n * K9 + k];
-    T2P_TRY(upload_f32(mt, &pre_conv_direct_));
-    // the same weights split into two f16 terms each, for the input convolution on the 16-bit matrix pipe (pre_conv_split_kernel).
-    // The split form needs |x| inside the f16 range: the state of a VE run stays within a few sigma_max
-    const int C = cfg_.num_channels;
-    if (dtype() != DT_F32 && (C == 5 || C == 8) && cfg_.sigma_max <= 4096.0) {
-      pre_conv_split_ = pool_.persistent(pre_conv_split_weight_bytes(C, arch_.nf));
-      if (!pre_conv_split_) return T2P_ERR_HIP;
-      T2P_TRY(launch_pre_conv_split_weights(pre_conv_direct_, pre_conv_split_, C, arch_.nf, nullptr));
-      T2P_HIP_CHECK(hipStreamSynchronize(nullptr));
-    }
-  }
-  std::vector<float> dw((size_t)arch_.temb_total * td), db(arch_.temb_total);
-  auto each_layer = [&](auto&& fn) -> int {
-    for (Stage& st : arch_.input_stages) for (Layer& l : st.layers) T2P_TRY(fn(l));
-    for (Layer& l : arch_.mid_stage.layers) T2P_TRY(fn(l));
-    for (Stage& st : arch_.out_stages) for (Layer& l : st.layers) T2P_TRY(fn(l));
-    return T2P_OK;
-  };
-  T2P_TRY(each_layer([&](Layer& l) -> int {
-    const std::string& p = l.prefix;
-    const int ci = l.in_ch, co = l.out_ch;
-    if (l.kind == 0) {
-      T2P_TRY(upload_norm(p + ".GroupNorm_0", ci, gn_groups(ci), &l.gn0));
-      T2P_TRY(upload_norm(p + ".GroupNorm_1", co, gn_groups(co), &l.gn1));
-      T2P_TRY(upload_linear(p + ".Conv_0.weight", p + ".Conv_0.bias", co, 9 * ci, &l.conv0, true));
-      if (l.up && cfg_.compute_dtype != DT_F32) {
-        // conv0 of an up block reads the 2x nearest-up-sampled map (layers.py:306-308): output phase (py, px) of pixel
-        // (2 yl + py, 2 xl + px) sees source pixel yl + floor((py + kh - 1) / 2) for kernel row kh, i.e. two source rows per
-        // phase; the taps that read the same source pixel are summed here (in fp32, before the one rounding to the compute
-        // dtype): four 2x2 convolutions on the source map with 4 / 9 of the multiplications
-        const HostTensor* w = host(p + ".Conv_0.weight", {co, ci, 3, 3});
-        if (!w) return T2P_ERR_STATE;
-        std::vector<float> w4((size_t)4 * co * 4 * ci, 0.f);
-        auto fl2 = [](int f) { return f >= 0 ? f / 2 : -((-f + 1) / 2); };
-        for (int py = 0; py < 2; ++py)
-          for (int px = 0; px < 2; ++px)
-            for (int kh = 0; kh < 3; ++kh)
-              for (int kw = 0; kw < 3; ++kw) {
-                const int ty = fl2(py + kh - 1) + 1 - py, tx = fl2(px + kw - 1) + 1 - px;     // 0 or 1
-                const size_t ph = (size_t)(py * 2 + px), tap = (size_t)(ty * 2 + tx);
-                for (int n = 0; n < co; ++n)
-                  for (int c = 0; c < ci; ++c)
-                    w4[((ph * co + n) * 4 + tap) * ci + c] += w->data[(((size_t)n * ci + c) * 3 + kh) * 3 + kw];
-              }
-        T2P_TRY(upload_matrix(pool_, w4, cfg_.compute_dtype, &l.conv0_up4));
-      }
-      T2P_TRY(upload_linear(p + ".Conv_1.weight", p + ".Conv_1.bias", co, 9 * co, &l.conv1, true));
-      if (l.has_conv2) T2P_TRY(upload_linear(p + ".Conv_2.weight", p + ".Conv_2.bias", co, ci, &l.conv2));
-      if (l.has_conv2 && !l.up && cfg_.compute_dtype != DT_F32 && ci % 64 == 0 && co % 64 == 0) {
-        // h + shortcut(x) = [conv1 | conv2] applied to [3x3 window of a1 | x] (layers.py:322-327): one K loop, one fp32 sum
-        const HostTensor* w1 = host(p + ".Conv_1.weight", {co, co, 3, 3});
-        const HostTensor* w2 = host(p + ".Conv_2.weight", {co, ci, 1, 1});
-        const HostTensor* b1 = host(p + ".Conv_1.bias", {co});
-        const HostTensor* b2 = host(p + ".Conv_2.bias", {co});
-        if (!w1 || !w2 || !b1 || !b2) return T2P_ERR_STATE;
-        const std::vector<float> m1 = to_nk(*w1, true, false, 0);
-        const size_t K1 = (size_t)9 * co, Kx = K1 + ci;
-        std::vector<float> m((size_t)co * Kx), bb(co);
-        for (int n = 0; n < co; ++n) {
-          std::copy(m1.begin() + n * K1, m1.begin() + (n + 1) * K1, m.begin() + n * Kx);
-          std::copy(w2->data.begin() + (size_t)n * ci, w2->data.begin() + (size_t)(n + 1) * ci, m.begin() + n * Kx + K1);
-          bb[n] = b1->data[n] + b2->data[n];
-        }
-        T2P_TRY(upload_matrix(pool_, m, cfg_.compute_dtype, &l.conv1x.w));
-        T2P_TRY(upload_f32(bb, &l.conv1x.b));
-        l.conv1x.N = co; l.conv1x.K = (int)Kx;
-      }
-      const HostTensor* w = host(p + ".Dense_0.weight", {co, td});
-      const HostTensor* b = host(p + ".Dense_0.bias", {co});
-      if (!w || !b) return T2P_ERR_STATE;
-      std::copy(w->data.begin(), w->data.end(), dw.begin() + (size_t)l.temb_off * td);
-      std::copy(b->data.begin(), b->data.end(), db.begin() + l.temb_off);
-    } else if (l.kind == 1) {
-      T2P_TRY(upload_norm(p + ".GroupNorm_0", ci, gn_groups(ci), &l.gn0));
-      T2P_TRY(upload_stack2(p + ".NIN_0.W", p + ".NIN_0.b", p + ".NIN_1.W", p + ".NIN_1.b", ci, ci, true, true, &l.qk));
-      T2P_TRY(upload_linear(p + ".NIN_2.W", p + ".NIN_2.b", ci, ci, &l.v, false, true));
-      T2P_TRY(upload_linear(p + ".NIN_3.W", p + ".NIN_3.b", ci, ci, &l.out, false, true));
-      if (cfg_.compute_dtype != DT_F32) {
-        const HostTensor* w2 = host(p + ".NIN_2.W", {ci, ci});      // NIN: [in][out]
-        const HostTensor* w3 = host(p + ".NIN_3.W", {ci, ci});
-        const HostTensor* b2 = host(p + ".NIN_2.b", {ci});
-        const HostTensor* b3 = host(p + ".NIN_3.b", {ci});
-        if (!w2 || !w3 || !b2 || !b3) return T2P_ERR_STATE;
-        HostTensor m;
-        m.shape = {ci, ci};
-        m.data = host_matmul(w2->data.data(), w3->data.data(), ci, ci, ci);       // [in][out]
-        std::vector<float> bb = host_matmul(b2->data.data(), w3->data.data(), 1, ci, ci);
-        for (int i = 0; i < ci; ++i) bb[i] += b3->data[i];
-        T2P_TRY(upload_matrix(pool_, to_nk(m, false, true), cfg_.compute_dtype, &l.v3.w));
-        T2P_TRY(upload_f32(bb, &l.v3.b));
-        l.v3.N = ci; l.v3.K = ci;
-        if (ci == 256 && l.qk.w && l.qk.b) {
-          l.fm_qk = pool_.persistent((size_t)2 * ci * ci * 2);
-          l.fm_v3 = pool_.persistent((size_t)ci * ci * 2);
-          if (!l.fm_qk || !l.fm_v3) return T2P_ERR_HIP;
-          T2P_TRY(launch_sf_frag_major(cfg_.compute_dtype, l.qk.w, l.fm_qk, 2 * ci, ci, nullptr));
-          T2P_TRY(launch_sf_frag_major(cfg_.compute_dtype, l.v3.w, l.fm_v3, ci, ci, nullptr));
-          T2P_HIP_CHECK(hipStreamSynchronize(nullptr));
-        }
-      }
-    } else {
-      const std::string t = p + ".transformer_blocks.0";
-      const int ctx = cfg_.context_dim;
-      T2P_TRY(upload_norm(p + ".norm", ci, 32, &l.gn0));
-      T2P_TRY(upload_linear(p + ".proj_in.weight", p + ".proj_in.bias", ci, ci, &l.proj_in));
-      T2P_TRY(upload_linear(p + ".proj_out.weight", p + ".proj_out.bias", ci, ci, &l.proj_out));
-      T2P_TRY(upload_stack2(t + ".attn1.to_q.weight", "", t + ".attn1.to_k.weight", "", ci, ci, false, false, &l.a1_qk));
-      T2P_TRY(upload_linear(t + ".attn1.to_v.weight", "", ci, ci, &l.a1_v));
-      if (cfg_.compute_dtype != DT_F32) {      // the fused attention kernel reads V row-major: q | k | v from one GEMM
-        const HostTensor* wq = host(t + ".attn1.to_q.weight", {ci, ci});
-        const HostTensor* wk = host(t + ".attn1.to_k.weight", {ci, ci});
-        const HostTensor* wv = host(t + ".attn1.to_v.weight", {ci, ci});
-        if (!wq || !wk || !wv) return T2P_ERR_STATE;
-        std::vector<float> m = wq->data;
-        m.insert(m.end(), wk->data.begin(), wk->data.end());
-        m.insert(m.end(), wv->data.begin(), wv->data.end());
-        T2P_TRY(upload_matrix(pool_, m, cfg_.compute_dtype, &l.a1_qkv.w));
-        l.a1_qkv.N = 3 * ci; l.a1_qkv.K = ci; l.a1_qkv.b = nullptr;
-      }
-      T2P_TRY(upload_linear(t + ".attn1.to_out.0.weight", t + ".attn1.to_out.0.bias", ci, ci, &l.a1_out));
-      T2P_TRY(upload_linear(t + ".attn2.to_q.weight", "", ci, ci, &l.a2_q));
-      T2P_TRY(upload_linear(t + ".attn2.to_k.weight", "", ci, ctx, &l.a2_k));
-      T2P_TRY(upload_linear(t + ".attn2.to_v.weight", "", ci, ctx, &l.a2_v));
-      T2P_TRY(upload_linear(t + ".attn2.to_out.0.weight", t + ".attn2.to_out.0.bias", ci, ci, &l.a2_out));
-      {   // GEGLU projection with rows interleaved (value_j, gate_j) so the GEMM epilogue can gate in registers
-        const HostTensor* w = host(t + ".ff.net.0.proj.weight", {8 * ci, ci});
-        const HostTensor* b = host(t + ".ff.net.0.proj.bias", {8 * ci});
-        if (!w || !b) return T2P_ERR_STATE;
-        const int inner = 4 * ci;
-        std::vector<float> wi((size_t)8 * ci * ci), bi((size_t)8 * ci);
-        for (int j = 0; j < inner; ++j) {
-          std::copy(w->data.begin() + (size_t)j * ci, w->data.begin() + (size_t)(j + 1) * ci, wi.begin() + (size_t)(2 * j) * ci);
-          std::copy(w->data.begin() + (size_t)(inner + j) * ci, w->data.begin() + (size_t)(inner + j + 1) * ci,
-                    wi.begin() + (size_t)(2 * j + 1) * ci);
-          bi[2 * j] = b->data[j];
-          bi[2 * j + 1] = b->data[inner + j];
-        }
-        T2P_TRY(upload_matrix(pool_, wi, cfg_.compute_dtype, &l.ff1.w));
-        T2P_TRY(upload_f32(bi, &l.ff1.b));
-        l.ff1.N = 8 * ci;
-        l.ff1.K = ci;
-      }
-      T2P_TRY(upload_linear(t + ".ff.net.2.weight", t + ".ff.net.2.bias", ci, 4 * ci, &l.ff2));
-      // (C = 512: the chains stream 4x the bytes per workgroup and measured equal to the separate launches: not built, DESIGN.md section 8)
-      if (cfg_.compute_dtype != DT_F32 && ci == 256 && l.a1_qkv.w) {
-        // fragment-major copies of the row-chain kernel's weights (1 KiB contiguous per MFMA fragment)
-        auto fm = [&](const void* w, int N, void** out) -> int {
-          *out = pool_.persistent((size_t)N * ci * 2);
-          if (!*out) return T2P_ERR_HIP;
-          return launch_sf_frag_major(cfg_.compute_dtype, w, *out, N, ci, nullptr);
-        };
-        T2P_TRY(fm(l.proj_in.w, ci, &l.fm_in));
-        T2P_TRY(fm(l.a1_qkv.w, 3 * ci, &l.fm_qkv));
-        T2P_TRY(fm(l.a1_out.w, ci, &l.fm_out1));
-        T2P_TRY(fm(l.a2_q.w, ci, &l.fm_q2));
-        if (ci == 256) {                        // (the chains through the feed-forward exist at C = 256 only)
-          T2P_TRY(fm(l.a2_out.w, ci, &l.fm_out2));
-          T2P_TRY(fm(l.ff1.w, 8 * ci, &l.fm_ff1));
-        }
-        T2P_HIP_CHECK(hipStreamSynchronize(nullptr));
-      }
-      if (cfg_.compute_dtype != DT_F32 && ci % 64 == 0) {
-        const HostTensor* wpo = host(p + ".proj_out.weight", {ci, ci, 1, 1});
-        const HostTensor* bpo = host(p + ".proj_out.bias", {ci});
-        const HostTensor* wf = host(t + ".ff.net.2.weight", {ci, 4 * ci});
-        const HostTensor* bf = host(t + ".ff.net.2.bias", {ci});
-        if (!wpo || !bpo || !wf || !bf) return T2P_ERR_STATE;
-        const std::vector<float> prod = host_matmul(wpo->data.data(), wf->data.data(), ci, ci, 4 * ci);    // [C][4 C]
-        std::vector<float> m((size_t)ci * 5 * ci), bb(ci);
-        for (int n = 0; n < ci; ++n) {
-          std::copy(prod.begin() + (size_t)n * 4 * ci, prod.begin() + (size_t)(n + 1) * 4 * ci, m.begin() + (size_t)n * 5 * ci);
-          std::copy(wpo->data.begin() + (size_t)n * ci, wpo->data.begin() + (size_t)(n + 1) * ci, m.begin() + (size_t)n * 5 * ci + 4 * ci);
-          double acc = bpo->data[n];
-          for (int j = 0; j < ci; ++j) acc += (double)wpo->data[(size_t)n * ci + j] * bf->data[j];
-          bb[n] = (float)acc;
-        }
-        T2P_TRY(upload_matrix(pool_, m, cfg_.compute_dtype, &l.ffpo.w));
-        T2P_TRY(upload_f32(bb, &l.ffpo.b));
-        l.ffpo.N = ci; l.ffpo.K = 5 * ci;
-        if (ci == 256 && l.fm_in) {          // fragment-major copy for the row-chain kernel's third product
-          l.fm_ffpo = pool_.persistent((size_t)ci * 5 * ci * 2);
-          if (!l.fm_ffpo) return T2P_ERR_HIP;
-          T2P_TRY(launch_sf_frag_major(cfg_.compute_dtype, l.ffpo.w, l.fm_ffpo, ci, 5 * ci, nullptr));
-          T2P_HIP_CHECK(hipStreamSynchronize(nullptr));
-        }
-      }
-      T2P_TRY(upload_norm(t + ".norm1", ci, 1, &l.ln1));
-      T2P_TRY(upload_norm(t + ".norm2", ci, 1, &l.ln2));
-      T2P_TRY(upload_norm(t + ".norm3", ci, 1, &l.ln3));
-    }
-    return T2P_OK;
-  }));
-  void* dwp = nullptr;
-  T2P_TRY(upload_matrix(pool_, dw, DT_F32, &dwp));
-  dense_all_.w = dwp;
-  dense_all_.N = arch_.temb_total;
-  dense_all_.K = td;
-  T2P_TRY(upload_f32(db, &dense_all_.b));
-  T2P_TRY(upload_norm("out.0", arch_.final_ch, gn_groups(arch_.final_ch), &head_norm_));
-  T2P_TRY(upload_linear("out.2.weight", "out.2.bias", cfg_.num_channels, 9 * arch_.final_ch, &head_conv_, true));
-
-  // 1 / sigmas[label]: sigmas = exp(linspace(log sigma_max, log sigma_min, N)) in float64
-  // (models/utils.py:50-60); the reference divides by the float64 value (ncsnpp.py:259-261).
-  const int N = cfg_.num_scales;
-  std::vector<float> inv(N);
-  const double a = std::log(cfg_.sigma_max), b = std::log(cfg_.sigma_min);
-  for (int i = 0; i < N; ++i) {
-    const double s = std::exp(a + (b - a) * (double)i / (double)(N - 1));
-    inv[i] = (float)(1.0 / s);
-  }
-  T2P_TRY(upload_f32(inv, &inv_sigma_));
-  T2P_TRY(upload_f32(std::vector<float>(N, 1.f), &unit_scale_));
+  flat_ = nullptr;
+  pack_stream_ = nullptr;
+  T2P_TRY(pack_weights());
+  T2P_HIP_CHECK(hipStreamSynchronize(nullptr));       // the fragment-major copies and the split input weights
   host_.clear();
   finalized_ = true;
+  return T2P_OK;
+}
+
+// The weights from a flat fp32 DEVICE buffer in parameters() order (a trainer's parameters or EMA shadow), packed on the device on
+// stream s.  On a finalized engine every buffer is overwritten in place: nothing is allocated and no pointer changes, so captured step
+// graphs stay valid.  Nothing is waited for; the caller keeps device_flat alive until s has passed this point.
+int Engine::load_flat(const float* device_flat, int64_t n, hipStream_t s) {
+  T2P_REQUIRE(device_flat, "load_flat: null buffer");
+  T2P_REQUIRE(n == total_, "load_flat: n must equal the element count of the engine's parameter table (" + std::to_string(total_) + ")");
+  int dev = -1;
+  T2P_HIP_CHECK(hipGetDevice(&dev));
+  T2P_REQUIRE(dev == device_, "load_flat: the engine lives on device " + std::to_string(device_) + ", the current device is " + std::to_string(dev));
+  flat_ = device_flat;
+  pack_stream_ = s;
+  const int rc = pack_weights();
+  flat_ = nullptr;
+  pack_stream_ = nullptr;
+  T2P_TRY(rc);
+  host_.clear();
+  finalized_ = true;
+  ctx_B_ = 0;      // the cached text keys / values were projected through the old to_k / to_v: score refuses until set_context ran again
   return T2P_OK;
 }
 
@@ -1483,7 +1566,7 @@ int Engine::set_context(const float* ctx, int B, int T, hipStream_t s) {
   const int dt = dtype(), D = cfg_.context_dim;
   const size_t es = dtype_size(dt);
   const long Tpad = (long)round_up((size_t)T, 8);
-  const bool realloc = (B != ctx_B_ || T != ctx_T_);
+  const bool realloc = (B != ctx_cap_B_ || T != ctx_cap_T_);   // (a weight refresh clears ctx_B_, not the buffers: they keep their addresses)
   const void* cx = ctx;
   void* conv = nullptr;
   PoolLease lease(pool_);                              // (the per-layer key / value caches are handed over with keep())
@@ -1513,7 +1596,7 @@ int Engine::set_context(const float* ctx, int B, int T, hipStream_t s) {
   for (Layer& l : arch_.mid_stage.layers) T2P_TRY(each(l));
   for (Stage& st : arch_.out_stages) for (Layer& l : st.layers) T2P_TRY(each(l));
   pool_.put(conv);
-  ctx_B_ = B; ctx_T_ = T; ctx_Tpad_ = (int)Tpad;
+  ctx_B_ = ctx_cap_B_ = B; ctx_T_ = ctx_cap_T_ = T; ctx_Tpad_ = (int)Tpad;
   return T2P_OK;
 }
 

@@ -1,5 +1,6 @@
 // Score-network engine (host side, drives the HIP kernels).  The sampling loops over it: sampler.h (PC), ddim.h (DDIM).
 #pragma once
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <string>
@@ -139,6 +140,12 @@ class Engine {
   const std::vector<ParamInfo>& params() const { return arch_.params; }
   int load_param(const char* name, const float* data, const int64_t* shape, int ndim);
   int finalize();
+  // the weights from a flat fp32 device buffer in parameters() order, packed on the device (weightpack.hip); any number of times
+  int load_flat(const float* device_flat, int64_t n, hipStream_t s);
+  int64_t num_elements() const { return total_; }
+  // the last load (either executor): bytes its packings read, bytes they wrote, how many packings (= launches of a device load) it ran
+  const int64_t* load_stats() const { return load_stats_; }
+  int device() const { return device_; }
   bool finalized() const { return finalized_; }
   int set_context(const float* ctx, int B, int T, hipStream_t s);
   // labels == nullptr: every row uses *step_counter (device int)
@@ -153,13 +160,17 @@ class Engine {
   int dtype() const { return cfg_.compute_dtype; }
 
  private:
-  int upload_linear(const std::string& wname, const std::string& bname, int N, int K, DevLinear* out,
-                    bool conv3x3 = false, bool nin = false, int force_dtype = -1);
-  int upload_stack2(const std::string& w0, const std::string& b0, const std::string& w1, const std::string& b1,
-                    int N, int K, bool nin, bool has_bias, DevLinear* out);
-  int upload_norm(const std::string& prefix, int C, int G, DevNorm* out);
-  int upload_f32(const std::vector<float>& v, float** out);
-  const HostTensor* host(const std::string& name, std::vector<int64_t> shape);
+  // the one walk that places and fills every weight-derived buffer; run by finalize() (host executor) and load_flat() (device executor)
+  int pack_weights();
+  int dest(void** slot, size_t bytes);
+  const float* psrc(const std::string& name, int64_t numel);
+  int pack(int kind, void* dst, int64_t off, int dtype, std::initializer_list<const float*> srcs, std::initializer_list<int64_t> dims);
+  int pack_frag(void** slot, const void* w, int N, int K);
+  int pack_linear(const std::string& wname, const std::string& bname, int N, int K, DevLinear* out,
+                  bool conv3x3 = false, bool nin = false, int force_dtype = -1, int cin_pad = 0);
+  int pack_stack2(const std::string& w0, const std::string& b0, const std::string& w1, const std::string& b1,
+                  int N, int K, bool nin, bool has_bias, DevLinear* out);
+  int pack_norm(const std::string& prefix, int C, int G, DevNorm* out);
 
   int run_stage(Stage& st, Act& h, const Act* skip, int B, hipStream_t s, const Layer* next_after = nullptr);
   int res_block(Layer& L, const Act& x, const Act* skip, Act* out, int B, hipStream_t s, NormHint hint = NormHint());
@@ -186,6 +197,12 @@ class Engine {
   std::unordered_map<std::string, HostTensor> host_;
   bool finalized_ = false;
   DevPool pool_;
+  std::unordered_map<std::string, std::pair<int64_t, int64_t>> poff_;   // parameter name -> (offset, element count) in a flat buffer
+  int64_t total_ = 0;
+  int device_ = 0;
+  const float* flat_ = nullptr;        // the running load: the flat device buffer (load_flat) or null (finalize: host_)
+  hipStream_t pack_stream_ = nullptr;
+  int64_t load_stats_[3] = {0, 0, 0};
 
   int cpad_ = 8;                // channel padding of the network input
   DevLinear pre0_, pre1_, pre_conv_, head_conv_, dense_all_;
@@ -194,7 +211,8 @@ class Engine {
   void* pre_conv_split_ = nullptr;     // the same, each weight as two f16 terms (pre_conv_split_kernel; 16-bit modes)
   float* inv_sigma_ = nullptr;  // [N] fp32, 1 / sigmas[label] (descending sigmas)
   float* unit_scale_ = nullptr; // [N] fp32 ones: the output scale without scale_by_sigma
-  int ctx_B_ = 0, ctx_T_ = 0, ctx_Tpad_ = 0;
+  int ctx_B_ = 0, ctx_T_ = 0, ctx_Tpad_ = 0;   // ctx_B_ == 0: no valid projection (never set, or the weights changed since)
+  int ctx_cap_B_ = 0, ctx_cap_T_ = 0;          // the shape the per-layer key / value buffers were allocated for
   void* splitk_ws_ = nullptr;
   size_t splitk_ws_bytes_ = 0;
   const float* tb_ = nullptr;   // per-eval temb biases [R][arch_.temb_total]

@@ -260,4 +260,32 @@ int launch_encode6d(const float* xyz, const int* nres, const unsigned char* atom
                     int npairs, float* coords_6d, unsigned char* mask_pair, hipStream_t s);
 int launch_embedding_gather(const void* table, int dtype, const int* ids, float* out, long ntok, int dim, int vocab, int* bad, hipStream_t s);
 
+// ---- weight packing on the device (weightpack.hip) -----------------------------------------------------------------------------
+// One packing = one kind applied to fp32 sources, written to dst in `dtype`.  Engine::pack_weights decides which packings a network
+// needs; the host load path runs them through weight_pack_host (engine.cpp), the device refresh through launch_weight_pack: same bits.
+//   kind        sources                          d[]                          writes
+//   WP_COPY     up to three vectors              n0, n1, n2                   src0 | src1 | src2 (Linear, 1x1, norms, biases, stacks)
+//   WP_ROWS     (rows, rowlen)                   rows, rowlen, ld             dst[r ld + j]
+//   WP_CONV3    (N, Ci, 3, 3)                    N, Ci, cin_pad, ld           dst[n ld + tap cin_pad + c], channels past Ci zero
+//   WP_CONV3_T  (N, C, 3, 3)                     N, C                         dst[(tap C + c) N + n]
+//   WP_NIN      one or two (K, N)                K, N, nsrc                   dst[z N K + n K + k]
+//   WP_GEGLU    (2 inner, rowlen)                inner, rowlen                rows interleaved (value_j, gate_j)
+//   WP_UP4      (co, ci, 3, 3)                   co, ci                       dst[((ph co + n) 4 + tap) ci + c], taps summed in (kh, kw) order
+//   WP_ADD      a, b                             n                            a + b (fp32)
+//   WP_PRODUCT  A (M, K), B (K, N), [addv (N)]   M, K, N, transposed, ld      sum_k A B (+ addv): fp32, ascending k, product and add rounded
+//   WP_DOT64    W (N, K), v (K), b0 (N)          N, K                         (float)(b0[n] + sum_j (double) W[n][j] v[j])
+// A pitch (ld) or cin_pad of 0 means "dense".
+enum { WP_COPY = 0, WP_ROWS = 1, WP_CONV3 = 2, WP_CONV3_T = 3, WP_NIN = 4, WP_GEGLU = 5, WP_UP4 = 6, WP_ADD = 7, WP_PRODUCT = 8, WP_DOT64 = 9 };
+struct WeightPack {
+  int kind = WP_COPY;
+  const float* src[3] = {nullptr, nullptr, nullptr};
+  void* dst = nullptr;
+  int64_t d[6] = {0, 0, 0, 0, 0, 0};
+  int dtype = DT_F32;
+};
+// checks p, fills in defaulted pitches; the packing writes the block [rows][width] at pitch ld (elements of dtype)
+int weight_pack_shape(WeightPack& p, int64_t* rows, int64_t* width, int64_t* ld);
+int launch_weight_pack(const WeightPack& p, hipStream_t s);
+void weight_pack_bytes(const WeightPack& p, int64_t rows, int64_t width, int64_t* bytes_read, int64_t* bytes_written);
+
 }  // namespace t2p

@@ -117,6 +117,7 @@ int Trainer::build() {
   T2P_REQUIRE(tc_.dropout >= 0.0 && tc_.dropout < 1.0 && tc_.ema_rate >= 0.0 && tc_.ema_rate <= 1.0, "dropout / ema_rate");
   int dev = 0;
   T2P_HIP_CHECK(hipGetDevice(&dev));       // fails without a HIP device: there is no CPU fallback
+  device_ = dev;
   T2P_TRY(arch_.build(mc_));
   long off = 0;
   for (const ParamInfo& p : arch_.params) {
@@ -235,6 +236,30 @@ int Trainer::write_tensor(int which, const char* name, const float* host_in) {
   float* dst[5] = {P_, Gr_, E_, M_, V_};
   T2P_HIP_CHECK(hipDeviceSynchronize());
   T2P_HIP_CHECK(hipMemcpy(dst[which] + p.off, host_in, (size_t)p.n * 4, hipMemcpyHostToDevice));
+  return T2P_OK;
+}
+int Trainer::buffer(int which, float** device_ptr, int64_t* n) {
+  T2P_REQUIRE(device_ptr && n, "train_buffer arguments");
+  T2P_REQUIRE(which == 0 || which == 2, "train_buffer: which is 0 (parameters) or 2 (EMA shadow), got " + std::to_string(which));
+  *device_ptr = which == 0 ? P_ : E_;
+  *n = (int64_t)total_;
+  return T2P_OK;
+}
+int Trainer::copy(int dst, int src, hipStream_t s) {
+  const bool store = dst == 5 && src == 0, copy_to = dst == 0 && src == 2, restore = dst == 0 && src == 5;
+  T2P_REQUIRE(store || copy_to || restore, "train_copy: the pairs are 0 -> 5 (store), 2 -> 0 (copy_to) and 5 -> 0 (restore), got " +
+                                               std::to_string(src) + " -> " + std::to_string(dst));
+  T2P_REQUIRE(!restore || stashed_, "train_copy: restore (5 -> 0) before any store (0 -> 5)");
+  const size_t bytes = (size_t)total_ * 4;
+  if (store && !stash_) {
+    stash_ = (float*)pool_.persistent(bytes);
+    if (!stash_) return T2P_ERR_HIP;
+  }
+  float* d = store ? stash_ : P_;
+  const float* f = store ? P_ : (copy_to ? E_ : stash_);
+  T2P_HIP_CHECK(hipMemcpyAsync(d, f, bytes, hipMemcpyDeviceToDevice, s));
+  if (store) stashed_ = true;
+  else T2P_TRY(prep_weights(P_, s));      // the kernel-layout and 16-bit copies of the convolution weights follow the parameters
   return T2P_OK;
 }
 int Trainer::set_step(int64_t step, int64_t adam_updates, int64_t ema_updates) {

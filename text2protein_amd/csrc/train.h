@@ -67,6 +67,13 @@ class Trainer {
   // calls loss(backward), averages grad_buffer() over the ranks (one RCCL all-reduce of the flat buffer), then this
   int apply(hipStream_t s);
   float* grad_buffer() const { return Gr_; }
+  // the flat fp32 device buffers in parameters() order: which = 0 parameters, 2 EMA shadow (the numbering of read_tensor)
+  int buffer(int which, float** device_ptr, int64_t* n);
+  // device-to-device copies between the flat buffers on stream s, the three verbs of the reference's EMA (ema.py:51-84): 0 -> 5 store,
+  // 2 -> 0 copy_to, 5 -> 0 restore.  5 is a stash allocated by the first store.  A copy into the parameters renews what the trainer
+  // derives from them (prep_weights)
+  int copy(int dst, int src, hipStream_t s);
+  int device() const { return device_; }
   int64_t device_bytes() const { return (int64_t)pool_.held_bytes(); }
 
  private:
@@ -124,6 +131,9 @@ class Trainer {
   float* P_ = nullptr;              // flat parameters
   float* Gr_ = nullptr;             // flat gradients
   float* M_ = nullptr; float* V_ = nullptr; float* E_ = nullptr;    // Adam moments, EMA shadow
+  float* stash_ = nullptr;          // ema.store's copy of the parameters (buffer 5 of copy(); allocated by the first store)
+  bool stashed_ = false;
+  int device_ = 0;
   double* sumsq_ = nullptr;
   float* loss_dev_ = nullptr;
   float* inv_sigma_ = nullptr;

@@ -160,6 +160,43 @@ int t2p_train_grad_buffer(t2p_trainer* t, float** device_ptr, int64_t* n) {
   API_END
 }
 
+int t2p_train_buffer(t2p_trainer* t, int which, float** device_ptr, int64_t* n) {
+  API_BEGIN
+  T2P_REQUIRE(t, "null trainer");
+  return t->impl.buffer(which, device_ptr, n);
+  API_END
+}
+
+int t2p_train_copy(t2p_trainer* t, int dst, int src, void* stream) {
+  API_BEGIN
+  T2P_REQUIRE(t, "null trainer");
+  return t->impl.copy(dst, src, (hipStream_t)stream);
+  API_END
+}
+
+// t2p_train_buffer + t2p_engine_load_flat; every mismatch is refused before anything is written
+int t2p_engine_load_from_trainer(t2p_engine* e, t2p_trainer* t, int which, void* stream) {
+  API_BEGIN
+  T2P_REQUIRE(e && t, "null argument");
+  T2P_REQUIRE(which == 0 || which == 2, "load_from_trainer: which is 0 (parameters) or 2 (EMA shadow), got " + std::to_string(which));
+  const auto& ep = e->impl.params();
+  const auto& tp = t->impl.params();
+  T2P_REQUIRE(ep.size() == tp.size(), "load_from_trainer: the trainer has " + std::to_string(tp.size()) + " parameter tensors, the engine " +
+                                          std::to_string(ep.size()));
+  for (size_t i = 0; i < ep.size(); ++i) {
+    T2P_REQUIRE(ep[i].name == tp[i].name, "load_from_trainer: parameter " + std::to_string(i) + " is " + tp[i].name + " in the trainer, " +
+                                              ep[i].name + " in the engine");
+    T2P_REQUIRE(ep[i].shape == tp[i].shape, "load_from_trainer: the shape of " + ep[i].name + " differs between the trainer and the engine");
+  }
+  T2P_REQUIRE(e->impl.device() == t->impl.device(), "load_from_trainer: the trainer lives on device " + std::to_string(t->impl.device()) +
+                                                        ", the engine on device " + std::to_string(e->impl.device()));
+  float* p = nullptr;
+  int64_t n = 0;
+  T2P_TRY(t->impl.buffer(which, &p, &n));
+  return e->impl.load_flat(p, n, (hipStream_t)stream);
+  API_END
+}
+
 int t2p_train_eval_loss(t2p_trainer* t, const t2p_train_batch* batch, float* loss_host, void* stream) {
   API_BEGIN
   T2P_REQUIRE(t && batch, "null argument");

@@ -173,8 +173,12 @@ class DiffusionSampler:
         return self.ddim_sample(shape, cond)
 
     def ddim_sample(self, shape, cond, clip_scheme='static', condition=None, noise_fn=None, call_index=None, force_ops=False,
-                    trace=None):
+                    trace=None, train_dtype="f16"):
         """diffusion_sampler.py:72-114 -> the sample, (B, C, L, L) float32 on the model's device.
+
+        A ``HipTrainModel`` as this sampler's ``model`` is sampled through ``model.sampling_model(train_dtype)``: a
+        ``HipScoreModel`` refreshed on the device from the trainer's current parameters at every call (train.py:198-215: after
+        ``ema.copy_to`` those are the EMA).  The fused stepper's ``set_context`` runs on every call, so no text cache survives a refresh.
 
         Extensions: ``condition`` (see the module text); ``noise_fn(shape) -> CPU tensor`` injects the standard-normal draws in
         the reference's order (the prior, then one per step with ``t_next >= 0``, drawn even when sigma == 0 as the reference
@@ -183,6 +187,13 @@ class DiffusionSampler:
         prediction of every step."""
         if cond is None:
             raise T2PError("cond is required: the engine needs a text context (HipScoreModel)")
+        if hasattr(self.model, "sampling_model"):
+            trainer = self.model
+            self.model = trainer.sampling_model(train_dtype)
+            try:
+                return self.ddim_sample(shape, cond, clip_scheme, condition, noise_fn, call_index, force_ops, trace)
+            finally:
+                self.model = trainer
         clip = self._clip(clip_scheme)
         shape = tuple(int(v) for v in shape)
         fused = isinstance(self.model, HipScoreModel) and not force_ops
@@ -238,7 +249,10 @@ class DiffusionSampler:
 
 class DDIMStepper:
     """Handle on the fused C++ loop (t2p_ddim_*): one ``step`` = one iteration of the reference's loop body
-    (diffusion_sampler.py:94-112) enqueued on the current stream."""
+    (diffusion_sampler.py:94-112) enqueued on the current stream.
+
+    After the model's weights were refreshed (``HipScoreModel.load_from``) call ``set_context`` again before the next ``step``: the
+    engine's text caches went with the old weights and a step without it is refused.  ``ddim_sample`` sets it on every call."""
 
     def __init__(self, model, sampler, batch, clip=True, seed=0):
         if not isinstance(model, HipScoreModel):

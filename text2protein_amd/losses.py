@@ -35,6 +35,7 @@ from .sde_lib import VESDE, VPSDE, subVPSDE
 
 _COND_FLAGS = {"length": 1, "ss": 2, "inpainting": 4}
 PARAM, GRAD, EMA, EXP_AVG, EXP_AVG_SQ = 0, 1, 2, 3, 4
+STASH = 5          # t2p_train_copy only: where ema.store keeps the parameters
 
 
 def condition_flags(condition) -> int:
@@ -156,6 +157,7 @@ class HipTrainModel:
         self.training = True
         self._keep = []
         self._sde = None          # (kind, parameters) once set_sde ran; the native default is VE with the model's sigmas
+        self._samplers = {}       # compute dtype -> HipScoreModel fed from this trainer's buffers (sampling_model)
 
     # -- nn.Module-like surface ----------------------------------------------------------------------------------------
     def train(self, mode=True):
@@ -171,6 +173,22 @@ class HipTrainModel:
     def parameters(self):
         """Handle the optimizer / EMA views are built from (the tensors themselves stay on the device)."""
         return _ParamHandle(self)
+
+    def sampling_model(self, dtype="f16"):
+        """A ``HipScoreModel`` of compute dtype ``dtype`` on this trainer's GPU holding the trainer's CURRENT parameters (after
+        ``ema.copy_to(model.parameters())`` those are the EMA): created at the first call for each dtype, refreshed on the device
+        by every call (``HipScoreModel.load_from``).  What the samplers evaluate when they are handed this model: the trainer's own
+        forward pass keeps every activation for the backward pass and is an order of magnitude slower per evaluation."""
+        from .model import HipScoreModel
+        m = self._samplers.get(dtype)
+        if m is None:
+            m = self._samplers[dtype] = HipScoreModel(self.config, dtype=dtype, device=self.device)
+        return m.load_from(self, "param")
+
+    def copy_buffer(self, dst, src):
+        """Device-to-device copy between the flat buffers (``t2p_train_copy``): 5 <- 0 store, 0 <- 2 copy_to, 0 <- 5 restore."""
+        torch.cuda.set_device(self.device)
+        check(self.lib.t2p_train_copy(self._h, int(dst), int(src), stream_ptr()))
 
     def param_table(self):
         out = []
@@ -480,6 +498,25 @@ class ExponentialMovingAverage:
     @property
     def shadow_params(self):
         return list(self.model.read(EMA).values())
+
+    def _same_model(self, parameters):
+        if not isinstance(parameters, _ParamHandle) or parameters.model is not self.model:
+            raise TypeError("takes model.parameters() of the HipTrainModel this EMA was created from")
+
+    def store(self, parameters):
+        """ema.py:72-78: save the current parameters for ``restore`` (a device-to-device copy into the trainer's stash)."""
+        self._same_model(parameters)
+        self.model.copy_buffer(STASH, PARAM)
+
+    def copy_to(self, parameters):
+        """ema.py:51-62: the parameters become the EMA shadow (device-to-device)."""
+        self._same_model(parameters)
+        self.model.copy_buffer(PARAM, EMA)
+
+    def restore(self, parameters):
+        """ema.py:80-84 (and :64-70): the parameters saved by ``store`` come back; raises before any ``store``."""
+        self._same_model(parameters)
+        self.model.copy_buffer(PARAM, STASH)
 
     def state_dict(self):
         return dict(decay=self.decay, num_updates=self.num_updates, shadow_params=self.shadow_params)      # ema.py:86-88

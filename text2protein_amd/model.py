@@ -136,6 +136,28 @@ class HipScoreModel:
             raise T2PError(f"EMA list has {len(shadow_params)} tensors, model has {len(self._specs)}")
         return self.load_state_dict(OrderedDict((s.name, p) for s, p in zip(self._specs, shadow_params)))
 
+    def load_from(self, train_model, which="ema"):
+        """The weights of a ``HipTrainModel`` on the same GPU -- its EMA shadow (``which="ema"``) or its current parameters
+        (``"param"``) -- packed into the engine's layouts by kernels, without leaving the device: the block
+        ``ema.store; ema.copy_to; sampling_fn(...); ema.restore`` of the reference's training loop (train.py:198-215) costs no host
+        round trip.  Bit for bit what ``load_ema_shadow`` / ``load_state_dict`` of the same numbers give.  May be called any number
+        of times, whichever way the model was first loaded: later calls overwrite the same device buffers (captured step graphs
+        stay valid, ``device_bytes()`` does not change).  The compute dtypes of the two models may differ.
+
+        The engine's cached text projections go with the old weights: the next call of the model re-projects its context, and a
+        ``PCStepper`` / ``DDIMStepper`` on this model needs its ``set_context`` again before the next step."""
+        code = {"param": 0, "ema": 2}.get(which, which) if isinstance(which, str) else which
+        if isinstance(code, str) or isinstance(code, bool) or not isinstance(code, int):
+            raise ValueError(f"which={which!r}: 'ema' or 'param'")
+        h = getattr(train_model, "_h", None)
+        if not h or not hasattr(train_model, "sampling_model"):
+            raise TypeError("load_from takes a HipTrainModel")
+        torch.cuda.set_device(self.device)
+        check(self.lib.t2p_engine_load_from_trainer(self._h, h, int(code), stream_ptr()))
+        self._finalized = True
+        self._ctx_key = None
+        return self
+
     def set_context(self, context):
         """Project the frozen text embedding through every to_k / to_v once (loop-invariant)."""
         context = context.to(self.device, torch.float32).contiguous()

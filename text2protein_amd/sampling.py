@@ -307,7 +307,12 @@ def raise_allreduce_error(pending, fallback):
 
 class PCStepper:
     """Handle on the fused C++ sampler (t2p_sampler_*): one ``step`` = one iteration of the loop
-    body of the reference ``pc_sampler`` (sampling.py:279-285) enqueued on the current stream."""
+    body of the reference ``pc_sampler`` (sampling.py:279-285) enqueued on the current stream.
+
+    After the model's weights were refreshed (``HipScoreModel.load_from``) the engine's text caches are void: set the context again
+    (``model.set_context``, or this object's ``set_context`` under guidance) before the next ``step`` / ``step_graph`` -- a step
+    without it is refused.  A captured ``step_graph`` stays valid across a refresh (the weights are overwritten in place).
+    ``get_pc_sampler`` sets the context on every call."""
 
     def __init__(self, model, sde, batch, snr, n_steps=1, probability_flow=False, denoise=True, eps=1e-5, seed=0,
                  global_batch=None, all_reduce=None, guidance_w=None):
@@ -463,7 +468,7 @@ def get_pc_sampler(sde, shape, predictor, corrector, snr, n_steps=1, probability
     ``w out(ctx) + (1 - w) out(0)`` (see ``get_score_fn``); ``w == 1`` is the plain conditional run.  The number of function
     evaluations returned stays ``sde.N * (n_steps + 1)`` as in the reference; with ``w != 1`` each of them is one network
     evaluation at twice the batch (two evaluations for a callable that is not a ``HipScoreModel``).
-    The returned ``pc_sampler(model, condition=None, context=None, noise_fn=None, n_iter=None, call_index=None)``
+    The returned ``pc_sampler(model, condition=None, context=None, noise_fn=None, n_iter=None, call_index=None, train_dtype="f16")``
     accepts ``noise_fn(shape) -> CPU tensor`` to inject the standard-normal draws in the
     reference's order (prior, then corrector and predictor of each step), and ``n_iter`` to stop
     after that many PC steps (benchmarks / tests).  Like the reference, every call draws fresh noise:
@@ -485,10 +490,16 @@ def get_pc_sampler(sde, shape, predictor, corrector, snr, n_steps=1, probability
             state["model"] = model
         return state["sampler"]
 
-    def pc_sampler(model, condition=None, context=None, noise_fn=None, n_iter=None, call_index=None):
-        """The PC sampler function -> (samples, number of function evaluations)."""
+    def pc_sampler(model, condition=None, context=None, noise_fn=None, n_iter=None, call_index=None, train_dtype="f16"):
+        """The PC sampler function -> (samples, number of function evaluations).
+
+        ``model`` may be a ``HipTrainModel``: the run then goes through ``model.sampling_model(train_dtype)``, a ``HipScoreModel``
+        refreshed on the device from the trainer's current parameters at every call (train.py:198-215: after ``ema.copy_to`` those
+        are the EMA).  The context is projected anew on every call, so a refresh between two calls never leaves stale text caches."""
         lib = _lib.load()
         torch.cuda.set_device(device)
+        if hasattr(model, "sampling_model"):
+            model = model.sampling_model(train_dtype)
         n_iter = sde.N if n_iter is None else int(n_iter)
         if n_iter > sde.N:
             raise ValueError(f"n_iter {n_iter} exceeds sde.N {sde.N}")
