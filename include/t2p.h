@@ -154,6 +154,23 @@ int t2p_sampler_set_guidance(t2p_sampler* s, double w, int enabled);
  * the engine at batch 2B; otherwise forwards to t2p_engine_set_context at batch B.  batch != cfg.batch is refused, nothing changes.
  * A guided step without it is refused. */
 int t2p_sampler_set_context(t2p_sampler* s, const float* context, int batch, int tokens, void* stream);
+/* Replacement inpainting (reference score_sde_pytorch/inpainting.py, get_pc_inpainter): fixes a motif for a network that was NOT
+ * trained under the `inpainting` condition.  After every corrector update (its last inner Langevin step) and every predictor update
+ * of loop step i the known region is overwritten with the data noised to that level,
+ *     r = fl(fl(mean_coef[i] data) + fl(z std[i])),   x = known ? r : x,   x_mean = known ? fl(mean_coef[i] data) : x
+ * (off the known region x_mean is the NEW x, not the update's mean: inpainting.py:46).  This happens inside the update kernels:
+ * a step enqueues the same number of dispatches with and without it.  known: device uint8 (B,C,L,L), 1 = known (the reference's
+ * mask); data: device fp32 (B,C,L,L); both borrowed.  mean_coef / std: HOST tables of N floats, (a_i, s_i) of
+ * sde.marginal_prob(data, t_i), t = linspace(T, eps, N) (VE: a_i == 1), copied.  All four NULL clears the replacement; tables
+ * without pointers or pointers without tables are refused and nothing changes.  Under a condition (t2p_sampler_set_condition) the
+ * precedence per element is: frozen by the condition -> x_initial; else known -> replaced; else the update.  Under guidance both
+ * halves of x receive the replaced state.  t2p_sampler_run with prior_given == 0 starts from known ? data : prior.
+ * z is drawn inside the kernels (Philox streams 0x80000000 after the corrector, 0x80000001 after the predictor; step word = loop
+ * step) unless t2p_sampler_set_inpaint_noise gives device draws (B,C,L,L) for the following steps (fixture replay; NULL = device
+ * draws again).  Injected corrector-side noise with n_steps_each > 1 is refused, as in t2p_sampler_step; a captured step
+ * (t2p_sampler_step_graph) refuses injected noise and re-captures when known / data change. */
+int t2p_sampler_set_inpaint(t2p_sampler* s, const uint8_t* known, const float* data, const float* mean_coef, const float* std);
+int t2p_sampler_set_inpaint_noise(t2p_sampler* s, const float* after_corrector, const float* after_predictor);
 /* reset the step counter to `step` (0 at the start of a run) for a fresh x; a step at index >= N is refused */
 int t2p_sampler_reset(t2p_sampler* s, int step, void* stream);
 /* One PC step at the current step index, in place on x (device fp32 (B,C,L,L)); x_mean receives the
@@ -558,6 +575,29 @@ int t2p_op_guided_langevin_update(const float* x, const float* o_c, const float*
 int t2p_op_guided_predictor(const float* x, const float* o_c, const float* o_u, const float* noise, const uint8_t* mask,
                             const float* x_initial, float* x_out, float* x_out2, float* x_mean_out, int64_t n, float w, float w1,
                             float scale, float G, float x_coef, int probability_flow, void* stream);
+/* The two update kernels of a PC step WITH the replacement of t2p_sampler_set_inpaint, the kernels the loop runs: arguments as
+ * t2p_op_guided_langevin_update / t2p_op_guided_predictor (o_u NULL: the plain forms), then the replacement.  (a, s) are the
+ * values mean_coef / std, or, with device tables of n_table floats, row `step` of them.  noise: device z, or NULL = drawn in the
+ * kernel as t2p_op_philox_normal(seed, stream_id) draws with `step` in the step word.  The 16-byte path additionally needs data and
+ * noise 16-byte and known 4-byte aligned. */
+typedef struct t2p_inpaint_replace {
+  const uint8_t* known;       /* device uint8, 1 = known */
+  const float* data;          /* device fp32 */
+  const float* noise;         /* device fp32 or NULL */
+  const float* mean_table;    /* device fp32[n_table] or NULL (with std_table) */
+  const float* std_table;
+  int32_t n_table;
+  int32_t step;
+  float mean_coef, std;
+  uint64_t seed, stream_id;
+} t2p_inpaint_replace;
+int t2p_op_inpaint_langevin_update(const float* x, const float* o_c, const float* o_u, const float* noise, const uint8_t* mask,
+                                   const float* x_initial, float* x_out, float* x_out2, float* x_mean_out, int64_t n, float w, float w1,
+                                   float scale, const float* sums, float batch_total, float snr, float alpha,
+                                   const t2p_inpaint_replace* replace, void* stream);
+int t2p_op_inpaint_predictor(const float* x, const float* o_c, const float* o_u, const float* noise, const uint8_t* mask,
+                             const float* x_initial, float* x_out, float* x_out2, float* x_mean_out, int64_t n, float w, float w1,
+                             float scale, float G, float x_coef, int probability_flow, const t2p_inpaint_replace* replace, void* stream);
 int t2p_op_philox_normal(float* out, int64_t n, uint64_t seed, uint64_t stream_id, void* stream);
 int t2p_op_convert(const float* in, void* out, int dtype, int64_t n, void* stream);
 /* One weight packing of t2p_engine_load_flat on caller-supplied device buffers: fp32 sources -> dst in `dtype`.  kind / dims (a pitch or

@@ -32,6 +32,10 @@ Differences, all at the edges of the hot path:
     The conditions and the output files are the same.
   * ``--pc_guidance_w W`` (with the default ``--sampler pc``, any config): the same guidance inside the predictor-corrector loop,
     every score made of ``W out(text) + (1 - W) out(no text)`` from one evaluation at twice the batch.  Unset is the plain loop.
+  * ``--inpaint_mode replace`` (default ``condition``, today's behaviour): the residues ``--mask_info`` selects are designed and
+    everything else of the chain given with ``--pdb`` / ``--inpaint_coords`` is held by *replacement* (the reference's
+    score_sde_pytorch/inpainting.py: the known region is overwritten with the data noised to the current level after every
+    update), which needs no ``inpainting`` condition in the config and so works with every checkpoint.  Not with ``--sampler ddim``.
 Under ``python -m torch.distributed.run --nproc-per-node N`` (or with ``--gpus N``, which starts the N ranks
 itself) every rank samples ``--batch_size`` chains on its own GPU and rank 0 gathers them with one RCCL
 all_gather before writing (text2protein_amd/distributed.py).  ``--global_batch_norm`` reproduces the reference's
@@ -99,6 +103,9 @@ def main():
                              "w out(text) + (1 - w) out(no text) from one evaluation at twice the batch; 1 = the plain conditional "
                              "run; unset (default) = no guidance.  (--guidance_w belongs to --sampler ddim and defaults to 0, the "
                              "unconditional run)")
+    parser.add_argument("--inpaint_mode", type=str, default="condition", choices=["condition", "replace"],
+                        help="condition: the known maps enter as the config's `inpainting` condition (default); replace: replacement "
+                             "inpainting in the predictor-corrector loop, for any checkpoint (needs --pdb or --inpaint_coords)")
     args = parser.parse_args()
 
     if args.pc_guidance_w is not None:                                  # before anything touches a device
@@ -106,6 +113,12 @@ def main():
             raise SystemExit("--pc_guidance_w guides the predictor-corrector loop: with --sampler ddim give --guidance_w")
         if args.pc_guidance_w != args.pc_guidance_w or args.pc_guidance_w in (float("inf"), float("-inf")):
             raise SystemExit("--pc_guidance_w must be finite")
+    replace = args.inpaint_mode == "replace"
+    if replace:
+        if args.sampler == "ddim":
+            raise SystemExit("--inpaint_mode replace belongs to the predictor-corrector loop: not with --sampler ddim")
+        if args.pdb is None and args.inpaint_coords is None:
+            raise SystemExit("--inpaint_mode replace needs the known 6D maps: give --pdb <file> or --inpaint_coords <file.pt|synthetic>")
     assert not (args.pdb is not None and args.select_length)
     if args.pdb is not None and args.inpaint_coords is not None:
         raise SystemExit("--pdb and --inpaint_coords both name a source of the known 6D maps: give one")
@@ -155,7 +168,7 @@ def main():
             # sampling_6d.py:146-147; the chain is the same for every iteration, so it is featurised once (and before the model is
             # built: a file that cannot be used is reported at once)
             pdb_condition = get_conditions_from_pdb(args.pdb, config, chain=args.chain, mask_info=args.mask_info or "1:5,10:15",
-                                                    batch_size=args.batch_size, sse=sse)
+                                                    batch_size=args.batch_size, sse=sse, with_batch=replace)
         except (OSError, ValueError, T2PError) as e:
             raise SystemExit(f"--pdb: {e}")
 
@@ -193,6 +206,21 @@ def main():
 
         def sampling_fn(model, condition=None, context=None):
             return ddim.ddim_sample(sampling_shape, context, condition=condition), evaluations
+    elif replace:
+        from text2protein_amd.inpainting import get_pc_inpainter, known_from_mask_info
+        if args.pc_guidance_w is not None:
+            kw["guidance_w"] = args.pc_guidance_w
+        inpainter = get_pc_inpainter(sde, sampling.get_predictor(config.sampling.predictor.lower()),
+                                     sampling.get_corrector(config.sampling.corrector.lower()), config.sampling.snr,
+                                     n_steps=config.sampling.n_steps_each, probability_flow=config.sampling.probability_flow,
+                                     denoise=config.sampling.noise_removal, eps=sampling_eps, seed=D.rank_seed(args.seed, rank), **kw)
+
+        def sampling_fn(model, condition=None, context=None):
+            # the maps are held by replacement, not by the `inpainting` condition; the other conditions apply as always
+            batch = condition.pop("_batch")
+            condition.pop("inpainting", None)
+            data, known_mask = known_from_mask_info(config, batch, args.mask_info or "1:5,10:15", condition)
+            return inpainter(model, data, known_mask, context=context, condition=condition)
     else:
         if args.pc_guidance_w is not None:
             kw["guidance_w"] = args.pc_guidance_w
@@ -251,10 +279,13 @@ def main():
             mask = get_mask_all_lengths(config, batch_size=B)[args.length_index - 1]
             condition = {"length": mask.to(device)}
         elif pdb_condition is not None:
-            condition = pdb_condition
+            condition = dict(pdb_condition)
         elif known is not None:
             # sampling_6d.py:146-147 -> get_condition_from_batch (utils.py:84-106): every condition the model was trained with
             condition = to_device(get_condition_from_batch(config, known, mask_info=args.mask_info or "1:5,10:15"))
+            if replace:
+                condition["_batch"] = {"coords_6d": known["coords_6d"].to(device),
+                                       **{k: known[k] for k in ("lengths", "aa_str") if k in known}}
         else:
             condition = {}
         sample, n = sampling_fn(score_model, condition=condition, context=context)

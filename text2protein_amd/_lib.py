@@ -56,6 +56,12 @@ class TrainBatch(C.Structure):           # t2p_train_batch
                 ("batch", C.c_int32), ("tokens", C.c_int32), ("t", C.c_void_p), ("z", C.c_void_p)]
 
 
+class InpaintReplace(C.Structure):       # t2p_inpaint_replace
+    _fields_ = [("known", C.c_void_p), ("data", C.c_void_p), ("noise", C.c_void_p), ("mean_table", C.c_void_p),
+                ("std_table", C.c_void_p), ("n_table", C.c_int32), ("step", C.c_int32), ("mean_coef", C.c_float), ("std", C.c_float),
+                ("seed", C.c_uint64), ("stream_id", C.c_uint64)]
+
+
 _vp, _i, _i64, _f, _u64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint64
 
 # name -> (restype, argtypes); every symbol declared in include/t2p.h
@@ -93,6 +99,13 @@ SIGNATURES = {
     "t2p_op_guided_langevin_norms": (_i, [_vp, _vp, _vp, _i, _i64, _f, _f, _f, _vp, _vp, _vp]),
     "t2p_op_guided_langevin_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _vp, _f, _f, _f, _vp]),
     "t2p_op_guided_predictor": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i, _vp]),
+    # replacement inpainting in the PC loop
+    "t2p_sampler_set_inpaint": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "t2p_sampler_set_inpaint_noise": (_i, [_vp, _vp, _vp]),
+    "t2p_op_inpaint_langevin_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _vp, _f, _f, _f,
+                                            C.POINTER(InpaintReplace), _vp]),
+    "t2p_op_inpaint_predictor": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f, _f, _f, _f, _f, _i,
+                                      C.POINTER(InpaintReplace), _vp]),
     # DDIM sampler with classifier-free guidance (csrc/ddim.hip)
     "t2p_ddim_create": (_i, [_vp, C.POINTER(DdimConfig), C.POINTER(DdimStepRow), C.POINTER(_vp)]),
     "t2p_ddim_destroy": (None, [_vp]),

@@ -152,10 +152,11 @@ def get_condition_from_batch(config, batch, mask_info=None):
     return out
 
 
-def get_conditions_from_pdb(pdb, config, chain="A", mask_info=None, batch_size=8, sse=None):
+def get_conditions_from_pdb(pdb, config, chain="A", mask_info=None, batch_size=8, sse=None, with_batch=False):
     """utils.py:122-137: chain ``chain`` of the file ``pdb``, featurised (dataset.py:311-325) and padded to ``max_res_num``
     (PaddingCollate), repeated over the batch, then ``get_condition_from_batch``; every tensor on ``config.device``, which must be a
-    GPU.  ``sse``: one of a / b / c per residue (P-SEA letters), required by the 8-channel layout.  A chain outside
+    GPU.  ``sse``: one of a / b / c per residue (P-SEA letters), required by the 8-channel layout.  ``with_batch`` adds the
+    featurised batch itself under ``"_batch"`` (replacement inpainting reads the maps and the residue counts from it).  A chain outside
     ``[min_res_num, max_res_num]`` is refused (the reference's dataset drops it, dataset.py:282-284)."""
     from .encode import encode_6d_batch, read_backbone
     xyz, atom_ok, nres = read_backbone(pdb, chain)
@@ -177,7 +178,10 @@ def get_conditions_from_pdb(pdb, config, chain="A", mask_info=None, batch_size=8
     batch = {"coords_6d": one["coords_6d"].repeat(batch_size, 1, 1, 1), "mask_pair": one["mask_pair"].repeat(batch_size, 1, 1),
              "lengths": one["lengths"].repeat(batch_size), "ss_indices": one["ss_indices"] * batch_size}
     cond = get_condition_from_batch(config, batch, mask_info=mask_info)
-    return {k: {kk: vv.to(device) for kk, vv in v.items()} if isinstance(v, dict) else v.to(device) for k, v in cond.items()}
+    out = {k: {kk: vv.to(device) for kk, vv in v.items()} if isinstance(v, dict) else v.to(device) for k, v in cond.items()}
+    if with_batch:
+        out["_batch"] = {"coords_6d": batch["coords_6d"], "lengths": batch["lengths"]}
+    return out
 
 
 def synthetic_condition(config, batch, kind, device, length=100, mask_info="1:5,10:15", seed=0):

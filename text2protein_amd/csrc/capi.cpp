@@ -193,6 +193,20 @@ int t2p_sampler_set_context(t2p_sampler* s, const float* context, int batch, int
   API_END
 }
 
+int t2p_sampler_set_inpaint(t2p_sampler* s, const uint8_t* known, const float* data, const float* mean_coef, const float* std) {
+  API_BEGIN
+  T2P_REQUIRE(s, "null sampler");
+  return s->impl.set_inpaint(known, data, mean_coef, std);
+  API_END
+}
+
+int t2p_sampler_set_inpaint_noise(t2p_sampler* s, const float* after_corrector, const float* after_predictor) {
+  API_BEGIN
+  T2P_REQUIRE(s, "null sampler");
+  return s->impl.set_inpaint_noise(after_corrector, after_predictor);
+  API_END
+}
+
 int t2p_sampler_reset(t2p_sampler* s, int step, void* stream) {
   API_BEGIN
   T2P_REQUIRE(s, "null sampler");
@@ -698,6 +712,66 @@ int t2p_op_guided_predictor(const float* x, const float* o_c, const float* o_u, 
   GuidedScore g;
   g.o_c = o_c; g.o_u = o_u; g.w = w; g.w1 = w1; g.scale = scale;
   return launch_predictor_update(a, g, x_out2, nullptr, G, probability_flow, (hipStream_t)stream, nullptr, x_coef);
+  API_END
+}
+
+// the replacement block of the two entries below; with tables the step index goes to a device counter (*counter, freed by the caller)
+static int op_inpaint_replace(const t2p_inpaint_replace* r, InpaintReplace* out, int** counter, hipStream_t s) {
+  T2P_REQUIRE(r && r->known && r->data, "inpaint replacement: known and data are required");
+  T2P_REQUIRE((r->mean_table == nullptr) == (r->std_table == nullptr), "inpaint replacement: the mean and std tables go together");
+  T2P_REQUIRE(!r->mean_table || (r->step >= 0 && r->step < r->n_table), "inpaint replacement: step outside the tables");
+  T2P_REQUIRE(r->step >= 0, "inpaint replacement: step is negative");
+  out->known = r->known; out->data = r->data; out->noise = r->noise; out->mean_coef = r->mean_coef; out->std = r->std;
+  out->seed = r->seed; out->stream = r->stream_id; out->step = (unsigned int)r->step;
+  if (r->mean_table) {
+    T2P_HIP_CHECK(hipMalloc((void**)counter, 256));
+    const int32_t step = r->step;
+    T2P_HIP_CHECK(hipMemcpyAsync(*counter, &step, sizeof(step), hipMemcpyHostToDevice, s));
+    T2P_HIP_CHECK(hipStreamSynchronize(s));
+    out->mean_table = r->mean_table; out->std_table = r->std_table; out->n_table = r->n_table; out->step_counter = *counter;
+  }
+  return T2P_OK;
+}
+static int op_inpaint_done(int rc, int* counter, hipStream_t s) {
+  if (counter) {
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(counter);
+  }
+  return rc;
+}
+
+int t2p_op_inpaint_langevin_update(const float* x, const float* o_c, const float* o_u, const float* noise, const uint8_t* mask,
+                                   const float* x_initial, float* x_out, float* x_out2, float* x_mean_out, int64_t n, float w, float w1,
+                                   float scale, const float* sums, float batch_total, float snr, float alpha,
+                                   const t2p_inpaint_replace* replace, void* stream) {
+  API_BEGIN
+  hipStream_t s = (hipStream_t)stream;
+  SdeUpdateArgs a;
+  a.x = x; a.noise = noise; a.mask = mask; a.x_initial = x_initial; a.x_out = x_out; a.x_mean_out = x_mean_out; a.n = n;
+  GuidedScore g;
+  g.o_c = o_c; g.o_u = o_u; g.w = w; g.w1 = w1; g.scale = scale;
+  InpaintReplace r;
+  int* counter = nullptr;
+  int rc = op_inpaint_replace(replace, &r, &counter, s);
+  if (rc == T2P_OK) rc = launch_langevin_update(a, g, x_out2, sums, batch_total, snr, alpha, s, nullptr, &r);
+  return op_inpaint_done(rc, counter, s);
+  API_END
+}
+
+int t2p_op_inpaint_predictor(const float* x, const float* o_c, const float* o_u, const float* noise, const uint8_t* mask,
+                             const float* x_initial, float* x_out, float* x_out2, float* x_mean_out, int64_t n, float w, float w1,
+                             float scale, float G, float x_coef, int probability_flow, const t2p_inpaint_replace* replace, void* stream) {
+  API_BEGIN
+  hipStream_t s = (hipStream_t)stream;
+  SdeUpdateArgs a;
+  a.x = x; a.noise = noise; a.mask = mask; a.x_initial = x_initial; a.x_out = x_out; a.x_mean_out = x_mean_out; a.n = n;
+  GuidedScore g;
+  g.o_c = o_c; g.o_u = o_u; g.w = w; g.w1 = w1; g.scale = scale;
+  InpaintReplace r;
+  int* counter = nullptr;
+  int rc = op_inpaint_replace(replace, &r, &counter, s);
+  if (rc == T2P_OK) rc = launch_predictor_update(a, g, x_out2, nullptr, G, probability_flow, s, nullptr, x_coef, &r);
+  return op_inpaint_done(rc, counter, s);
   API_END
 }
 

@@ -1482,39 +1482,55 @@ int launch_langevin_norms(const GuidedScore& g, const float* noise, int B, long 
   return T2P_OK;
 }
 
-template <bool VEC>
+template <bool VEC, bool REPL>
 __global__ __launch_bounds__(256) void langevin_update_kernel(SdeUpdateArgs a, GuidedScore g, float* x_out2, const float* sums,
-                                                              float batch_total, float snr, float alpha, const float* alpha_table) {
+                                                              float batch_total, float snr, float alpha, const float* alpha_table,
+                                                              InpaintReplace rp) {
   // step_size = (snr * noise_norm / grad_norm)^2 * 2 * alpha   (sampling.py:195); VP: alpha = sde.alphas[timestep] (sampling.py:184-186)
   if (alpha_table) alpha = alpha_table[min(max(*g.step_counter, 0), g.n_table - 1)];
   const float gn = sums[0] / batch_total, nn = sums[1] / batch_total;
   const float r = snr * nn / gn;
   const float step = r * r * 2.f * alpha;
   const float nscale = sqrtf(step * 2.f);
-  update_loop<VEC, false>(a, g, x_out2, QuadDraw(), [=](float x, float s, float z, float* xm) {
+  update_loop<VEC, false, REPL>(a, g, x_out2, QuadDraw(), [=](float x, float s, float z, float* xm) {
     *xm = __builtin_fmaf(step, s, x);
     return __builtin_fmaf(nscale, z, *xm);
-  });
+  }, rp);
+}
+
+// the checks both update launchers make of a replacement; *vec: its pointers allow the 16-byte path
+static int inpaint_replace_ok(const InpaintReplace* r, bool* vec) {
+  if (!r) return T2P_OK;
+  T2P_REQUIRE(r->known && r->data, "replacement inpainting: known and data go together");
+  T2P_REQUIRE((r->mean_table == nullptr) == (r->std_table == nullptr), "replacement inpainting: the mean and std tables go together");
+  T2P_REQUIRE(!r->mean_table || (r->step_counter && r->n_table > 0), "replacement inpainting: the tables need the step counter and their length");
+  *vec = quad_vec_ok(4, {r->data, r->noise}, r->known);
+  return T2P_OK;
 }
 
 int launch_langevin_update(const SdeUpdateArgs& a, const GuidedScore& g, float* x_out2, const float* sums, float batch_total,
-                           float snr, float alpha, hipStream_t s, const float* alpha_table) {
+                           float snr, float alpha, hipStream_t s, const float* alpha_table, const InpaintReplace* r) {
   T2P_REQUIRE(a.x && g.o_c && a.noise && a.x_out && sums && a.n > 0, "langevin_update arguments");
   T2P_REQUIRE((a.mask == nullptr) == (a.x_initial == nullptr), "mask and x_initial go together");
   T2P_REQUIRE((!g.scale_table && !alpha_table) || (g.step_counter && g.n_table > 0), "a per-step table needs the step counter and its length");
   const dim3 grid(ew_grid((a.n + 3) / 4));
-  if (quad_vec_ok(a.n, {a.x, g.o_c, g.o_u, a.noise, a.x_initial, a.x_out, x_out2, a.x_mean_out}, a.mask))
-    hipLaunchKernelGGL(langevin_update_kernel<true>, grid, dim3(256), 0, s, a, g, x_out2, sums, batch_total, snr, alpha, alpha_table);
-  else
-    hipLaunchKernelGGL(langevin_update_kernel<false>, grid, dim3(256), 0, s, a, g, x_out2, sums, batch_total, snr, alpha, alpha_table);
+  bool rvec = true;
+  T2P_TRY(inpaint_replace_ok(r, &rvec));
+  const bool vec = rvec && quad_vec_ok(a.n, {a.x, g.o_c, g.o_u, a.noise, a.x_initial, a.x_out, x_out2, a.x_mean_out}, a.mask);
+  const InpaintReplace rp = r ? *r : InpaintReplace();
+#define T2P_LAUNCH_LANGEVIN(VEC, REPL) \
+  hipLaunchKernelGGL((langevin_update_kernel<VEC, REPL>), grid, dim3(256), 0, s, a, g, x_out2, sums, batch_total, snr, alpha, alpha_table, rp)
+  if (r) { if (vec) T2P_LAUNCH_LANGEVIN(true, true); else T2P_LAUNCH_LANGEVIN(false, true); }
+  else { if (vec) T2P_LAUNCH_LANGEVIN(true, false); else T2P_LAUNCH_LANGEVIN(false, false); }
+#undef T2P_LAUNCH_LANGEVIN
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }
 
-template <bool VEC>
+template <bool VEC, bool REPL>
 __global__ __launch_bounds__(256) void predictor_update_kernel(SdeUpdateArgs a, GuidedScore g, float* x_out2, const float* G_table,
                                                                float G_value, int probability_flow, const float* x_coef_table,
-                                                               float x_coef_value) {
+                                                               float x_coef_value, InpaintReplace rp) {
   // the host refuses steps >= N (Sampler::step); the clamp is a second guard against reading past the table
   const int si = G_table ? min(max(*g.step_counter, 0), g.n_table - 1) : 0;
   const float G = G_table ? G_table[si] : G_value;
@@ -1523,23 +1539,29 @@ __global__ __launch_bounds__(256) void predictor_update_kernel(SdeUpdateArgs a, 
   // VP (sde_lib.py:148-157): f = (sqrt(alpha) - 1) x, so x - f = (2 - sqrt(alpha)) x: the coefficient comes from a per-step table
   const float xc = x_coef_table ? x_coef_table[si] : x_coef_value;
   // rev_f = f - G^2 * score ; x_mean = x - rev_f ; x = x_mean + G z   (sde_lib.py:96-101, sampling.py:162-167)
-  update_loop<VEC, false>(a, g, x_out2, QuadDraw(), [=](float x, float s, float z, float* xm) {
+  update_loop<VEC, false, REPL>(a, g, x_out2, QuadDraw(), [=](float x, float s, float z, float* xm) {
     *xm = sum_of_products(xc, x, g2, s);
     return __builtin_fmaf(gz, z, *xm);
-  });
+  }, rp);
 }
 
 int launch_predictor_update(const SdeUpdateArgs& a, const GuidedScore& g, float* x_out2, const float* G_table, float G_value,
-                            int probability_flow, hipStream_t s, const float* x_coef_table, float x_coef_value) {
+                            int probability_flow, hipStream_t s, const float* x_coef_table, float x_coef_value, const InpaintReplace* r) {
   T2P_REQUIRE(!x_coef_table || G_table, "the x coefficient table goes with the G table");
   T2P_REQUIRE(a.x && g.o_c && a.noise && a.x_out && a.n > 0, "predictor_update arguments");
   T2P_REQUIRE((a.mask == nullptr) == (a.x_initial == nullptr), "mask and x_initial go together");
   T2P_REQUIRE((!g.scale_table && !G_table) || (g.step_counter && g.n_table > 0), "a per-step table needs the step counter and its length");
   const dim3 grid(ew_grid((a.n + 3) / 4));
-  if (quad_vec_ok(a.n, {a.x, g.o_c, g.o_u, a.noise, a.x_initial, a.x_out, x_out2, a.x_mean_out}, a.mask))
-    hipLaunchKernelGGL(predictor_update_kernel<true>, grid, dim3(256), 0, s, a, g, x_out2, G_table, G_value, probability_flow, x_coef_table, x_coef_value);
-  else
-    hipLaunchKernelGGL(predictor_update_kernel<false>, grid, dim3(256), 0, s, a, g, x_out2, G_table, G_value, probability_flow, x_coef_table, x_coef_value);
+  bool rvec = true;
+  T2P_TRY(inpaint_replace_ok(r, &rvec));
+  const bool vec = rvec && quad_vec_ok(a.n, {a.x, g.o_c, g.o_u, a.noise, a.x_initial, a.x_out, x_out2, a.x_mean_out}, a.mask);
+  const InpaintReplace rp = r ? *r : InpaintReplace();
+#define T2P_LAUNCH_PREDICTOR(VEC, REPL) \
+  hipLaunchKernelGGL((predictor_update_kernel<VEC, REPL>), grid, dim3(256), 0, s, a, g, x_out2, G_table, G_value, probability_flow, \
+                     x_coef_table, x_coef_value, rp)
+  if (r) { if (vec) T2P_LAUNCH_PREDICTOR(true, true); else T2P_LAUNCH_PREDICTOR(false, true); }
+  else { if (vec) T2P_LAUNCH_PREDICTOR(true, false); else T2P_LAUNCH_PREDICTOR(false, false); }
+#undef T2P_LAUNCH_PREDICTOR
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }
@@ -1651,6 +1673,18 @@ __global__ __launch_bounds__(256) void apply_mask_kernel(float* x, const unsigne
 int launch_apply_mask(float* x, const unsigned char* mask, const float* x_initial, long n, hipStream_t s) {
   T2P_REQUIRE(x && mask && x_initial && n > 0, "apply_mask arguments");
   hipLaunchKernelGGL(apply_mask_kernel, dim3(ew_grid(n)), dim3(256), 0, s, x, mask, x_initial, n);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+
+// x = where(known, data, x)   (inpainting.py:66)
+__global__ __launch_bounds__(256) void put_known_kernel(float* x, const unsigned char* known, const float* data, long n) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    if (known[i]) x[i] = data[i];
+}
+int launch_put_known(float* x, const unsigned char* known, const float* data, long n, hipStream_t s) {
+  T2P_REQUIRE(x && known && data && n > 0, "put_known arguments");
+  hipLaunchKernelGGL(put_known_kernel, dim3(ew_grid(n)), dim3(256), 0, s, x, known, data, n);
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }

@@ -11,7 +11,10 @@
 //   PC sampler (sampler.cpp)  prior         sampler seed   sampling  0                            0           quad q    normals (VE: x sigma_max)
 //                             predictor     sampler seed   sampling  1                            loop step   quad q    normals
 //                             corrector k   sampler seed   sampling  2 k + 2                      loop step   quad q    normals
-//   DDIM (ddim.hip)           prior         sampler seed   sampling  0                            0           quad q    normals
+//                             replace, after the corrector   sampler seed   sampling  0x80000000   loop step   quad q    normals, in the Langevin update kernel
+//                             replace, after the predictor   sampler seed   sampling  0x80000001   loop step   quad q    normals, in the predictor update kernel
+//                             (replacement inpainting, update_loop.h; disjoint from 0, 1 and 2 k + 2 for every k < 2^30 - 1)
+//   DDIM (ddim.hip)           prior        sampler seed   sampling  0                            0           quad q    normals
 //                             step i        sampler seed   sampling  i + 1                        0           quad q    normals, in the update kernel
 //   t2p_op_philox_normal                    caller's seed  sampling  caller's                     0           quad q    normals
 //   Trainer (train.h)         times t       trainer seed   training  rng_t()  = calls             -           sample b  word 0: t = eps + (1 - eps) u

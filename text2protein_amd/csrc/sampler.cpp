@@ -113,6 +113,34 @@ int Sampler::set_vp_tables(const float* label_f, const float* score_scale, const
   return T2P_OK;
 }
 
+int Sampler::set_inpaint(const uint8_t* known, const float* data, const float* mean_coef_host, const float* std_host) {
+  const bool ptrs = known && data, tabs = mean_coef_host && std_host;
+  T2P_REQUIRE((known != nullptr) == (data != nullptr), "set_inpaint: known and data go together");
+  T2P_REQUIRE((mean_coef_host != nullptr) == (std_host != nullptr), "set_inpaint: the mean_coef and std tables go together");
+  T2P_REQUIRE(ptrs == tabs, "set_inpaint: the pointers and the tables go together (all null clears the replacement)");
+  if (ptrs) {
+    const size_t bytes = (size_t)cfg_.N * 4;
+    if (!rp_mean_) {
+      float* m = (float*)e_->pool().persistent(bytes);
+      float* sd = (float*)e_->pool().persistent(bytes);
+      if (!m || !sd) return T2P_ERR_HIP;
+      rp_mean_ = m; rp_std_ = sd;
+    }
+    T2P_HIP_CHECK(hipMemcpy(rp_mean_, mean_coef_host, bytes, hipMemcpyHostToDevice));
+    T2P_HIP_CHECK(hipMemcpy(rp_std_, std_host, bytes, hipMemcpyHostToDevice));
+  }
+  known_ = known; data_ = data;
+  if (!ptrs) rp_noise_c_ = rp_noise_p_ = nullptr;
+  return T2P_OK;
+}
+
+int Sampler::set_inpaint_noise(const float* after_corrector, const float* after_predictor) {
+  T2P_REQUIRE(cfg_.n_steps_each == 1 || !after_corrector, "injected corrector-side noise supports n_steps_each == 1");
+  T2P_REQUIRE(known_ || (!after_corrector && !after_predictor), "set_inpaint_noise: call t2p_sampler_set_inpaint first");
+  rp_noise_c_ = after_corrector; rp_noise_p_ = after_predictor;
+  return T2P_OK;
+}
+
 int Sampler::set_norm_allreduce(float* sums, t2p_allreduce_fn fn, void* user) {
   T2P_REQUIRE((sums == nullptr) == (fn == nullptr), "the sums buffer and the all-reduce callback go together");
   sums_ext_ = sums; allreduce_ = fn; allreduce_user_ = user;
@@ -156,6 +184,14 @@ int Sampler::step(float* x, float* x_mean, const float* nc, const float* np, hip
   };
   SdeUpdateArgs a;
   a.x = x; a.mask = mask_; a.x_initial = mask_ ? x_init_ : nullptr; a.x_out = x; a.n = n_;     // x_initial alone was always ignored
+  // replacement inpainting: the known region is re-noised after the corrector (its last inner step) and after the predictor, inside
+  // the update kernels; streams of the two draws: philox.h
+  InpaintReplace rc;
+  rc.known = known_; rc.data = data_; rc.mean_table = rp_mean_; rc.std_table = rp_std_; rc.step_counter = step_dev_; rc.n_table = cfg_.N;
+  rc.seed = cfg_.seed;
+  InpaintReplace rp = rc;
+  rc.noise = rp_noise_c_; rc.stream = 0x80000000ull;
+  rp.noise = rp_noise_p_; rp.stream = 0x80000001ull;
   for (int k = 0; k < cfg_.n_steps_each; ++k) {
     T2P_TRY(score_fn());
     a.noise = nc;
@@ -169,7 +205,7 @@ int Sampler::step(float* x, float* x_mean, const float* nc, const float* np, hip
       if (rc != 0) { set_last_error("the norm all-reduce callback failed with status " + std::to_string(rc)); return T2P_ERR_STATE; }
     }
     T2P_TRY(launch_langevin_update(a, g, x2, sums, (float)(allreduce_ ? cfg_.global_batch : B), (float)cfg_.snr, 1.f, s,
-                                   vp ? vp_alpha_ : nullptr));
+                                   vp ? vp_alpha_ : nullptr, known_ && k == cfg_.n_steps_each - 1 ? &rc : nullptr));
   }
   T2P_TRY(score_fn());
   a.noise = np;
@@ -178,7 +214,7 @@ int Sampler::step(float* x, float* x_mean, const float* nc, const float* np, hip
     a.noise = noise_;
   }
   a.x_mean_out = x_mean ? x_mean : xmean_;
-  T2P_TRY(launch_predictor_update(a, g, x2, g_table_, 0.f, cfg_.probability_flow, s, vp ? vp_x_coef_ : nullptr));
+  T2P_TRY(launch_predictor_update(a, g, x2, g_table_, 0.f, cfg_.probability_flow, s, vp ? vp_x_coef_ : nullptr, 1.f, known_ ? &rp : nullptr));
   T2P_TRY(launch_add_int(step_dev_, 1, s));
   ++host_step_;
   return T2P_OK;
@@ -192,11 +228,13 @@ int Sampler::step_graph(float* x, float* x_mean, hipStream_t s) {
   T2P_REQUIRE(x && x_mean, "step_graph needs explicit x and x_mean buffers");
   T2P_REQUIRE(!allreduce_, "the captured step does not run the norm all-reduce hook: use t2p_sampler_step");
   T2P_REQUIRE(host_step_ >= 0 && host_step_ < cfg_.N, "PC step index beyond sde.N: call t2p_sampler_reset before another run");
+  T2P_REQUIRE(!rp_noise_c_ && !rp_noise_p_, "the captured step draws on the device: clear t2p_sampler_set_inpaint_noise");
   // one eager step first: fills the activation pool (no hipMalloc under capture); step() counts it.  Guided: also the first step
   // after a reset, which writes the second block of x once (the captured step does not)
   if (eager_steps_ < 1 || (guided() && mirrored_ != x))
     return step(x, x_mean, nullptr, nullptr, s);
-  if (graph_exec_ && (graph_x_ != x || graph_xm_ != x_mean || graph_mask_ != mask_ || graph_seed_ != cfg_.seed)) {
+  if (graph_exec_ && (graph_x_ != x || graph_xm_ != x_mean || graph_mask_ != mask_ || graph_seed_ != cfg_.seed || graph_known_ != known_ ||
+                      graph_data_ != data_)) {
     (void)hipGraphExecDestroy(graph_exec_);
     graph_exec_ = nullptr;
   }
@@ -214,7 +252,7 @@ int Sampler::step_graph(float* x, float* x_mean, hipStream_t s) {
     T2P_HIP_CHECK(ec);
     T2P_HIP_CHECK(hipGraphInstantiate(&graph_exec_, graph, nullptr, nullptr, 0));
     (void)hipGraphDestroy(graph);
-    graph_x_ = x; graph_xm_ = x_mean; graph_mask_ = mask_; graph_seed_ = cfg_.seed;
+    graph_x_ = x; graph_xm_ = x_mean; graph_mask_ = mask_; graph_seed_ = cfg_.seed; graph_known_ = known_; graph_data_ = data_;
   }
   T2P_HIP_CHECK(hipGraphLaunch(graph_exec_, s));
   ++host_step_;
@@ -257,6 +295,7 @@ int Sampler::run(float* x, float* out, int prior_given, int n_steps, hipStream_t
     // VESDE.prior_sampling (sde_lib.py:229-230) then where(mask, x, x_initial)
     T2P_TRY(launch_philox_normal(x, n_, cfg_.seed, 0, nullptr, s));
     if (cfg_.sde == T2P_SDE_VE) T2P_TRY(launch_scale(x, n_, (float)cfg_.sigma_max, s));     // VP prior: N(0, 1) (sde_lib.py:133-134)
+    if (known_) T2P_TRY(launch_put_known(x, known_, data_, n_, s));     // x = known ? d : prior (inpainting.py:66), then the condition
     if (mask_) T2P_TRY(launch_apply_mask(x, mask_, x_init_, n_, s));
   }
   for (int i = 0; i < n_steps; ++i) T2P_TRY(step(x, xmean_, nullptr, nullptr, s));

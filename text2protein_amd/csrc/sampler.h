@@ -21,6 +21,11 @@ class Sampler {
   // from ONE evaluation of [x ; x] under [ctx ; 0] at batch 2B.  x then has room for 2B samples (see t2p_sampler_step).
   int set_guidance(double w, int enabled);
   int set_context(const float* ctx, int B, int T, hipStream_t s);
+  // replacement inpainting (score_sde_pytorch/inpainting.py): after every corrector and predictor update the known region becomes
+  // mean_coef[i] data + std[i] z at loop step i; host tables of N floats.  All null clears it.  The pointers are borrowed.
+  int set_inpaint(const uint8_t* known, const float* data, const float* mean_coef_host, const float* std_host);
+  // the z of the two replacements of the next steps (fixture replay); null = drawn on the device (philox.h)
+  int set_inpaint_noise(const float* after_corrector, const float* after_predictor);
   bool guided() const { return guidance_ && w_ != 1.0; }     // w == 1: 1 a + 0 b == a, the plain path at batch B
   int reset(int step, hipStream_t s);
   int step(float* x, float* x_mean, const float* nc, const float* np, hipStream_t s);
@@ -58,6 +63,14 @@ class Sampler {
   float* graph_x_ = nullptr;
   float* graph_xm_ = nullptr;
   const uint8_t* graph_mask_ = nullptr;
+  const uint8_t* graph_known_ = nullptr;
+  const float* graph_data_ = nullptr;
+  const uint8_t* known_ = nullptr;    // replacement inpainting: 1 = known, with data_
+  const float* data_ = nullptr;
+  float* rp_mean_ = nullptr;          // device float[N] each: a_i and s_i of marginal_prob at loop step i
+  float* rp_std_ = nullptr;
+  const float* rp_noise_c_ = nullptr; // injected z of the replacement after the corrector / the predictor
+  const float* rp_noise_p_ = nullptr;
   int eager_steps_ = 0;
   bool guidance_ = false;
   double w_ = 1.0;

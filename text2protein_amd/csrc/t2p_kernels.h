@@ -122,6 +122,21 @@ struct SdeUpdateArgs {
   float* x_mean_out = nullptr;     // un-masked x_mean (masking of the final x_mean: sampling.py:287)
   long n = 0;                      // total elements
 };
+// Replacement inpainting (reference score_sde_pytorch/inpainting.py:39-47): after an update U the known region is overwritten with the
+// data noised to the step's level, r = fl(fl(a d) + fl(z s)), and x_mean becomes known ? fl(a d) : the new x.  An element the
+// condition mask freezes stays x_initial (in x and in x_mean).  Rides in the update kernels: no launch of its own.
+struct InpaintReplace {
+  const unsigned char* known = nullptr;   // 1 = known (B, C, L, L); null together with data
+  const float* data = nullptr;            // the clean data d, fp32
+  const float* noise = nullptr;           // z; null = drawn in the kernel: sampling layout, (seed, stream), counter = quad q
+  const float* mean_table = nullptr;      // a of loop step i, read at *step_counter ...
+  const float* std_table = nullptr;       // ... and s; both null: mean_coef / std below
+  const int* step_counter = nullptr;      // device step index: the tables' row and the step word of the draw; null: `step`
+  int n_table = 0;
+  float mean_coef = 1.f, std = 0.f;
+  unsigned long long seed = 0, stream = 0;
+  unsigned int step = 0;
+};
 // sums[0] = sum_b ||s_b||_2, sums[1] = sum_b ||noise_b||_2  (per-sample norms over B samples, summed over b).  width: consecutive
 // elements a thread sums per trip, 1 (the plain loop and t2p_op_langevin*) or 4 (the guided loop): the order of the float32 sums
 int launch_langevin_norms(const GuidedScore& g, const float* noise, int B, long per_sample, float* sq_ws, float* sums, int width,
@@ -130,13 +145,15 @@ int launch_langevin_norms(const GuidedScore& g, const float* noise, int B, long 
 // = sums[] / batch_total (batch_total may exceed the local batch: global-batch semantics)
 // alpha_table (optional): alpha = alpha_table[*step_counter] (VP: sde.alphas[timestep], sampling.py:184-186)
 // x_out2 (optional): a second copy of the new state, the other half of the [x ; x] input of the next guided evaluation
+// r (optional, here and in the predictor): the replacement of the known region after the update
 int launch_langevin_update(const SdeUpdateArgs& a, const GuidedScore& g, float* x_out2, const float* sums, float batch_total,
-                           float snr, float alpha, hipStream_t s, const float* alpha_table = nullptr);
+                           float snr, float alpha, hipStream_t s, const float* alpha_table = nullptr, const InpaintReplace* r = nullptr);
 // predictor: x_mean = x_coef x + G^2 * s * (0.5 if probability_flow); x = x_mean + (0 if pf else G) z
 // G = G_table[*step_counter] when G_table != null, else G_value
 // x_coef_table (optional, with G_table): VP, 2 - sqrt(alpha) (sde_lib.py:148-157); x_coef_value: the coefficient where no table is given
 int launch_predictor_update(const SdeUpdateArgs& a, const GuidedScore& g, float* x_out2, const float* G_table, float G_value,
-                            int probability_flow, hipStream_t s, const float* x_coef_table = nullptr, float x_coef_value = 1.f);
+                            int probability_flow, hipStream_t s, const float* x_coef_table = nullptr, float x_coef_value = 1.f,
+                            const InpaintReplace* r = nullptr);
 // noise[i] = N(0,1) from Philox4x32-10 keyed by (seed, stream); counter = element index / 4
 int launch_philox_normal(float* out, long n, unsigned long long seed, unsigned long long stream,
                          const int* step_counter, hipStream_t s);
@@ -252,6 +269,8 @@ int launch_widen(const void* in, int dtype, float* out, long n, hipStream_t s); 
 int launch_gather_label(const int* labels, const int* step_counter, const float* table, float* out, int B, int N,
                         hipStream_t s, const int* label_table = nullptr);
 int launch_apply_mask(float* x, const unsigned char* mask, const float* x_initial, long n, hipStream_t s);
+// x = where(known, data, x): the start of a replacement-inpainting run (inpainting.py:66)
+int launch_put_known(float* x, const unsigned char* known, const float* data, long n, hipStream_t s);
 int launch_decode6d(const float* x, int B, int C, int L, float* clipped, float* absval, int* lengths, hipStream_t s);
 // 6D encode of a padded batch of backbones (dataset.py:396-450, :200-239, :114-168): xyz [B][L][3][3] fp32 (N, Ca, C), nres [B],
 // atom_ok [B][L][3] or null -> coords_6d [B][C][L][L] (C = 5 or 8), mask_pair [B][L][L]; blocks [n][4] / pairs [npairs][2]: device

@@ -26,6 +26,13 @@ __device__ inline float sum_of_products(float a, float b, float c, float d) {
   const float ab = a * b, cd = c * d;
   return ab + cd;
 }
+// r = fl(fl(a d) + fl(z s)) of the replacement (inpainting.py:43-44); *mean = fl(a d)
+__device__ inline float noised_data(float a, float d, float z, float s, float* mean) {
+#pragma clang fp contract(off)
+  const float ad = a * d, zs = z * s;
+  *mean = ad;
+  return ad + zs;
+}
 __device__ inline float guided_scale(const GuidedScore& g) {
   return g.scale_table ? g.scale_table[min(max(*g.step_counter, 0), g.n_table - 1)] : g.scale;
 }
@@ -47,15 +54,29 @@ struct QuadDraw {
 // loads, s per element, UPDATE(x, s, z, &second) -> x_next, the mask, the stores: x_next to a.x_out and x_out2 (optional: the other
 // half of the [x ; x] input of a guided evaluation), `second` (x_mean / the clean-sample prediction, never masked) to a.x_mean_out.
 // VEC: quad_vec_ok holds and a quad moves as one 16-byte access per tensor; otherwise element by element, bounded by a.n.
-template <bool VEC, bool DRAW, typename Update>
-__device__ inline void update_loop(const SdeUpdateArgs& a, const GuidedScore& g, float* x_out2, const QuadDraw& d, Update update) {
+// REPL: the replacement branch (InpaintReplace, r.known set): per element, frozen by the mask -> x_initial; else known -> the noised
+// data; else the update.  `second` becomes fl(a d) where replaced and x_next elsewhere (inpainting.py:46).  The second normal is
+// drawn here (nobody else reads it) unless r.noise gives it; a quad without a known element draws nothing.
+template <bool VEC, bool DRAW, bool REPL = false, typename Update>
+__device__ inline void update_loop(const SdeUpdateArgs& a, const GuidedScore& g, float* x_out2, const QuadDraw& d, Update update,
+                                   const InpaintReplace& r = InpaintReplace()) {
   const float scale = guided_scale(g);
+  float ra = 1.f, rs = 0.f;
+  uint32_t rstep = 0u;
+  if (REPL) {
+    const int st = r.step_counter ? *r.step_counter : (int)r.step;
+    rstep = (uint32_t)st;
+    ra = r.mean_table ? r.mean_table[min(max(st, 0), r.n_table - 1)] : r.mean_coef;
+    rs = r.std_table ? r.std_table[min(max(st, 0), r.n_table - 1)] : r.std;
+  }
   const long nq = (a.n + 3) / 4;
   for (long q = (long)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (long)gridDim.x * blockDim.x) {
     const long i = q * 4;
     const int cnt = VEC ? 4 : (int)(a.n - i < 4 ? a.n - i : 4);
     alignas(16) float x[4], c[4], u[4] = {0.f, 0.f, 0.f, 0.f}, z[4] = {0.f, 0.f, 0.f, 0.f}, xi[4] = {0.f, 0.f, 0.f, 0.f};
     alignas(4) unsigned char m[4] = {1, 1, 1, 1};
+    alignas(16) float dd[4] = {0.f, 0.f, 0.f, 0.f}, rz[4] = {0.f, 0.f, 0.f, 0.f};
+    alignas(4) unsigned char kn[4] = {0, 0, 0, 0};
     if (VEC) {
       *(float4*)x = *(const float4*)(a.x + i);
       *(float4*)c = *(const float4*)(g.o_c + i);
@@ -65,6 +86,11 @@ __device__ inline void update_loop(const SdeUpdateArgs& a, const GuidedScore& g,
         *(uchar4*)m = *(const uchar4*)(a.mask + i);
         *(float4*)xi = *(const float4*)(a.x_initial + i);
       }
+      if (REPL) {
+        *(uchar4*)kn = *(const uchar4*)(r.known + i);
+        *(float4*)dd = *(const float4*)(r.data + i);
+        if (r.noise) *(float4*)rz = *(const float4*)(r.noise + i);
+      }
     } else {
       for (int k = 0; k < 4; ++k) x[k] = c[k] = 0.f;
       for (int k = 0; k < cnt; ++k) {
@@ -73,6 +99,11 @@ __device__ inline void update_loop(const SdeUpdateArgs& a, const GuidedScore& g,
         if (g.o_u) u[k] = g.o_u[i + k];
         if (a.noise) z[k] = a.noise[i + k];
         if (a.mask) { m[k] = a.mask[i + k]; xi[k] = a.x_initial[i + k]; }
+        if (REPL) {
+          kn[k] = r.known[i + k];
+          dd[k] = r.data[i + k];
+          if (r.noise) rz[k] = r.noise[i + k];
+        }
       }
     }
     if (DRAW && d.on) {
@@ -86,6 +117,22 @@ __device__ inline void update_loop(const SdeUpdateArgs& a, const GuidedScore& g,
     for (int k = 0; k < 4; ++k) {
       xn[k] = update(x[k], guided_score(c[k], u[k], g.o_u != nullptr, g.w, g.w1, scale), z[k], &xm[k]);
       if (!m[k]) xn[k] = xi[k];
+    }
+    if (REPL) {
+      if (!r.noise && (kn[0] | kn[1] | kn[2] | kn[3])) {
+        uint32_t ctr[4];
+        philox_counter_sampling(ctr, q, r.stream, rstep);
+        philox4x32_10(ctr, r.seed);
+        philox_normal4(ctr, rz);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        float ad;
+        const float rr = noised_data(ra, dd[k], rz[k], rs, &ad);
+        const bool rep = kn[k] && m[k];
+        xn[k] = rep ? rr : xn[k];
+        xm[k] = rep ? ad : xn[k];
+      }
     }
     if (VEC) {
       *(float4*)(a.x_out + i) = *(const float4*)xn;

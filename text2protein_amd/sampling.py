@@ -393,8 +393,32 @@ class PCStepper:
         self._keep = (mask_u8, x_initial)          # the C side borrows these pointers
         check(self.lib.t2p_sampler_set_condition(self._h, ptr(mask_u8), ptr(x_initial)))
 
+    def set_inpaint(self, known_u8=None, data=None, mean_coef=None, std=None):
+        """Replacement inpainting for the following steps (t2p_sampler_set_inpaint): ``known_u8`` (1 = known) and ``data`` on the
+        device, ``mean_coef`` / ``std`` float32 CPU tables of N entries (``sde.inpaint_tables(eps)``).  All ``None`` clears it."""
+        for t in (mean_coef, std):
+            if t is not None and (t.device.type != "cpu" or t.dtype != torch.float32 or t.numel() != self.N or not t.is_contiguous()):
+                raise T2PError(f"the replacement tables are contiguous float32 CPU tensors of {self.N} entries")
+        check(self.lib.t2p_sampler_set_inpaint(self._h, ptr(known_u8), ptr(data), ptr(mean_coef), ptr(std)))
+        self._keep_inpaint = (known_u8, data)      # the C side borrows these pointers (the tables are copied)
+        if known_u8 is None:
+            self._keep_inpaint_noise = ()          # clearing the replacement drops injected noise on the C side too
+
+    def set_inpaint_noise(self, after_corrector=None, after_predictor=None):
+        """The z of the two replacements of the following steps (fixture replay); ``None`` = drawn on the device."""
+        check(self.lib.t2p_sampler_set_inpaint_noise(self._h, ptr(after_corrector), ptr(after_predictor)))
+        self._keep_inpaint_noise = (after_corrector, after_predictor)
+
     def reset(self, step=0):
         check(self.lib.t2p_sampler_reset(self._h, int(step), stream_ptr()))
+
+    def run(self, x, out, prior_given=False, n_steps=0):
+        """The whole loop in one C call (t2p_sampler_run): ``x`` holds the conditioned prior when ``prior_given``, else it is drawn
+        on the device; ``out`` receives x_mean (denoise) or x."""
+        try:
+            check(self.lib.t2p_sampler_run(self._h, ptr(x), ptr(out), int(bool(prior_given)), int(n_steps), stream_ptr()))
+        except T2PError as e:
+            raise_allreduce_error(getattr(self, "_cb_error", None), e)
 
     def step(self, x, x_mean, noise_corrector=None, noise_predictor=None):
         try:

@@ -79,6 +79,12 @@ class VESDE(SDE):
         ts = torch.linspace(self.T, eps, self.N)
         return self.discretize_coeffs(ts)[1].float().contiguous()
 
+    def inpaint_tables(self, eps):
+        """(mean_coef, std), float32[N] each: ``marginal_prob(d, t_i) = (mean_coef[i] d, std[i])`` at loop step i of
+        ``linspace(T, eps, N)``, what replacement inpainting noises the known region with (inpainting.py:43).  VE: the mean is d."""
+        ts = torch.linspace(self.T, eps, self.N)
+        return torch.ones(self.N), self.marginal_prob_std(ts).float().contiguous()
+
     def label_table(self, eps):
         """Time label the score network receives at loop step i: ``round((T - t_i) (N - 1))`` in the
         reference's float32 arithmetic (models/utils.py:159-171 on ``linspace(T, eps, N)``).  It equals
@@ -139,6 +145,12 @@ class VPSDE(SDE):
         """Integer part of the time label of loop step i (index of the std / sigma tables, models/utils.py:150-153)."""
         ts, _ = self._steps(eps)
         return (ts * (self.N - 1)).long().to(torch.int32).contiguous()
+
+    def inpaint_tables(self, eps):
+        """(mean_coef, std), float32[N] each, of ``marginal_prob`` at loop step i (sde_lib.py:134-138), in its float32 arithmetic."""
+        ts, _ = self._steps(eps)
+        log_mean_coeff = -0.25 * ts ** 2 * (self.beta_1 - self.beta_0) - 0.5 * ts * self.beta_0
+        return torch.exp(log_mean_coeff).float().contiguous(), torch.sqrt(1. - torch.exp(2. * log_mean_coeff)).float().contiguous()
 
     def vp_tables(self, eps):
         """(label_f, score_scale, x_coef, corr_alpha), float32[N] each: the fractional label ``t (N - 1)`` the network embeds,
