@@ -388,6 +388,21 @@ int t2p_op_tgemm(const float* A, int64_t sAm, int64_t sAk, const float* B, int64
 int t2p_op_tgemm16(int dtype, const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBk, int64_t sBn, float* C, int64_t ldc,
                    int M, int N, int K, int nz, int64_t sAz, int64_t sBz, int64_t sCz, float alpha, float beta, const float* bias_n, int ksplit,
                    int conv, int H, int W, int conv_C, void* stream);
+/* one 3x3 convolution of the training step (nn.Conv2d, padding 1, + the per-sample time-embedding bias of layers.py:316), forward and
+ * backward, through the code the trainer runs (train.h: train_conv3x3_forward / train_conv3x3_backward) in the trainer's order: the
+ * weight layouts (conv_w_prep) and, for dtype 1 = bf16 / 2 = f16, their 16-bit copies and those of x / dy as HipTrainModel(dtype=...)
+ * makes them for a residual-block convolution (dtype 0: the exact-f32 kernels, which the input and head convolutions keep in every
+ * mode); the forward product; the data gradient in place; the gathered weight gradient with the library's split-K; its fold into the
+ * reference layout; the column sums.  All pointers device fp32:
+ *   x [batch][H W][Cip] NHWC, pad columns zero;  w [Co][Ci][3][3];  bias [Co];  tbias [batch][Co] or NULL (needs Cop == Co)
+ *   y [batch][H W][Cop]: Co columns written, the pad columns zeroed
+ *   dy [batch][H W][Cop]; NULL = forward only.   dx [batch][H W][Cip], ACCUMULATED into (Ci columns; the pad columns untouched);
+ *   NULL = x needs no gradient.   dw [Co][Ci][3][3], dbias [Co], dtbias [batch][Co] (with tbias): ACCUMULATED into
+ * fixed_order: the reductions of the 16-bit step (column sums in a fixed order; plan switch 48's meaning), else atomics.
+ * Cip, Cop: multiples of 4 (of 8 for dtype 1 / 2), >= Ci, Co.  Scratch is allocated inside the call and freed before it returns. */
+int t2p_op_train_conv3x3(int dtype, const float* x, const float* w, const float* bias, const float* tbias, int batch, int H, int W, int Ci,
+                         int Co, int Cip, int Cop, float* y, const float* dy, float* dx, float* dw, float* dbias, float* dtbias,
+                         int fixed_order, void* stream);
 /* block_dropout alone (losses.py:54-64; the training pass applies it at :106-107 through the same two kernels): out = x (device fp32
  * (batch, C, L, L)) with channels 4:7 of the dropped blocks' rows and columns zeroed; out may alias x, otherwise x is untouched.
  * host_blocks / host_drop / p as t2p_train_set_ss_blocks; seed / stream_id: the Philox key and stream of the device draws (host_drop
@@ -670,6 +685,10 @@ int t2p_profile_attention(double* out3);
  * "kind,M,N,K,taps,batch,launches,ms,flops" (kind as in out9; K "a+b" = a channels per tap + b shortcut columns;
  * taps negative = gathered from the half-resolution map).  T2P_ERR_INVALID when the buffer is too small */
 int t2p_profile_shapes(char* buf, int len);
+/* after t2p_profile_end: the 3x3-convolution launches of that region on the LDS-DMA kernels by kernel instantiation and operand
+ * shape, as text lines "kernel;M;N;K;launches" (the name as t2p_profile_dominant gives it; K = channels per tap): which tile geometry
+ * every convolution of a pass ran, not only the dominant one.  T2P_ERR_INVALID when the buffer is too small */
+int t2p_profile_conv_kernels(char* buf, int len);
 /* per-block timing of the score network (UNetModel.forward, ncsnpp.py:220-263): HIP events on the launch stream at every block
  * boundary between _begin and _end; _end synchronises the device and writes CSV lines
  * "prefix,kind,map side,in channels,out channels,ms" in launch order (pre = embedding + input convolution, head = out.*) */

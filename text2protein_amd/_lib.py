@@ -154,6 +154,7 @@ SIGNATURES = {
     "t2p_profile_dominant": (_i, [C.POINTER(C.c_double), C.c_char_p, C.c_int]),
     "t2p_profile_attention": (_i, [C.POINTER(C.c_double)]),
     "t2p_profile_shapes": (_i, [C.c_char_p, C.c_int]),
+    "t2p_profile_conv_kernels": (_i, [C.c_char_p, C.c_int]),
     "t2p_debug_tap": (_i, [_i, _vp, C.c_int64, C.POINTER(C.c_int64)]),
     "t2p_profile_layers_begin": (_i, []),
     "t2p_profile_layers_end": (_i, [C.c_char_p, C.c_int]),
@@ -185,6 +186,7 @@ SIGNATURES = {
     "t2p_op_tgemm": (_i, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i, _i, _i, _i, _i64, _i64, _i64, _f, _f, _vp, _i, _i, _i, _i, _i, _vp]),
     "t2p_op_tgemm16": (_i, [_i, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i, _i, _i, _i, _i64, _i64, _i64, _f, _f, _vp, _i, _i, _i, _i, _i,
                             _vp]),
+    "t2p_op_train_conv3x3": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "t2p_op_ss_block_dropout": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, C.c_double, _u64, _u64, _vp, _vp]),
     "t2p_op_inpaint_mask_draw": (_i, [_vp, _i, _i, C.c_double, C.c_double, _u64, _u64, _i, _vp, _vp, C.POINTER(_i), _vp]),
     "t2p_op_groupnorm_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),

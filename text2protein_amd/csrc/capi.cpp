@@ -947,6 +947,13 @@ int t2p_profile_shapes(char* buf, int len) {
   API_END
 }
 
+int t2p_profile_conv_kernels(char* buf, int len) {
+  API_BEGIN
+  T2P_REQUIRE(buf && len > 0, "null argument");
+  return profile_conv_kernels(buf, len);
+  API_END
+}
+
 int t2p_debug_tap(int block_index, float* dst, int64_t capacity, int64_t* shape4) {
   API_BEGIN
   if (shape4) {

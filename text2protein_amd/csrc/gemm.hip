@@ -1854,6 +1854,16 @@ int profile_shapes(char* buf, int len) {
   std::memcpy(buf, t.c_str(), t.size() + 1);
   return T2P_OK;
 }
+// the 3x3-convolution launches of the last region on the LDS-DMA kernels, one line per (instantiation, operand shape):
+// kernel;M;N;K;launches  (the kernel name as profile_dominant prints it; it holds commas, hence the semicolons)
+static std::map<std::string, int> g_conv_kernels;
+int profile_conv_kernels(char* buf, int len) {
+  std::string t = "kernel;M;N;K;launches\n";
+  for (auto& kv : g_conv_kernels) t += kv.first + ";" + std::to_string(kv.second) + "\n";
+  if ((int)t.size() + 1 > len) { set_last_error("profile_conv_kernels: buffer too small"); return T2P_ERR_INVALID; }
+  std::memcpy(buf, t.c_str(), t.size() + 1);
+  return T2P_OK;
+}
 void profile_begin() {
   for (ProfRec& r : g_prof_attn) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
   g_prof_attn.clear();
@@ -1869,6 +1879,7 @@ int profile_end(double out[3][3]) {
   for (int k = 0; k < 3; ++k) out[k][0] = out[k][1] = out[k][2] = 0;
   std::map<std::string, std::array<double, 4>> per;
   g_shapes.clear();
+  g_conv_kernels.clear();
   for (ProfRec& r : g_prof) {
     T2P_HIP_CHECK(hipEventSynchronize(r.b));
     float ms = 0.f;
@@ -1884,6 +1895,7 @@ int profile_end(double out[3][3]) {
     if (r.kind == 0 && r.name) {
       auto& e = per[r.name];
       e[0] += ms; e[1] += r.flops; e[2] += 1; e[3] += r.bytes;
+      g_conv_kernels[std::string(r.name) + ";" + std::to_string(r.M) + ";" + std::to_string(r.N) + ";" + std::to_string(r.K)] += 1;
     }
     (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b);
   }

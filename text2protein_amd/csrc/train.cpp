@@ -37,7 +37,10 @@ bool g_train_plumbing16 = false;   // plan switch 48: a trainer created while it
 
 static int gn_groups_of(int c) { return std::min(c / 4, 32); }   // layers.py:282
 
-Trainer::Trainer(const t2p_model_config& mc, const t2p_train_config& tc) : mc_(mc), tc_(tc) {}
+Trainer::Trainer(const t2p_model_config& mc, const t2p_train_config& tc) : mc_(mc), tc_(tc) {
+  scratch_.get = [this](size_t bytes) { return pool_.get(bytes); };
+  scratch_.put = [this](void* p) { pool_.put(p); };
+}
 Trainer::~Trainer() {}
 
 long Trainer::poff(const std::string& name, std::vector<int64_t> shape) {
@@ -399,76 +402,94 @@ int Trainer::reduce_ws(long floats, float** ws) {
 }
 
 // out [nz][N] += the column sums of the nz blocks of `rows` rows of dy: nz = 1 a bias gradient, nz = B the per-sample time-embedding bias
-int Trainer::colsum(const float* dy, int nz, long rows, int N, long ld, float* out) {
+int train_colsum(const float* dy, int nz, long rows, int N, long ld, float* out, bool fixed_order, const ConvScratch& sc, hipStream_t s) {
   float* ws = nullptr;
-  T2P_TRY(reduce_ws(colsum_ws_floats(nz, rows, N), &ws));
-  return launch_colsum(dy, nz, rows, N, ld, out, N, 1, ws, s_);
+  if (fixed_order) {
+    ws = (float*)sc.get((size_t)colsum_ws_floats(nz, rows, N) * 4);
+    if (!ws) return T2P_ERR_HIP;
+  }
+  const int rc = launch_colsum(dy, nz, rows, N, ld, out, N, 1, ws, s);
+  if (ws) sc.put(ws);                // stream-ordered: the next user of the block runs after this reduction
+  return rc;
+}
+int Trainer::colsum(const float* dy, int nz, long rows, int N, long ld, float* out) {
+  return train_colsum(dy, nz, rows, N, ld, out, plumbing16_, scratch_, s_);
 }
 
-int Trainer::tg(const TGemmArgs& a) {
-  if (dt_ == DT_F32) return launch_tgemm(a, s_);
+int train_tgemm(int dt, const TGemmArgs& a, const ConvScratch& sc, hipStream_t s) {
+  if (dt == DT_F32) return launch_tgemm(a, s);
   const long n = tgemm16_ws_floats(a);
   float* ws = nullptr;
   if (n > 0) {
-    ws = (float*)pool_.get((size_t)n * 4);
+    ws = (float*)sc.get((size_t)n * 4);
     if (!ws) return T2P_ERR_HIP;
   }
-  const int rc = launch_tgemm16(a, dt_, ws, s_);
-  if (ws) pool_.put(ws);             // stream-ordered: the next user of the block runs after this product
+  const int rc = launch_tgemm16(a, dt, ws, s);
+  if (ws) sc.put(ws);                // stream-ordered: the next user of the block runs after this product
   return rc;
 }
+int Trainer::tg(const TGemmArgs& a) { return train_tgemm(dt_, a, scratch_, s_); }
 
 // ---- operators -----------------------------------------------------------------------------------------------------------------------------
-// y [B][H W][ldc] = conv3x3(x) + bias (+ bias_bn[b][:]) (+ residual_inplace, which may be y: the register-staged kernel reads and writes
-// an output element in the same thread), N columns written.  w16 == nullptr: the engine's exact-f32 implicit-GEMM kernel on w; else its
-// 16-bit kernels on w16 (the LDS-DMA implicit GEMM takes 16-bit A only: x is rounded once into a pass-local 16-bit copy)
-int Trainer::conv_gemm(const float* x, int B, int H, int W, int Cin, const float* w, const void* w16, long ldb, const float* bias,
-                       const float* bias_bn, int N, float* y, long ldc, const float* residual_inplace) {
+// y [B][H W][ldc] = conv3x3(x) + bias (+ bias_bn[b][:]) (+ residual_inplace, which may be y: every epilogue reads and writes an output
+// element in the same thread, once -- tests/test_gpu_train_conv.py holds each plan the step takes to that), N columns written.
+// w16 == nullptr: the engine's exact-f32 implicit-GEMM kernel on w; else its 16-bit kernels on w16 (the LDS-DMA implicit GEMM takes
+// 16-bit A only: x is rounded once into a pass-local 16-bit copy)
+int train_conv_gemm(int dt, const float* x, int B, int H, int W, int Cin, const float* w, const void* w16, long ldb, const float* bias,
+                    const float* bias_bn, int N, float* y, long ldc, const float* residual_inplace, const ConvScratch& sc, hipStream_t s) {
   GemmParams p;
   p.dtype = DT_F32; p.a_f32 = 1; p.A0 = x; p.C0 = Cin; p.lda0 = Cin; p.taps = 9; p.H = H; p.W = W;
   p.Bw = w; p.ldb = ldb; p.M = B * H * W; p.N = N; p.bias_n = bias; p.bias_bn = bias_bn; p.rows_per_batch = H * W; p.ld_bn = N;
   p.R = residual_inplace; p.ldr = ldc;
   p.C = y; p.c_f32 = 1; p.ldc = ldc;
-  if (!w16) return launch_gemm(p, s_);
+  if (!w16) return launch_gemm(p, s);
   const long n = (long)B * H * W * Cin;
-  void* x16 = pool_.get((size_t)n * 2);
+  void* x16 = sc.get((size_t)n * 2);
   if (!x16) return T2P_ERR_HIP;
-  p.dtype = dt_; p.a_f32 = 0; p.A0 = x16; p.Bw = w16;
-  int rc = launch_convert(x, x16, dt_, n, s_);
-  if (rc == T2P_OK) rc = launch_gemm(p, s_);
-  pool_.put(x16);                  // stream-ordered: the next user of the block runs after this convolution
+  p.dtype = dt; p.a_f32 = 0; p.A0 = x16; p.Bw = w16;
+  int rc = launch_convert(x, x16, dt, n, s);
+  if (rc == T2P_OK) rc = launch_gemm(p, s);
+  sc.put(x16);                     // stream-ordered: the next user of the block runs after this convolution
   return rc;
 }
 
 // y [B][H W][Cop] = conv3x3(x [B][H W][Cip]) + bias (+ tbias[b][:]: Dense_0(act(temb)) of the block, layers.py:316); Co of the Cop
 // columns are written (the head convolution: Cop = 8 > Co, the rest zero).  c.wf16 (the residual-block convolutions in 16-bit
 // modes) selects the 16-bit implicit GEMM for the forward and the data gradient; the input and head convolutions keep the exact-f32 kernel
+int train_conv3x3_forward(int dt, const ConvW& c, const float* x, int B, int H, int W, const float* bias, const float* tbias, float* y,
+                          const ConvScratch& sc, hipStream_t s) {
+  if (c.Cop != c.Co) T2P_HIP_CHECK(hipMemsetAsync(y, 0, (size_t)B * H * W * c.Cop * 4, s));
+  return train_conv_gemm(dt, x, B, H, W, c.Cip, c.wf, c.wf16, 9L * c.Cip, bias, tbias, c.Co, y, c.Cop, nullptr, sc, s);
+}
+
+int train_conv3x3_backward(int dt, bool fixed_order, const ConvW& c, const float* x, const float* dy, int B, int H, int W, float* dx,
+                           float* dwc, float* dw, float* dbias, float* dtbias, const ConvScratch& sc, hipStream_t s) {
+  const long rows = (long)B * H * W;
+  if (dx)                                          // dX = conv3x3(dY, flipped transposed taps), accumulated in place through the residual operand
+    T2P_TRY(train_conv_gemm(dt, dy, B, H, W, c.Cop, c.wd, c.wd16, 9L * c.Cop, nullptr, nullptr, c.Ci, dx, c.Cip, dx, sc, s));
+  T2P_HIP_CHECK(hipMemsetAsync(dwc, 0, (size_t)c.Co * 9 * c.Cip * 4, s));
+  TGemmArgs w;                                     // dW[co][tap][ci] = sum_pixels dY[pixel][co] X[pixel + tap][ci]
+  w.A = dy; w.sAm = 1; w.sAk = c.Cop; w.B = x; w.conv_b = 1; w.H = H; w.W = W; w.conv_C = c.Cip; w.ldx = c.Cip;
+  w.C = dwc; w.ldc = 9L * c.Cip; w.M = c.Co; w.N = 9 * c.Cip; w.K = (int)rows; w.beta = 1.f; w.ksplit = 0;
+  T2P_TRY(train_tgemm(dt, w, sc, s));
+  T2P_TRY(launch_conv_w_grad_fold(dwc, dw, c.Co, c.Ci, c.Cip, s));
+  T2P_TRY(train_colsum(dy, 1, rows, c.Co, c.Cop, dbias, fixed_order, sc, s));
+  if (dtbias) T2P_TRY(train_colsum(dy, B, (long)H * W, c.Co, c.Cop, dtbias, fixed_order, sc, s));
+  return T2P_OK;
+}
+
 int Trainer::conv3x3(TT* x, const Conv& c, TT* tbias, TT** out) {
   T2P_REQUIRE(x->C == c.Cip && (!tbias || (tbias->C == c.Co && c.Cop == c.Co)), "conv3x3 channels");
   T2P_ACT(y, x->B, x->H, x->W, c.Cop);
-  if (c.Cop != c.Co) T2P_HIP_CHECK(hipMemsetAsync(y->p, 0, (size_t)y->numel() * 4, s_));
-  T2P_TRY(conv_gemm(x->p, x->B, x->H, x->W, c.Cip, c.wf, c.wf16, 9L * c.Cip, Pc_ + c.b, tbias ? tbias->p : nullptr, c.Co, y->p, c.Cop, nullptr));
+  T2P_TRY(train_conv3x3_forward(dt_, conv_w(c), x->p, x->B, x->H, x->W, Pc_ + c.b, tbias ? tbias->p : nullptr, y->p, scratch_, s_));
   *out = y;
   const Conv C = c;
   tape_.push_back([this, x, y, C, tbias]() -> int {
     if (!y->g) return T2P_OK;
-    const long rows = x->rows();
-    if (x->needs_grad) {                           // dX = conv3x3(dY, flipped transposed taps), accumulated in place through the residual operand
-      T2P_GRAD(gx, x);
-      T2P_TRY(conv_gemm(y->g, x->B, x->H, x->W, C.Cop, C.wd, C.wd16, 9L * C.Cop, nullptr, nullptr, C.Ci, gx, C.Cip, gx));
-    }
-    T2P_HIP_CHECK(hipMemsetAsync(dwc_, 0, (size_t)C.Co * 9 * C.Cip * 4, s_));
-    TGemmArgs w;                                   // dW[co][tap][ci] = sum_pixels dY[pixel][co] X[pixel + tap][ci]
-    w.A = y->g; w.sAm = 1; w.sAk = C.Cop; w.B = x->p; w.conv_b = 1; w.H = x->H; w.W = x->W; w.conv_C = C.Cip; w.ldx = C.Cip;
-    w.C = dwc_; w.ldc = 9L * C.Cip; w.M = C.Co; w.N = 9 * C.Cip; w.K = (int)rows; w.beta = 1.f; w.ksplit = 0;
-    T2P_TRY(tg(w));
-    T2P_TRY(launch_conv_w_grad_fold(dwc_, Gr_ + C.w, C.Co, C.Ci, C.Cip, s_));
-    T2P_TRY(colsum(y->g, 1, rows, C.Co, C.Cop, Gr_ + C.b));
-    if (tbias) {
-      T2P_GRAD(gt, tbias);
-      T2P_TRY(colsum(y->g, x->B, (long)x->H * x->W, C.Co, C.Cop, gt));
-    }
-    return T2P_OK;
+    float *gx = nullptr, *gt = nullptr;
+    if (x->needs_grad && !(gx = grad(x))) return T2P_ERR_HIP;
+    if (tbias && !(gt = grad(tbias))) return T2P_ERR_HIP;
+    return train_conv3x3_backward(dt_, plumbing16_, conv_w(C), x->p, y->g, x->B, x->H, x->W, gx, dwc_, Gr_ + C.w, Gr_ + C.b, gt, scratch_, s_);
   });
   return T2P_OK;
 }

@@ -37,6 +37,36 @@ struct TT {               // an NHWC activation [B][H W][C] fp32 of the training
   long numel() const { return rows() * C; }
 };
 
+// ---- the 3x3 convolution of the training step ----------------------------------------------------------------------------------------------
+// One statement of its products, run by Trainer::conv3x3 and by t2p_op_train_conv3x3 (include/t2p.h) alike: explicit buffers, and
+// pass-local device memory through ConvScratch (the trainer: its pool; the operator entry: hipMalloc, freed after the call).
+struct ConvScratch {
+  std::function<void*(size_t)> get;     // bytes -> device block, nullptr when there is none
+  std::function<void(void*)> put;       // stream-ordered: the next user of the block runs after the launches that used it
+};
+struct ConvW {            // one convolution's weights in the kernels' layouts (launch_conv_w_prep) and their 16-bit copies (or nullptr)
+  int Co = 0, Ci = 0, Cip = 0, Cop = 0;
+  const float* wf = nullptr; const float* wd = nullptr;
+  const void* wf16 = nullptr; const void* wd16 = nullptr;
+};
+// one strided product: launch_tgemm (dt = DT_F32) or launch_tgemm16 with its workspace from sc
+int train_tgemm(int dt, const TGemmArgs& a, const ConvScratch& sc, hipStream_t s);
+// out [nz][N] += the column sums of the nz blocks of `rows` rows of dy; fixed_order: through a workspace from sc, else atomics
+int train_colsum(const float* dy, int nz, long rows, int N, long ld, float* out, bool fixed_order, const ConvScratch& sc, hipStream_t s);
+// one launch of the engine's implicit-GEMM 3x3 convolution (forward and data gradient): y [B][H W][ldc] = conv3x3(x) + bias
+// (+ bias_bn[b][:]) (+ residual_inplace, which may be y), N columns written.  w16 == nullptr: the exact-f32 kernel on w; else the
+// 16-bit kernels of dtype dt on w16 and on a 16-bit copy of x made here
+int train_conv_gemm(int dt, const float* x, int B, int H, int W, int Cin, const float* w, const void* w16, long ldb, const float* bias,
+                    const float* bias_bn, int N, float* y, long ldc, const float* residual_inplace, const ConvScratch& sc, hipStream_t s);
+// y [B][H W][Cop] = conv3x3(x [B][H W][Cip]) + bias (+ tbias [B][Co]); Co of the Cop columns are written, the rest zeroed
+int train_conv3x3_forward(int dt, const ConvW& c, const float* x, int B, int H, int W, const float* bias, const float* tbias, float* y,
+                          const ConvScratch& sc, hipStream_t s);
+// the backward of that convolution: dx [B][H W][Cip] += conv3x3(dy, wd) in place (dx == nullptr: x needs no gradient), dw [Co][Ci][3][3]
+// += the gathered product dy^T x (through dwc: >= Co 9 Cip floats of scratch, compute layout), dbias [Co] and dtbias [B][Co] (or
+// nullptr) += the column sums of dy
+int train_conv3x3_backward(int dt, bool fixed_order, const ConvW& c, const float* x, const float* dy, int B, int H, int W, float* dx,
+                           float* dwc, float* dw, float* dbias, float* dtbias, const ConvScratch& sc, hipStream_t s);
+
 class Trainer {
  public:
   Trainer(const t2p_model_config& mc, const t2p_train_config& tc);
@@ -92,9 +122,8 @@ class Trainer {
   int tg(const TGemmArgs& a);               // one strided product: launch_tgemm (F32) or launch_tgemm16 (F16 / BF16)
   int reduce_ws(long floats, float** ws);   // pass-local workspace of a fixed-order reduction; null in the f32 step (atomic form)
   int colsum(const float* dy, int nz, long rows, int N, long ld, float* out);   // out [nz][N] += column sums of dy (bias gradients)
-  // one launch of the engine's implicit-GEMM 3x3 convolution (forward and data gradient of conv3x3)
-  int conv_gemm(const float* x, int B, int H, int W, int Cin, const float* w, const void* w16, long ldb, const float* bias,
-                const float* bias_bn, int N, float* y, long ldc, const float* residual_inplace);
+  static ConvW conv_w(const Conv& c) { ConvW w; w.Co = c.Co; w.Ci = c.Ci; w.Cip = c.Cip; w.Cop = c.Cop; w.wf = c.wf; w.wd = c.wd;
+                                       w.wf16 = c.wf16; w.wd16 = c.wd16; return w; }
   // Philox stream ids of the running loss call, all under the key tc_.seed: the diffusion times t, the noise z and the dropout mask of
   // residual block k.  philox.h tabulates them with their counter layouts and records the two known defects of this numbering, kept as they are.
   unsigned long long rng_t() const { return (unsigned long long)loss_calls_; }
@@ -168,6 +197,7 @@ class Trainer {
   int inp_pass_n_ = 0;              // the running pass: the request it took over (0: none, or the batch supplies mask_inpaint)
 
   DevPool pool_;
+  ConvScratch scratch_;             // pool_.get / pool_.put, for the free functions above
   hipStream_t s_ = nullptr;
   const float* Pc_ = nullptr;       // the parameters of the running pass (P_ or E_)
   std::deque<TT> acts_;

@@ -234,6 +234,72 @@ int t2p_op_tgemm16(int dtype, const float* A, int64_t sAm, int64_t sAk, const fl
   API_END
 }
 
+// scratch of one operator call: hipMalloc blocks, all held until the call ends (put is a no-op), then freed after the stream has drained --
+// whichever way the call ends
+struct OpScratch {
+  explicit OpScratch(hipStream_t stream) : s(stream) {}
+  ~OpScratch() {
+    if (blocks.empty()) return;
+    (void)hipStreamSynchronize(s);
+    for (void* p : blocks) (void)hipFree(p);
+  }
+  OpScratch(const OpScratch&) = delete;
+  OpScratch& operator=(const OpScratch&) = delete;
+  void* get(size_t bytes) {
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, std::max(bytes, (size_t)16));
+    if (e != hipSuccess) {
+      set_last_error(std::string("operator scratch: hipMalloc: ") + hipGetErrorString(e));
+      return nullptr;
+    }
+    blocks.push_back(p);
+    return p;
+  }
+  hipStream_t s;
+  std::vector<void*> blocks;
+};
+
+int t2p_op_train_conv3x3(int dtype, const float* x, const float* w, const float* bias, const float* tbias, int batch, int H, int W, int Ci,
+                         int Co, int Cip, int Cop, float* y, const float* dy, float* dx, float* dw, float* dbias, float* dtbias,
+                         int fixed_order, void* stream) {
+  API_BEGIN
+  T2P_REQUIRE(dtype == DT_F32 || dtype == DT_BF16 || dtype == DT_F16, "train_conv3x3: dtype is 0 (f32), 1 (bf16) or 2 (f16)");
+  T2P_REQUIRE(x && w && bias && y && batch > 0 && H > 0 && W > 0 && Ci > 0 && Co > 0, "train_conv3x3 arguments");
+  const int vec = dtype == DT_F32 ? 4 : 8;
+  T2P_REQUIRE(Cip >= Ci && Cop >= Co && Cip % vec == 0 && Cop % vec == 0, "train_conv3x3: Cip / Cop pad Ci / Co to the kernels' vector width");
+  T2P_REQUIRE(!tbias || Cop == Co, "train_conv3x3: the time-embedding bias needs Cop == Co");
+  T2P_REQUIRE(!dy || (dw && dbias && (dtbias != nullptr) == (tbias != nullptr)), "train_conv3x3: the backward takes dw, dbias and (with tbias) dtbias");
+  T2P_REQUIRE((long)batch * H * W < (1L << 31), "train_conv3x3: rows");
+  hipStream_t s = (hipStream_t)stream;
+  OpScratch mem(s);
+  ConvScratch sc;
+  sc.get = [&mem](size_t bytes) { return mem.get(bytes); };
+  sc.put = [](void*) {};
+  const bool need_dx = dy && dx;
+  const size_t nf = (size_t)Co * 9 * Cip, nd = (size_t)Ci * 9 * Cop;
+  ConvW c;
+  c.Co = Co; c.Ci = Ci; c.Cip = Cip; c.Cop = Cop;
+  float* wf = (float*)mem.get(nf * 4);
+  float* wd = need_dx ? (float*)mem.get(nd * 4) : nullptr;            // (the network input's convolution has none either)
+  if (!wf || (need_dx && !wd)) return T2P_ERR_HIP;
+  T2P_TRY(launch_conv_w_prep(w, wf, wd, Co, Ci, Cip, Cop, s));
+  c.wf = wf; c.wd = wd;
+  if (dtype != DT_F32) {
+    void* wf16 = mem.get(nf * 2);
+    void* wd16 = need_dx ? mem.get(nd * 2) : nullptr;
+    if (!wf16 || (need_dx && !wd16)) return T2P_ERR_HIP;
+    T2P_TRY(launch_convert(wf, wf16, dtype, (long)nf, s));
+    if (need_dx) T2P_TRY(launch_convert(wd, wd16, dtype, (long)nd, s));
+    c.wf16 = wf16; c.wd16 = wd16;
+  }
+  T2P_TRY(train_conv3x3_forward(dtype, c, x, batch, H, W, bias, tbias, y, sc, s));
+  if (!dy) return T2P_OK;
+  float* dwc = (float*)mem.get(nf * 4);
+  if (!dwc) return T2P_ERR_HIP;
+  return train_conv3x3_backward(dtype, fixed_order != 0, c, x, dy, batch, H, W, dx, dwc, dw, dbias, dtbias, sc, s);
+  API_END
+}
+
 // block_dropout alone, through the two kernels of the training pass: the residue flags, then dsm_perturb with an all-false pair mask
 // (every element takes the select's fallback branch, perturbed = the dropped x)
 int t2p_op_ss_block_dropout(const float* x, float* out, int batch, int C, int L, const int32_t* host_blocks, int n, const uint8_t* host_drop,
