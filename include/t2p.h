@@ -276,6 +276,8 @@ int t2p_op_ddim_update(const float* x, const float* eps_c, const float* eps_u, c
  * t2p_train_set_ss_blocks <- block_dropout(coords_6d, batch["ss_indices"]) under the ss condition (losses.py:54-64, called at :106-107)
  * t2p_train_set_inpaint_draw <- utils.random_mask_batch(batch, config) (utils.py:15-60), which train.py calls before every train and eval
  *                          step (train.py:176, :193) when "inpainting" is in the condition
+ * t2p_train_set_context_drop <- (no counterpart: the reference's loss has no context dropout) per-sample dropout of the text context,
+ *                          the training that gives the guided samplers' out(context * 0) a meaning
  * The model runs in train mode (models/utils.py:116-118): Dropout_0 of every residual block is active when dropout > 0.       */
 typedef struct t2p_train_config {
   double lr, beta1, eps, weight_decay;   /* optim.lr / beta1 / eps / weight_decay; beta2 = 0.999 as get_optimizer fixes it    */
@@ -355,6 +357,19 @@ int t2p_train_set_ss_blocks(t2p_trainer* t, const int32_t* host_blocks, int n, c
  * differs from the pass's batch fails that pass, which computes and changes nothing, and the request is cleared.  Without a request
  * and without mask_inpaint the pass is refused as before ("the inpainting condition needs batch.mask_inpaint"). */
 int t2p_train_set_inpaint_draw(t2p_trainer* t, const int32_t* host_len_lo_hi, int B, double random_p, double contiguous_p);
+/* Text-context dropout, the training side of classifier-free guidance (the samplers evaluate w out(ctx) + (1 - w) out(ctx * 0); the
+ * second term needs a network that has trained on an all-zero context).  Every sample b of the batch is dropped independently; a dropped
+ * sample trains exactly as if batch->context[b] were all zeros; kept samples and batch->context itself are not touched.  host_drop: host
+ * uint8 [B], the decision per sample (copied at the call), or NULL with B > 0 = drawn on the device: sample b is dropped iff
+ * u < (float)p, u one Philox uniform keyed by the trainer seed (training layout, counter b, stream 4096 loss_calls + 4: csrc/philox.h).
+ * attn2.to_k and attn2.to_v have no bias, so a zero context is K = V = 0: the pass zeroes the dropped samples' rows of every projected
+ * K and V in place (no copy of the context) and, in the backward pass, the same rows of dK and dV before the projections' weight
+ * gradients are formed -- those receive nothing from a dropped sample.
+ * Per-batch data, like the ss block list: the NEXT t2p_train_loss / t2p_train_step / t2p_train_eval_loss consumes the request,
+ * whatever becomes of that pass (eval_loss after explicit all-ones decisions is the unconditional evaluation loss); B = 0 clears it.
+ * A pass without a request makes no launch and no draw for this.  Refused, leaving the stored request as it was: B < 0; p outside
+ * [0, 1] or NaN.  A B that differs from the pass's batch fails that pass, which computes and changes nothing, and the request is cleared. */
+int t2p_train_set_context_drop(t2p_trainer* t, const uint8_t* host_drop, int B, double p);
 /* loss_host: host float; score_out (optional): device fp32 (batch, C, L, L), the score the loss was computed from */
 int t2p_train_loss(t2p_trainer* t, const t2p_train_batch* batch, int backward, float* loss_host, float* score_out, void* stream);
 int t2p_train_step(t2p_trainer* t, const t2p_train_batch* batch, float* loss_host, void* stream);
@@ -417,6 +432,13 @@ int t2p_op_ss_block_dropout(const float* x, float* out, int batch, int C, int L,
  * t2p_train_set_inpaint_draw refuses (with L for max_res_num), B <= 0, a force_mode outside -1 .. 2. */
 int t2p_op_inpaint_mask_draw(const int32_t* host_len_lo_hi, int B, int L, double random_p, double contiguous_p, uint64_t seed, uint64_t stream_id,
                              int force_mode, uint8_t* flags_out, uint8_t* pair_out, int* mode_out_host, void* stream);
+/* the two kernels of t2p_train_set_context_drop alone, in place on x = device fp32 [batch][row_floats] (16-byte aligned): the decisions
+ * (host_drop: host uint8 [batch], or NULL = drawn at probability p under the Philox key `seed` and stream `stream_id`, the trainer's:
+ * its seed and 4096 loss_calls + 4), then row b of x becomes +0.0f where sample b is dropped -- stored, not multiplied, so an Inf or a
+ * NaN becomes 0; the other rows are neither read nor written.  drop_out_device (optional): device uint8 [batch], the decisions used.
+ * Refused with x untouched: batch <= 0, row_floats <= 0 or not a multiple of 4 (16-byte stores), p outside [0, 1]. */
+int t2p_op_context_drop(float* x, int batch, int64_t row_floats, const uint8_t* host_drop, double p, uint64_t seed, uint64_t stream_id,
+                        uint8_t* drop_out_device, void* stream);
 /* backward halves of the operators (gradients accumulate into dx / dgamma / dbeta / du) */
 int t2p_op_groupnorm_backward(const float* x, const float* dy, const float* gamma, const float* beta, int silu, int batch, int HW, int C,
                               int groups, float eps, float* dx, float* dgamma, float* dbeta, void* stream);

@@ -24,9 +24,11 @@
 //                                                                                                               (b + 1) 2^32       sample b, word 0: r = lo + (((w >> 8) (hi - lo)) >> 24),
 //                                                                                                                                  word 1: start = ((w >> 8) (l - r)) >> 24
 //                                                                                                               (b + 1) 2^32 + 1 + j   word 0: the 32-bit key of residue j (the r lowest are masked)
-//                             Dropout_0 k   trainer seed   training  rng_dropout(k)               -           quad q    4 words: element 4 q + j kept
+//                             context drop  trainer seed   training  rng_ctx() = 4096 calls + 4   -           sample b  word 0: the text context dropped when u < p
+//                             Dropout_0 k   trainer seed   training  rng_dropout(k)            -           quad q    4 words: element 4 q + j kept
 //                                                                      = 4096 calls + 16 + k                            when u_j >= p
 //   t2p_op_inpaint_mask_draw                caller's seed  training  caller's                     -           as the trainer's inpaint mask
+//   t2p_op_context_drop                     caller's seed  training  caller's                     -           as the trainer's context drop
 //   (calls = Trainer::loss_calls_, the number of loss calls completed before the running one.)
 //
 // Two known defects, recorded here and left as they are (fixing either changes drawn bits):

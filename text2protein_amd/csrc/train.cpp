@@ -351,6 +351,25 @@ int Trainer::set_inpaint_draw(const int32_t* host_len_lo_hi, int B, double rando
   inp_n_ = B; inp_p_random_ = (float)random_p; inp_contig_above_ = (float)(1.0 - contiguous_p);
   return T2P_OK;
 }
+int Trainer::set_context_drop(const uint8_t* host_drop, int B, double p) {
+  T2P_REQUIRE(B >= 0, "set_context_drop: a negative batch size");
+  if (B == 0) { ctx_n_ = 0; return T2P_OK; }
+  T2P_REQUIRE(p >= 0.0 && p <= 1.0, "set_context_drop: the dropout probability must lie in [0, 1]");      // (false for a NaN)
+  // as set_ss_blocks: no pass is in flight here, the buffer is free to overwrite
+  if (B > ctx_cap_) {
+    const int cap = std::max(B, 2 * ctx_cap_);
+    uint8_t* nb = (uint8_t*)pool_.get((size_t)cap);
+    if (!nb) return T2P_ERR_HIP;
+    if (ctx_drop_) pool_.put(ctx_drop_);
+    ctx_drop_ = nb; ctx_cap_ = cap; ctx_n_ = 0;       // (the request in the old buffer goes with it)
+  }
+  if (host_drop) {
+    ctx_n_ = 0;                                       // a failed copy leaves no request
+    T2P_HIP_CHECK(hipMemcpy(ctx_drop_, host_drop, (size_t)B, hipMemcpyHostToDevice));
+  }
+  ctx_n_ = B; ctx_given_ = host_drop != nullptr; ctx_p_ = p;
+  return T2P_OK;
+}
 
 // ---- pass-local memory ------------------------------------------------------------------------------------------------------------------
 float* Trainer::tmp(size_t bytes) {
@@ -734,6 +753,19 @@ int Trainer::st_block(const LayerT& L, TT* x, TT* ctx, TT** out) {
     T2P_TRY(linear(l, wq, &q));
     T2P_TRY(linear(kv_src ? kv_src : l, wk, &k));
     T2P_TRY(linear(kv_src ? kv_src : l, wv, &v));
+    if (kv_src && ctx_pass_n_ > 0) {
+      // context dropout: to_k and to_v have no bias, so a zero context is K = V = 0 for that sample.  The row mask is applied to the
+      // projections in place (no copy of the context) and, in the reverse sweep between attention's backward and the two linears', to
+      // their gradients: dW_k and dW_v receive nothing from a dropped sample, as with a context that was zero
+      T2P_REQUIRE(k->numel() == v->numel() && k->B == ctx_pass_n_, "context dropout: K / V shapes");
+      const long n = k->numel() / k->B;
+      T2P_TRY(launch_zero_sample_rows(k->p, v->p, k->B, n, ctx_drop_, s_));
+      tape_.push_back([this, k, v, n]() -> int {
+        float* g0 = k->g ? k->g : v->g;
+        float* g1 = k->g ? v->g : nullptr;
+        return g0 ? launch_zero_sample_rows(g0, g1, k->B, n, ctx_drop_, s_) : T2P_OK;
+      });
+    }
     T2P_TRY(attention(q, k, v, heads, scale, &o));
     T2P_TRY(linear(o, wo, &y));
     return add_scale(y, t, 1.f, res);
@@ -826,6 +858,9 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool tra
   }
   T2P_TRY(launch_dsm_perturb(b.coords_6d, z, stdv, mean_coef, b.mask_pair, mask_inpaint, tc_.cond_flags, B, Cx, L, perturbed, mask, num_elem, s_,
                              ss_rows));
+  // text-context dropout: the decisions of this pass, drawn here unless they were given.  batch.context itself stays as the caller gave
+  // it; every cross-attention zeroes the dropped samples' rows of its projected K and V (st_block)
+  if (ctx_pass_n_ > 0 && !ctx_given_) T2P_TRY(launch_context_drop_draw(B, (float)ctx_p_, tc_.seed, rng_ctx(), ctx_drop_, s_));
 
   // UNetModel.forward (ncsnpp.py:220-263)
   T2P_ACT(x0, B, L, L, 8, false);
@@ -915,6 +950,11 @@ int Trainer::loss(const t2p_train_batch& b, bool backward, bool use_ema, float* 
   const int inp_request = inp_n_;                 // so is the random-mask request; a batch that supplies mask_inpaint ignores it
   inp_pass_n_ = b.mask_inpaint ? 0 : inp_n_;
   inp_n_ = 0;
+  ctx_pass_n_ = ctx_n_;                           // and the context-dropout request
+  ctx_n_ = 0;
+  T2P_REQUIRE(ctx_pass_n_ == 0 || ctx_pass_n_ == b.batch,
+              "context dropout: the request holds " + std::to_string(ctx_pass_n_) + " samples, the batch " + std::to_string(b.batch) +
+                  "; nothing was computed or changed and the request is cleared");
   T2P_REQUIRE(inp_pass_n_ == 0 || inp_pass_n_ == b.batch,
               "inpaint draw: the request holds " + std::to_string(inp_request) + " samples, the batch " + std::to_string(b.batch) +
                   "; nothing was computed or changed and the request is cleared");

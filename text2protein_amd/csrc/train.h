@@ -89,6 +89,9 @@ class Trainer {
   // random_mask_batch (utils.py:15-60) of the NEXT loss / step / eval pass whose batch carries no mask_inpaint: host int32 [B][3] =
   // (l, lo, hi) per sample and the two mode probabilities.  That pass draws the mask on the device and consumes the request; B = 0 clears it
   int set_inpaint_draw(const int32_t* host_len_lo_hi, int B, double random_p, double contiguous_p);
+  // text-context dropout of the NEXT loss / step / eval pass (training for classifier-free guidance): a dropped sample trains as if its
+  // context were all zeros.  host_drop: host uint8 [B] decisions, or nullptr = drawn on the device at probability p.  B = 0 clears
+  int set_context_drop(const uint8_t* host_drop, int B, double p);
   // loss_fn (losses.py:105-134); with `backward` also d loss / d parameters into the gradient buffer (zeroed first: optimizer.zero_grad())
   int loss(const t2p_train_batch& b, bool backward, bool use_ema, float* loss_host, float* score_out, hipStream_t s);
   // step_fn with train=True (losses.py:165-176) = loss(backward) + apply()
@@ -133,6 +136,8 @@ class Trainer {
   unsigned long long rng_ss() const { return (unsigned long long)(loss_calls_ * 4096 + 2); }
   // the random inpainting mask of the running loss call (counter indices: philox.h); + 3 of the free ids
   unsigned long long rng_inpaint() const { return (unsigned long long)(loss_calls_ * 4096 + 3); }
+  // the context-dropout decisions of the running loss call (counter = the sample index); + 4 of the free ids
+  unsigned long long rng_ctx() const { return (unsigned long long)(loss_calls_ * 4096 + 4); }
 
   // forward ops: each appends its backward to tape_
   TT* act(int B, int H, int W, int C, bool needs_grad = true);
@@ -195,6 +200,12 @@ class Trainer {
   int inp_cap_ = 0, inp_n_ = 0;     // inp_n_: the batch size of the request, 0 = none
   float inp_p_random_ = 0.f, inp_contig_above_ = 1.f;   // (float)random_p, (float)(1.0 - contiguous_p)
   int inp_pass_n_ = 0;              // the running pass: the request it took over (0: none, or the batch supplies mask_inpaint)
+  // text-context dropout of the next pass (set_context_drop): device uint8 [cap] decisions, given or drawn by the pass
+  uint8_t* ctx_drop_ = nullptr;
+  int ctx_cap_ = 0, ctx_n_ = 0;     // ctx_n_: the batch size of the request, 0 = none
+  bool ctx_given_ = false;          // explicit decisions (else drawn on the device at ctx_p_)
+  double ctx_p_ = 0.0;
+  int ctx_pass_n_ = 0;              // the running pass: the request it took over (0: none, the launches of a pass without context dropout)
 
   DevPool pool_;
   ConvScratch scratch_;             // pool_.get / pool_.put, for the free functions above

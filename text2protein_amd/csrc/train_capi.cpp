@@ -130,6 +130,13 @@ int t2p_train_set_inpaint_draw(t2p_trainer* t, const int32_t* host_len_lo_hi, in
   API_END
 }
 
+int t2p_train_set_context_drop(t2p_trainer* t, const uint8_t* host_drop, int B, double p) {
+  API_BEGIN
+  T2P_REQUIRE(t, "null trainer");
+  return t->impl.set_context_drop(host_drop, B, p);
+  API_END
+}
+
 int t2p_train_loss(t2p_trainer* t, const t2p_train_batch* batch, int backward, float* loss_host, float* score_out, void* stream) {
   API_BEGIN
   T2P_REQUIRE(t && batch, "null argument");
@@ -347,6 +354,34 @@ int t2p_op_ss_block_dropout(const float* x, float* out, int batch, int C, int L,
   (void)hipStreamSynchronize(s);                                         // host_blocks / host_drop and the scratch are free after the call
   (void)hipFree(ws);
   return rc;
+  API_END
+}
+
+// context dropout alone, through the two kernels of the training pass: the decisions (given or drawn), then the row zeroing in place
+int t2p_op_context_drop(float* x, int batch, int64_t row_floats, const uint8_t* host_drop, double p, uint64_t seed, uint64_t stream_id,
+                        uint8_t* drop_out_device, void* stream) {
+  API_BEGIN
+  T2P_REQUIRE(x && batch > 0 && batch <= 65535 && row_floats > 0, "context_drop arguments");
+  T2P_REQUIRE(row_floats % 4 == 0, "context_drop: row_floats must be a multiple of 4 (16-byte stores)");
+  T2P_REQUIRE(((uintptr_t)x & 15) == 0, "context_drop: x must be 16-byte aligned");
+  T2P_REQUIRE(p >= 0.0 && p <= 1.0, "context_drop: the dropout probability must lie in [0, 1]");
+  hipStream_t s = (hipStream_t)stream;
+  unsigned char* drop = nullptr;
+  T2P_HIP_CHECK(hipMalloc(&drop, (size_t)batch));
+  int rc = T2P_OK;
+  hipError_t e = hipSuccess;
+  if (host_drop) e = hipMemcpyAsync(drop, host_drop, (size_t)batch, hipMemcpyHostToDevice, s);
+  else rc = launch_context_drop_draw(batch, (float)p, seed, stream_id, drop, s);
+  if (rc == T2P_OK && e == hipSuccess) rc = launch_zero_sample_rows(x, nullptr, batch, (long)row_floats, drop, s);
+  if (rc == T2P_OK && e == hipSuccess && drop_out_device) e = hipMemcpyAsync(drop_out_device, drop, (size_t)batch, hipMemcpyDeviceToDevice, s);
+  const hipError_t e2 = hipStreamSynchronize(s);                         // host_drop and the scratch are free after the call
+  (void)hipFree(drop);
+  if (rc != T2P_OK) return rc;
+  if (e != hipSuccess || e2 != hipSuccess) {
+    set_last_error(std::string("context_drop: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+    return T2P_ERR_HIP;
+  }
+  return T2P_OK;
   API_END
 }
 

@@ -113,6 +113,12 @@ int launch_dsm_perturb(const float* x, const float* z, const float* std, const f
 // with counter k, stream id stream_id and key seed (the uniform of dsm_prepare's t).  drop_out (optional, [n]): the decisions used
 int launch_ss_block_rows(const int* blocks, int n, const unsigned char* drop, float p, unsigned long long seed, unsigned long long stream_id,
                          int B, int L, unsigned char* rows, unsigned char* drop_out, hipStream_t s);
+// text-context dropout, the decisions: drop [B] uint8 = 1 where sample b is dropped, iff u < p with u = (c0 >> 8) 2^-24 of Philox4x32-10,
+// training layout, counter b, stream id stream_id, key seed (the uniform of dsm_prepare's t and of the block decisions)
+int launch_context_drop_draw(int B, float p, unsigned long long seed, unsigned long long stream_id, unsigned char* drop, hipStream_t s);
+// x0 and (optional) x1: fp32 [B][n], 16-byte aligned, n % 4 == 0.  Row b of each becomes +0.0f where drop[b] != 0 (stored, not multiplied:
+// an Inf or a NaN becomes 0); the rows of the other samples are neither read nor written.  One launch for both buffers
+int launch_zero_sample_rows(float* x0, float* x1, int B, long n, const unsigned char* drop, hipStream_t s);
 // random_mask_batch (utils.py:15-60) drawn on the device: flags [B][L] uint8 (1 = residue masked) and pair [B][L][L] uint8 =
 // flags[b][i] | flags[b][j], one workgroup per sample.  llh: device int32 [B][3] = (l, lo, hi), l valid residues, lo = int(min l),
 // hi = int(max l) from the host; the callers guarantee 0 <= lo < hi <= l <= L <= 256.  mode: force_mode when >= 0, else drawn from one

@@ -1174,6 +1174,48 @@ int launch_ss_block_rows(const int* blocks, int n, const unsigned char* drop, fl
   return T2P_OK;
 }
 
+// ---- text-context dropout (training for classifier-free guidance: a dropped sample trains on context * 0) --------------------------------
+// one thread per sample: drop[b] = u < p, u the Philox uniform dsm_time forms ((c0 >> 8) 2^-24), counter = the sample index, key = seed
+__global__ __launch_bounds__(64) void context_drop_draw_kernel(const int B, const float p, const unsigned long long seed,
+                                                               const unsigned long long stream_id, unsigned char* __restrict__ drop) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  uint32_t c[4];
+  philox_counter_training(c, b, stream_id);
+  philox4x32_10(c, seed);
+  drop[b] = philox_uniform24(c[0]) < p ? 1 : 0;
+}
+int launch_context_drop_draw(int B, float p, unsigned long long seed, unsigned long long stream_id, unsigned char* drop, hipStream_t s) {
+  T2P_REQUIRE(drop && B > 0 && p >= 0.f && p <= 1.f, "context_drop_draw arguments");
+  hipLaunchKernelGGL(context_drop_draw_kernel, dim3(cdiv_l(B, 64)), dim3(64), 0, s, B, p, seed, stream_id, drop);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+
+// grid (chunks of ZERO_ROW_CHUNK float4, B, 1 or 2 buffers): the workgroups of a kept sample read its flag and exit; those of a dropped
+// one store +0.0f over their chunk of row b (16-byte stores; a store, not a product: Inf and NaN become 0 too)
+constexpr int ZERO_ROW_CHUNK = 1024;               // float4 per workgroup: four stores per thread
+__global__ __launch_bounds__(256) void zero_sample_rows_kernel(float4* __restrict__ x0, float4* __restrict__ x1, const long n4,
+                                                               const unsigned char* __restrict__ drop) {
+  const int b = blockIdx.y;
+  if (!drop[b]) return;
+  float4* __restrict__ row = (blockIdx.z ? x1 : x0) + (long)b * n4;
+  const long begin = (long)blockIdx.x * ZERO_ROW_CHUNK;
+  const long end = begin + ZERO_ROW_CHUNK < n4 ? begin + ZERO_ROW_CHUNK : n4;
+  for (long i = begin + threadIdx.x; i < end; i += 256) row[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+int launch_zero_sample_rows(float* x0, float* x1, int B, long n, const unsigned char* drop, hipStream_t s) {
+  T2P_REQUIRE(x0 && drop && B > 0 && B <= 65535 && n > 0, "zero_sample_rows arguments");
+  T2P_REQUIRE(n % 4 == 0, "zero_sample_rows: the row length must be a multiple of 4 floats (16-byte stores)");
+  T2P_REQUIRE(((uintptr_t)x0 & 15) == 0 && ((uintptr_t)x1 & 15) == 0, "zero_sample_rows: the buffers must be 16-byte aligned");
+  const long n4 = n / 4, chunks = (n4 + ZERO_ROW_CHUNK - 1) / ZERO_ROW_CHUNK;
+  T2P_REQUIRE(chunks < (1L << 31), "zero_sample_rows: row too long");
+  hipLaunchKernelGGL(zero_sample_rows_kernel, dim3((unsigned)chunks, B, x1 ? 2 : 1), dim3(256), 0, s, reinterpret_cast<float4*>(x0),
+                     reinterpret_cast<float4*>(x1), n4, drop);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+
 // ---- random inpainting mask (utils.py:15-60, called by train.py before every train and eval step) ----------------------------------------
 // grid B, 256 threads: thread j is residue j of sample blockIdx.x (L <= 256).  Counter indices within the stream (training layout):
 // 0 the mode (word 0); (b + 1) 2^32 sample b's count and window start (words 0, 1); (b + 1) 2^32 + 1 + j residue j's key (word 0).

@@ -102,6 +102,37 @@ def _check_inpaint_draw(draw):
         raise ValueError(f"inpaint_mask_draw must be None, 'host' or 'device', not {draw!r}")
 
 
+def _check_context_dropout(p, draw):
+    try:
+        ok = 0.0 <= float(p) <= 1.0            # (a NaN fails the comparison)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"context_dropout must be a probability in [0, 1], not {p!r}")
+    if draw not in ("host", "device"):
+        raise ValueError(f"context_dropout_draw must be 'host' or 'device', not {draw!r}")
+
+
+def draw_context_decisions(n, context_dropout):
+    """One ``random.random() < context_dropout`` per sample in sample order."""
+    return [1 if random.random() < context_dropout else 0 for _ in range(int(n))]
+
+
+def _request_context_drop(model, batch, p, draw):
+    """Training for classifier-free guidance: every sample of the batch loses its text context with probability ``p`` in the pass that
+    follows.  ``p == 0``: no native call and no ``random`` draw.  Comes after the block-dropout and inpainting-mask draws, so one
+    ``random.seed`` reproduces a step; a failure here clears those two requests, as no pass follows."""
+    if p <= 0.0:
+        return
+    try:
+        n = batch["coords_6d"].shape[0]
+        model.set_context_drop(n, drop=draw_context_decisions(n, p) if draw == "host" else None, p=p)
+    except Exception:
+        model.set_ss_blocks([])
+        model.set_inpaint_draw(None, None)
+        raise
+
+
 def _draw_batch_inpaint_mask(model, batch, condition, draw):
     """train.py:176 / :193: under the ``inpainting`` condition a batch WITHOUT ``mask_inpaint`` gets the reference's random mask --
     ``"host"``: ``conditions.random_mask_batch`` on a copy of the batch (the reference's draws in its order); ``"device"``: the request of
@@ -309,6 +340,22 @@ class HipTrainModel:
         check(self.lib.t2p_train_set_inpaint_draw(self._h, C.c_void_p(arr.ctypes.data), arr.shape[0], float(inpainting_cfg.random_mask_prob),
                                                   float(inpainting_cfg.contiguous_mask_prob)))
 
+    def set_context_drop(self, n, drop=None, p=0.1):
+        """Text-context dropout (training for classifier-free guidance) for the NEXT ``loss`` / ``step`` / ``eval_loss``, which consumes
+        the request: ``n`` = the batch size, ``drop`` = one decision per sample or None = drawn on the device at probability ``p`` from
+        the trainer's Philox.  A dropped sample trains exactly as if ``batch["context"][b]`` were all zeros -- the ``context * 0`` of
+        the guided samplers; ``batch["context"]`` itself is not modified.  ``n`` = 0 / None clears the request."""
+        n = int(n or 0)
+        if n == 0:
+            check(self.lib.t2p_train_set_context_drop(self._h, None, 0, 0.0))
+            return
+        d = None
+        if drop is not None:
+            d = np.ascontiguousarray(np.asarray(drop).reshape(-1) != 0, dtype=np.uint8)
+            if d.shape[0] != n:
+                raise T2PError(f"{d.shape[0]} context-dropout decisions for {n} samples")
+        check(self.lib.t2p_train_set_context_drop(self._h, C.c_void_p(d.ctypes.data) if d is not None else None, n, float(p)))
+
     def _batch(self, batch, t=None, z=None):
         dev = self.device
         hold = [batch["coords_6d"].to(dev, torch.float32).contiguous(), batch["mask_pair"].to(dev, torch.uint8).contiguous(),
@@ -326,8 +373,9 @@ class HipTrainModel:
         return tb, hold
 
     def _pass_inputs(self, batch, t, z, need_weights=True):
-        """``_batch`` for a pass.  A pass that fails here never reaches the library, so a block list (``set_ss_blocks``) or a random-mask
-        request (``set_inpaint_draw``) set for it is cleared: it is this batch's data and must not reach whichever pass comes next."""
+        """``_batch`` for a pass.  A pass that fails here never reaches the library, so a block list (``set_ss_blocks``), a random-mask
+        request (``set_inpaint_draw``) or a context-dropout request (``set_context_drop``) set for it is cleared: it is this batch's
+        data and must not reach whichever pass comes next."""
         try:
             if need_weights and not self._loaded:
                 raise T2PError("load weights before training")
@@ -335,6 +383,7 @@ class HipTrainModel:
         except Exception:
             self.lib.t2p_train_set_ss_blocks(self._h, None, 0, None, 0.0)
             self.lib.t2p_train_set_inpaint_draw(self._h, None, 0, 0.0, 0.0)
+            self.lib.t2p_train_set_context_drop(self._h, None, 0, 0.0)
             raise
 
     def loss(self, batch, t=None, z=None, backward=False, return_score=False):
@@ -528,7 +577,8 @@ class ExponentialMovingAverage:
         self.model.set_step(cur[0], ema_updates=int(state_dict["num_updates"]))
 
 
-def get_sde_loss_fn(sde, train, eps=1e-5, block_dropout=0.2, block_dropout_draw="host", inpaint_mask_draw=None):
+def get_sde_loss_fn(sde, train, eps=1e-5, block_dropout=0.2, block_dropout_draw="host", inpaint_mask_draw=None, context_dropout=0.0,
+                    context_dropout_draw="device"):
     """losses.py:66-136 for ``sde`` = VESDE, VPSDE or subVPSDE (the model takes the SDE on first use and keeps it).  ``batch["context"]`` holds the caption embedding (B, T, context_dim); with raw captions pass
     ``llm_components`` = a callable ``captions -> embedding`` (text2protein_amd.text_context.TextContextProducer).
 
@@ -541,10 +591,20 @@ def get_sde_loss_fn(sde, train, eps=1e-5, block_dropout=0.2, block_dropout_draw=
     before every train and eval step (``utils.random_mask_batch``, train.py:176, :193) from ``config.model.inpainting`` and the residue
     counts ``batch["lengths"]`` / ``batch["aa_str"]``.  ``"host"``: ``conditions.random_mask_batch``, the reference's ``random`` / ``torch``
     draws in its order (the same seeds give its mask); ``"device"``: drawn on the GPU from the trainer seed
-    (``HipTrainModel.set_inpaint_draw``).  None (the default): no mask is drawn and such a batch is refused."""
+    (``HipTrainModel.set_inpaint_draw``).  None (the default): no mask is drawn and such a batch is refused.
+
+    ``context_dropout``: training for classifier-free guidance.  With ``train=True`` and a probability above 0, every sample of every
+    batch loses its text context with that probability and trains exactly as if ``batch["context"][b]`` were all zeros -- the
+    ``context * 0`` that ``--guidance_w`` / ``guidance_w=`` evaluate (``HipTrainModel.set_context_drop``; the reference's loss has no
+    counterpart).  ``context_dropout_draw="device"``: drawn on the GPU from the trainer seed; ``"host"``: ``random.random()`` once per
+    sample in sample order, after the block-dropout and inpainting-mask host draws, so one ``random.seed`` reproduces a step.
+    ``train=False`` never drops: the evaluation loss stays the conditional one.  At 0.0 (the default) nothing is requested and no
+    ``random`` draw is consumed.  A probability outside [0, 1] or an unknown draw mode raises ``ValueError`` here."""
     _sde_key(sde)
     _check_draw(block_dropout_draw)
     _check_inpaint_draw(inpaint_mask_draw)
+    _check_context_dropout(context_dropout, context_dropout_draw)
+    context_dropout = float(context_dropout)
 
     def loss_fn(model, batch, condition=None, llm_components=None, t=None, z=None):
         model.set_sde(sde)
@@ -557,21 +617,29 @@ def get_sde_loss_fn(sde, train, eps=1e-5, block_dropout=0.2, block_dropout_draw=
         _set_batch_ss_blocks(model, batch, condition, block_dropout, block_dropout_draw)
         batch = _draw_batch_inpaint_mask(model, batch, condition, inpaint_mask_draw)
         if train:
+            _request_context_drop(model, batch, context_dropout, context_dropout_draw)
             return model.loss(batch, t=t, z=z, backward=False)
         return model.eval_loss(batch, t=t, z=z)
 
     return loss_fn
 
 
-def get_step_fn(sde, train, optimize_fn=None, dist=None, block_dropout=0.2, block_dropout_draw="host", inpaint_mask_draw=None):
+def get_step_fn(sde, train, optimize_fn=None, dist=None, block_dropout=0.2, block_dropout_draw="host", inpaint_mask_draw=None,
+                context_dropout=0.0, context_dropout_draw="device"):
     """losses.py:140-186.  ``block_dropout`` / ``block_dropout_draw`` / ``inpaint_mask_draw``: as in ``get_sde_loss_fn`` (each rank drops the blocks and draws the mask of its shard).  ``dist`` (an initialised ``torch.distributed`` module, text2protein_amd.distributed.init_process_group):
     data-parallel training, one process per GPU -- each rank takes its shard of the batch, the flat gradient buffer is averaged over
     the ranks with ONE all-reduce (RCCL over xGMI) and every rank applies the same update; the returned loss is the mean over the
     ranks.  With equal shards this is the reference's DataParallel step on the concatenated batch (the loss is a mean of per-sample
-    terms, losses.py:128-131)."""
+    terms, losses.py:128-131).
+
+    ``context_dropout`` / ``context_dropout_draw``: as in ``get_sde_loss_fn`` (train steps only).  Under ``dist`` each rank decides for
+    its own shard; the device draw is keyed by the trainer seed and the sample's index WITHIN the shard, so ranks need different
+    trainer seeds (``get_train_model(config, seed=base + rank)``) to drop different patterns."""
     _sde_key(sde)
     _check_draw(block_dropout_draw)
     _check_inpaint_draw(inpaint_mask_draw)
+    _check_context_dropout(context_dropout, context_dropout_draw)
+    context_dropout = float(context_dropout)
     world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
 
     def step_fn(state, batch, condition=None, t=None, z=None):
@@ -589,6 +657,7 @@ def get_step_fn(sde, train, optimize_fn=None, dist=None, block_dropout=0.2, bloc
                 optimize_fn(state["optimizer"], model.parameters(), step=state["step"])
             _set_batch_ss_blocks(model, batch, condition, block_dropout, block_dropout_draw)
             batch = _draw_batch_inpaint_mask(model, batch, condition, inpaint_mask_draw)
+            _request_context_drop(model, batch, context_dropout, context_dropout_draw)
             prev = model.get_step()
             model.set_step(state["step"])
             if world == 1:

@@ -2,6 +2,7 @@
 
     python tools/bench_train.py --config cond_length.yml --batch 8 --steps 5 [--tokens 64] [--dropout 0.1] [--dtype f32|f16|bf16] [--sde ve|vp|subvp]
                                 [--condition length,ss [--ss-blocks 64]] [--inpaint_draw host|device [--rounds 5]]
+                                [--context-dropout 0.1 [--rounds 5]]
 
 --ss-blocks N: N synthetic secondary-structure blocks per step (8 residues each, spread over the samples and the 100 valid residues),
 dropped on the device at the reference's p = 0.2; needs the `ss` condition, which needs an 8-channel configuration
@@ -12,6 +13,11 @@ from config.model.inpainting and 100 valid residues per sample) is drawn before 
 device from the trainer's Philox; needs the `inpainting` condition (cond_length_inpainting.yml).  With --rounds R the same process times R
 rounds of --steps steps WITH A SUPPLIED MASK and R rounds with the drawn one, alternating, and reports every round of both
 (`supplied_ms_rounds`, `drawn_ms_rounds`); `ms_per_step` is then the median drawn round.
+
+--context-dropout P: text-context dropout (training for classifier-free guidance), every sample dropped on the device with probability P
+before every step (get_step_fn(context_dropout=P)).  With --rounds R the same process times R rounds of --steps PLAIN steps and R rounds of
+dropout steps, alternating, and reports every round of both (`plain_ms_rounds`, `ctxdrop_ms_rounds`) with their medians and spreads
+(max - min); `ms_per_step` is then the median dropout round.
 
 Prints one JSON line: ms per step, samples/s, the loss sequence, device memory, and the achieved matrix rate against the peak of the
 compute dtype's MFMA (157.3 TFLOP/s f32, 2500 TFLOP/s f16 / bf16), counting a step as 3 x the forward pass AS EXECUTED (the text K / V projections are inside a training
@@ -46,7 +52,9 @@ def main():
     ap.add_argument("--condition", default="", help="override model.condition, comma-separated (e.g. length,ss)")
     ap.add_argument("--ss-blocks", type=int, default=0, help="synthetic secondary-structure blocks per step, drawn on the device")
     ap.add_argument("--inpaint_draw", default=None, choices=["host", "device"], help="draw the random inpainting mask before every step")
-    ap.add_argument("--rounds", type=int, default=1, help="with --inpaint_draw: rounds of supplied-mask steps and drawn-mask steps, alternating")
+    ap.add_argument("--rounds", type=int, default=1, help="with --inpaint_draw: rounds of supplied-mask steps and drawn-mask steps, alternating; "
+                                                          "with --context-dropout: rounds of plain steps and dropout steps, alternating")
+    ap.add_argument("--context-dropout", type=float, default=0.0, help="drop every sample's text context with this probability, on the device")
     a = ap.parse_args()
     from text2protein_amd import losses, sde_lib, synth
     from text2protein_amd.config import load_config
@@ -78,7 +86,11 @@ def main():
         sde = (sde_lib.VPSDE if a.sde == "vp" else sde_lib.subVPSDE)(beta_min=cfg.model.beta_min, beta_max=cfg.model.beta_max, N=cfg.model.num_scales)
     if a.inpaint_draw and "inpainting" not in (cfg.model.condition or []):
         raise SystemExit("--inpaint_draw needs the inpainting condition (cond_length_inpainting.yml)")
+    if a.inpaint_draw and a.context_dropout > 0 and a.rounds > 1:
+        raise SystemExit("--rounds compares one pair of variants: --inpaint_draw or --context-dropout, not both")
     step_fn = losses.get_step_fn(sde, train=True, optimize_fn=losses.optimization_manager(cfg), inpaint_mask_draw=a.inpaint_draw)
+    ctxdrop_fn = losses.get_step_fn(sde, train=True, optimize_fn=losses.optimization_manager(cfg), inpaint_mask_draw=a.inpaint_draw,
+                                    context_dropout=a.context_dropout, context_dropout_draw="device")
     drawn_batch = dict({k: v for k, v in batch.items() if k != "mask_inpaint"}, lengths=[100] * B)      # no mask: the step draws it
     state = dict(model=model, optimizer=losses.get_optimizer(cfg, model.parameters()),
                  ema=losses.ExponentialMovingAverage(model.parameters(), decay=cfg.model.ema_rate), step=5000)
@@ -89,7 +101,7 @@ def main():
     def one_step():
         if blocks:
             model.set_ss_blocks(blocks, drop=None, p=0.2)       # per-batch data: set before every step, consumed by it
-        return step_fn(state, drawn_batch if a.inpaint_draw else batch, condition=cfg.model.condition)
+        return (ctxdrop_fn if a.context_dropout > 0 else step_fn)(state, drawn_batch if a.inpaint_draw else batch, condition=cfg.model.condition)
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -113,6 +125,19 @@ def main():
             seq += out
         dt = sorted(drawn)[len(drawn) // 2] / 1e3
         extra = {"supplied_ms_rounds": supplied, "drawn_ms_rounds": drawn, "supplied_median_ms": sorted(supplied)[len(supplied) // 2]}
+    elif a.context_dropout > 0 and a.rounds > 1:
+        for _ in range(a.warmup):
+            step_fn(state, batch, condition=cfg.model.condition)
+        plain, dropped = [], []
+        for _ in range(a.rounds):
+            plain.append(timed(lambda: step_fn(state, batch, condition=cfg.model.condition))[0] * 1e3)
+            d, out = timed(one_step)
+            dropped.append(d * 1e3)
+            seq += out
+        med = lambda v: sorted(v)[len(v) // 2]     # noqa: E731
+        dt = med(dropped) / 1e3
+        extra = {"plain_ms_rounds": plain, "ctxdrop_ms_rounds": dropped, "plain_median_ms": med(plain), "ctxdrop_median_ms": med(dropped),
+                 "plain_spread_ms": max(plain) - min(plain), "ctxdrop_spread_ms": max(dropped) - min(dropped)}
     else:
         dt, out = timed(one_step)
         seq += out
@@ -120,7 +145,7 @@ def main():
     out = {"metric": f"training step ({'fp32' if a.dtype == 'f32' else a.dtype})", "dtype": a.dtype, "sde": a.sde, "config": a.config, "batch": B, "L": L,
            "tokens": a.tokens, "ms_per_step": dt * 1e3, "samples_per_s": B / dt, "losses": [round(v, 5) for v in seq],
            "device_GiB": model.device_bytes() / 2 ** 30, "channels": C, "condition": list(cfg.model.condition or []), "ss_blocks": len(blocks),
-           "inpaint_draw": a.inpaint_draw, **extra}
+           "inpaint_draw": a.inpaint_draw, "context_dropout": a.context_dropout, **extra}
     tf = gf / dt / 1e3
     if a.dtype == "f32":
         out.update(tflops_f32=tf, frac_of_f32_peak=tf / PEAK_TFLOPS["f32"])
