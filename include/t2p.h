@@ -260,7 +260,9 @@ int t2p_op_ddim_update(const float* x, const float* eps_c, const float* eps_u, c
  * model->compute_dtype selects the products: T2P_DTYPE_F32 exact f32; T2P_DTYPE_F16 / T2P_DTYPE_BF16 16-bit operands with fp32
  * accumulation (residual-block 3x3 convolutions on the 16-bit implicit GEMM, every other product on t2p_op_tgemm16; input / head
  * convolutions, norms, softmax and elementwise work stay fp32).  Parameters, gradients, Adam moments, EMA and loss are fp32 in every
- * mode.  16-bit modes seed the backward pass with S dL/do (S = 2^round(log2(B C L L))) and divide S out of the gradient buffer, so
+ * mode.  The objective is the denoising score-matching loss under the VE (default), VP or sub-VP SDE (t2p_train_set_sde), or the DDIM
+ * sampler's noise-prediction loss (t2p_train_set_ploss).  16-bit modes seed the backward pass with S dL/do (S = 2^round(log2(B C L L)),
+ * or a power of two chosen on the device where the seed carries 1 / sigma) and divide S out of the gradient buffer, so
  * t2p_train_read(GRAD) and t2p_train_grad_buffer hold true gradients; every reduction that feeds a gradient or an update runs in a
  * fixed order (gradients and post-step state bitwise reproducible; the scalar loss is summed with double atomics), and
  * t2p_train_step / t2p_train_apply return an error and change nothing (parameters, moments, EMA, counters) when the loss or the
@@ -268,6 +270,8 @@ int t2p_op_ddim_update(const float* x, const float* eps_c, const float* eps_u, c
  * t2p_train_create      <- get_model + get_optimizer + ExponentialMovingAverage(model.parameters(), decay)
  *                          (score_sde_pytorch/utils.py:4-9, losses.py:26-36, models/ema.py:13-30; train.py builds `state` from them)
  * t2p_train_set_sde     <- the `sde` of get_sde_loss_fn / get_step_fn (losses.py:66,140): VE (the default), VP or sub-VP
+ * t2p_train_set_ploss   <- DiffusionSampler.p_loss / forward (sampler/diffusion_sampler.py:144-167) as the objective instead of an SDE loss:
+ *                          integer timesteps, the sampler's own sqrt_alpha_cumprod tables, l1 or l2 on the predicted noise
  * t2p_train_load_param  <- load_state_dict of one tensor; the EMA shadow starts as a copy (ema.py:28-29)
  * t2p_train_loss        <- loss_fn(model, batch, condition)      (losses.py:105-134), optionally with loss.backward()
  * t2p_train_step        <- step_fn(state, batch, condition), train=True (losses.py:165-176): zero_grad, loss, backward,
@@ -296,7 +300,8 @@ typedef struct t2p_train_batch {
   const uint8_t* mask_inpaint; /* device uint8 (batch, L, L):   batch["mask_inpaint"], needed with the inpainting condition      */
   const float* context;        /* device fp32 (batch, tokens, context_dim): llm.model.embed_tokens(caption tokens)              */
   int32_t batch, tokens;
-  const float* t;              /* device fp32 [batch] or NULL = t ~ U(t_eps, 1) drawn on the device (losses.py:106)              */
+  const float* t;              /* device fp32 [batch] or NULL = t ~ U(t_eps, 1) drawn on the device (losses.py:106); under          */
+                               /* t2p_train_set_ploss: the integer timesteps as floats, NULL = drawn in [0, timesteps)           */
   const float* z;              /* device fp32 (batch, C, L, L) or NULL = z ~ N(0, 1) drawn on the device (losses.py:107)         */
 } t2p_train_batch;
 
@@ -323,6 +328,32 @@ int t2p_train_get_step(const t2p_trainer* t, int64_t out3[3]);
  * NULL otherwise.  Refused with nothing changed: an unknown sde; beta_max <= beta_min or beta_min <= 0; VP without a table; sub-VP with
  * scale_by_sigma and num_scales < 1000 (the reference would index sigmas[trunc(999 t)] out of range). */
 int t2p_train_set_sde(t2p_trainer* t, int sde, double beta_min, double beta_max, const float* std_table);
+/* The DDIM sampler's training objective (sampler/diffusion_sampler.py:144-167: q_sample, p_loss, forward) instead of an SDE loss.
+ * loss_type: 1 = l1, 2 = l2.  The two tables are host float[timesteps] (DiffusionSampler's sqrt_alpha_cumprod and
+ * sqrt_one_minus_alphas_cumprod, built in float32 from whatever betas it was given) and are copied; timesteps is not tied to
+ * num_scales.  Call after t2p_train_create and before the first pass; the trainer keeps the objective.  Every pass then computes
+ *   t_b      batch->t[b] (device fp32 holding the integer timestep, exact below 2^24; the table index is clamped to [0, timesteps - 1],
+ *            range and integrality are the caller's to check), or with batch->t NULL drawn on the device: t_b = ((w >> 8) timesteps) >> 24,
+ *            w = word 0 of Philox4x32-10 under the trainer seed, training layout, counter b, stream 4096 loss_calls + 5 (csrc/philox.h)
+ *   x_noisy  sqrt_alphas_cumprod[t_b] x + sqrt_one_minus_alphas_cumprod[t_b] z  (:147-148; the product and sum of the VP step's kernel)
+ *   o        UNetModel.forward on (x_noisy, the INTEGER label t_b, context), train mode (Dropout_0 active) -- or eval mode under the EMA
+ *            in t2p_train_eval_loss -- with that method's own h / sigmas[t_b] when scale_by_sigma is set (ncsnpp.py:259-261; no SDE
+ *            conversion follows); score_out receives o (NCHW), the predicted noise
+ *   loss     r = o - z.  batch->mask_pair NULL: the reference's loss, mean |r| or mean r^2 over EVERY element (:156-159; padding included,
+ *            cond_flags ignored, nothing frozen; mask_inpaint is not read).  batch->mask_pair given (an extension, as `condition` in the
+ *            DDIM sampler: frozen entries stay clean in training as the sampler re-imposes them): the mask of the SDE loss (mask_pair x
+ *            the conditional mask of cond_flags, mask_inpaint, the drawn inpainting mask), x_noisy = where(mask, x_noisy, x), per sample
+ *            sum_mask |r| or r^2 over (num_elem + 1e-8), then the mean over samples (the form of losses.py:128-131: equal shards under data
+ *            parallelism reproduce the whole batch); ss block dropout is honoured.
+ * Context dropout, t2p_train_eval_loss, t2p_train_apply, the gradient buffer and t2p_train_copy work unchanged.  16-bit modes seed the
+ * backward pass with the host power of two S of the VE step (l1 seeds are +-S / ((num_elem + 1e-8) batch)) -- except under
+ * scale_by_sigma, where residual and seed carry 1 / sigmas[t_b] (up to 1 / sigma_min) and S is chosen on the device as under VP.
+ * Refused with nothing changed: after t2p_train_set_sde to VP or sub-VP; after a pass has run; a second call; a loss_type other than
+ * 1 or 2; timesteps < 1 or > 2^24; a NULL table; with scale_by_sigma, timesteps > num_scales (the reference would index sigmas out of
+ * range).  Afterwards every t2p_train_set_sde is refused.  The unmasked pass with a pending ss
+ * block list or inpaint-draw request returns an error, computes and changes nothing, and the request is cleared. */
+int t2p_train_set_ploss(t2p_trainer* t, int loss_type, int timesteps, const float* sqrt_alphas_cumprod,
+                        const float* sqrt_one_minus_alphas_cumprod);
 /* parity runs: keep-masks of Dropout_0 for the next pass, one device uint8 [batch][H][W][C] (NHWC, the block's own resolution and
  * width) per residual block in forward order; n = 0 returns to on-device Philox masks */
 int t2p_train_set_dropout_masks(t2p_trainer* t, const uint8_t* const* device_masks, int n);
@@ -432,6 +463,10 @@ int t2p_op_ss_block_dropout(const float* x, float* out, int batch, int C, int L,
  * t2p_train_set_inpaint_draw refuses (with L for max_res_num), B <= 0, a force_mode outside -1 .. 2. */
 int t2p_op_inpaint_mask_draw(const int32_t* host_len_lo_hi, int B, int L, double random_p, double contiguous_p, uint64_t seed, uint64_t stream_id,
                              int force_mode, uint8_t* flags_out, uint8_t* pair_out, int* mode_out_host, void* stream);
+/* the timestep draw of t2p_train_set_ploss alone, through the same device function: out_dev device int32 [B], out_dev[b] =
+ * ((w >> 8) timesteps) >> 24 with w = word 0 of the Philox block (key seed, training layout, counter b, stream stream_id; the trainer's:
+ * its seed and 4096 loss_calls + 5).  Refused: B <= 0, timesteps outside [1, 2^24], a NULL output. */
+int t2p_op_ploss_draw_t(uint64_t seed, uint64_t stream_id, int B, int timesteps, int32_t* out_dev, void* stream);
 /* the two kernels of t2p_train_set_context_drop alone, in place on x = device fp32 [batch][row_floats] (16-byte aligned): the decisions
  * (host_drop: host uint8 [batch], or NULL = drawn at probability p under the Philox key `seed` and stream `stream_id`, the trainer's:
  * its seed and 4096 loss_calls + 4), then row b of x becomes +0.0f where sample b is dropped -- stored, not multiplied, so an Inf or a

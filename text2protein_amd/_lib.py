@@ -171,6 +171,7 @@ SIGNATURES = {
     "t2p_train_set_step": (_i, [_vp, _i64, _i64, _i64]),
     "t2p_train_get_step": (_i, [_vp, C.POINTER(_i64)]),
     "t2p_train_set_sde": (_i, [_vp, _i, C.c_double, C.c_double, _vp]),
+    "t2p_train_set_ploss": (_i, [_vp, _i, _i, _vp, _vp]),
     "t2p_train_set_dropout_masks": (_i, [_vp, C.POINTER(_vp), _i]),
     "t2p_train_set_ss_blocks": (_i, [_vp, _vp, _i, _vp, C.c_double]),
     "t2p_train_set_inpaint_draw": (_i, [_vp, _vp, _i, C.c_double, C.c_double]),
@@ -191,6 +192,7 @@ SIGNATURES = {
     "t2p_op_ss_block_dropout": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, C.c_double, _u64, _u64, _vp, _vp]),
     "t2p_op_inpaint_mask_draw": (_i, [_vp, _i, _i, C.c_double, C.c_double, _u64, _u64, _i, _vp, _vp, C.POINTER(_i), _vp]),
     "t2p_op_context_drop": (_i, [_vp, _i, _i64, _vp, C.c_double, _u64, _u64, _vp, _vp]),
+    "t2p_op_ploss_draw_t": (_i, [_u64, _u64, _i, _i, _vp, _vp]),
     "t2p_op_groupnorm_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "t2p_op_layernorm_backward": (_i, [_vp, _vp, _vp, _i64, _i, _f, _vp, _vp, _vp, _vp]),
     "t2p_op_groupnorm_backward_form": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp]),

@@ -25,10 +25,12 @@
 //                                                                                                                                  word 1: start = ((w >> 8) (l - r)) >> 24
 //                                                                                                               (b + 1) 2^32 + 1 + j   word 0: the 32-bit key of residue j (the r lowest are masked)
 //                             context drop  trainer seed   training  rng_ctx() = 4096 calls + 4   -           sample b  word 0: the text context dropped when u < p
+//                             p_loss t      trainer seed   training  rng_ploss_t() = 4096 calls + 5  -        sample b  word 0: t = ((w >> 8) timesteps) >> 24 (set_ploss)
 //                             Dropout_0 k   trainer seed   training  rng_dropout(k)            -           quad q    4 words: element 4 q + j kept
 //                                                                      = 4096 calls + 16 + k                            when u_j >= p
 //   t2p_op_inpaint_mask_draw                caller's seed  training  caller's                     -           as the trainer's inpaint mask
 //   t2p_op_context_drop                     caller's seed  training  caller's                     -           as the trainer's context drop
+//   t2p_op_ploss_draw_t                     caller's seed  training  caller's                     -           as the trainer's p_loss t
 //   (calls = Trainer::loss_calls_, the number of loss calls completed before the running one.)
 //
 // Two known defects, recorded here and left as they are (fixing either changes drawn bits):

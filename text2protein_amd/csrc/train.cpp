@@ -1,4 +1,5 @@
-// Training step of the score network on MI355X, under the VE, VP or sub-VP SDE (set_sde).
+// Training step of the score network on MI355X, under the VE, VP or sub-VP SDE (set_sde) or under the DDIM sampler's
+// noise-prediction loss (set_ploss: sampler/diffusion_sampler.py:144-167).
 //
 // What the reference does in one step (score_sde_pytorch/losses.py:165-176): optimizer.zero_grad(); loss = loss_fn(...) (:105-134);
 // loss.backward(); optimize_fn (:41-49: warm-up on state['step'], clip_grad_norm_, Adam); state['step'] += 1; ema.update
@@ -272,6 +273,7 @@ int Trainer::set_step(int64_t step, int64_t adam_updates, int64_t ema_updates) {
 }
 int Trainer::get_step(int64_t out[3]) const { out[0] = step_; out[1] = adam_k_; out[2] = ema_k_; return T2P_OK; }
 int Trainer::set_sde(int sde, double beta_min, double beta_max, const float* std_table) {
+  T2P_REQUIRE(ploss_ == 0, "set_sde: this trainer has the p_loss objective (set_ploss) and keeps it");
   T2P_REQUIRE(sde == T2P_SDE_VE || sde == T2P_SDE_VP || sde == T2P_SDE_SUBVP, "set_sde: unknown SDE (T2P_SDE_VE, T2P_SDE_VP or T2P_SDE_SUBVP)");
   T2P_REQUIRE(beta_min > 0.0 && beta_max > beta_min, "set_sde: 0 < beta_min < beta_max");
   T2P_REQUIRE(sde != T2P_SDE_VP || std_table, "set_sde: the VP SDE needs sqrt_1m_alphas_cumprod (float[num_scales])");
@@ -285,6 +287,23 @@ int Trainer::set_sde(int sde, double beta_min, double beta_max, const float* std
     vp_std_ = tab;
   }
   sde_ = sde; beta_min_ = beta_min; beta_max_ = beta_max;
+  return T2P_OK;
+}
+int Trainer::set_ploss(int loss_type, int timesteps, const float* sqrt_alphas_cumprod, const float* sqrt_one_minus_alphas_cumprod) {
+  T2P_REQUIRE(ploss_ == 0, "set_ploss: this trainer has the p_loss objective already and keeps it");
+  T2P_REQUIRE(sde_ == T2P_SDE_VE, "set_ploss: this trainer was set to the VP or sub-VP SDE loss (set_sde) and keeps it");
+  T2P_REQUIRE(loss_calls_ == 0, "set_ploss: a pass has run; the objective is chosen after create and before the first pass");
+  T2P_REQUIRE(loss_type == 1 || loss_type == 2, "set_ploss: unknown loss_type (1 = l1, 2 = l2)");
+  T2P_REQUIRE(timesteps >= 1 && timesteps <= (1 << 24), "set_ploss: timesteps must lie in [1, 2^24] (integer labels exact in fp32, 24-bit draws)");
+  T2P_REQUIRE(!mc_.scale_by_sigma || timesteps <= mc_.num_scales,
+              "set_ploss: with scale_by_sigma the network divides by sigmas[t] (ncsnpp.py:259-261): timesteps <= num_scales");
+  T2P_REQUIRE(sqrt_alphas_cumprod && sqrt_one_minus_alphas_cumprod, "set_ploss: the tables sqrt_alphas_cumprod and sqrt_one_minus_alphas_cumprod (float[timesteps])");
+  float* tab = (float*)pool_.persistent((size_t)timesteps * 8);
+  if (!tab) return T2P_ERR_HIP;
+  T2P_HIP_CHECK(hipDeviceSynchronize());
+  T2P_HIP_CHECK(hipMemcpy(tab, sqrt_alphas_cumprod, (size_t)timesteps * 4, hipMemcpyHostToDevice));
+  T2P_HIP_CHECK(hipMemcpy(tab + timesteps, sqrt_one_minus_alphas_cumprod, (size_t)timesteps * 4, hipMemcpyHostToDevice));
+  ploss_tab_ = tab; ploss_T_ = timesteps; ploss_ = loss_type;
   return T2P_OK;
 }
 int Trainer::set_dropout_masks(const uint8_t* const* masks, int n) {
@@ -802,11 +821,15 @@ int Trainer::run_layers(const std::vector<LayerT>& ls, TT* h, TT* stemb, TT* ctx
   return T2P_OK;
 }
 
-// loss_fn (losses.py:105-134) on the parameters P; with `backward`, d loss / d P accumulates into Gr_
+// loss_fn (losses.py:105-134), or p_loss (diffusion_sampler.py:150-163) after set_ploss, on the parameters P; with `backward`,
+// d loss / d P accumulates into Gr_
 int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool train, bool backward, float* loss_dev, float* score_out) {
   const int B = b.batch, L = mc_.max_res_num, HW = L * L, Cx = mc_.num_channels, nf = mc_.nf;
-  T2P_REQUIRE(b.coords_6d && b.mask_pair && b.context && B > 0 && b.tokens > 0, "training batch");
-  T2P_REQUIRE(!(tc_.cond_flags & 4) || b.mask_inpaint || inp_pass_n_ > 0, "the inpainting condition needs batch.mask_inpaint");
+  // p_loss without a pair mask: the reference's loss as written (diffusion_sampler.py:150-163) -- every element counts, nothing is frozen
+  const bool unmasked = ploss_ != 0 && !b.mask_pair;
+  const int cond_flags = unmasked ? 0 : tc_.cond_flags;
+  T2P_REQUIRE(b.coords_6d && (b.mask_pair || unmasked) && b.context && B > 0 && b.tokens > 0, "training batch");
+  T2P_REQUIRE(!(cond_flags & 4) || b.mask_inpaint || inp_pass_n_ > 0, "the inpainting condition needs batch.mask_inpaint");
   T2P_REQUIRE(!(tc_.cond_flags & 2) || Cx >= 7, "the ss condition needs the 8-channel layout");
   Pc_ = P;
   drop_index_ = 0;
@@ -821,7 +844,12 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool tra
   // per sample: the std of the loss, the mean coefficient (VP / sub-VP), the time label and the signed scale that turns the network's
   // output into the score (VE: 1 or 1 / sigma; VP: -1 / std_table[label]; sub-VP: -1 / std; models/utils.py:138-171)
   float* mean_coef = nullptr; float* labels_f = nullptr;
-  if (sde_ == T2P_SDE_VE) {
+  if (ploss_) {                                   // the integer timestep, its two table entries, the integer label
+    mean_coef = tmp(B * 4);
+    if (!mean_coef) return T2P_ERR_HIP;
+    T2P_TRY(launch_ploss_prepare(b.t, B, ploss_T_, ploss_tab_, ploss_tab_ + ploss_T_, mc_.scale_by_sigma ? inv_sigma_ : nullptr, mc_.num_scales,
+                                 tc_.seed, rng_ploss_t(), t_dev, mean_coef, stdv, labels, scale, s_));
+  } else if (sde_ == T2P_SDE_VE) {
     T2P_TRY(launch_dsm_prepare(b.t, B, (float)tc_.t_eps, (float)mc_.sigma_min, (float)mc_.sigma_max, mc_.num_scales,
                                mc_.scale_by_sigma ? inv_sigma_ : nullptr, tc_.seed, rng_t(), t_dev, stdv, labels, scale, s_));
   } else {
@@ -848,7 +876,14 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool tra
   }
   // random_mask_batch (utils.py:15-60; train.py:176, :193): a batch without mask_inpaint and a request for this pass -- the mask is drawn
   // here and goes where batch.mask_inpaint goes
-  const uint8_t* mask_inpaint = b.mask_inpaint;
+  const uint8_t* mask_inpaint = unmasked ? nullptr : b.mask_inpaint;
+  const uint8_t* mask_pair = b.mask_pair;
+  if (unmasked) {
+    uint8_t* ones = (uint8_t*)tmp((size_t)B * HW);
+    if (!ones) return T2P_ERR_HIP;
+    T2P_HIP_CHECK(hipMemsetAsync(ones, 1, (size_t)B * HW, s_));
+    mask_pair = ones;
+  }
   if (inp_pass_n_ > 0) {
     uint8_t* drawn = (uint8_t*)tmp((size_t)B * L + (size_t)B * HW);      // [B][L] residue flags, then the [B][L][L] pair mask
     if (!drawn) return T2P_ERR_HIP;
@@ -856,7 +891,7 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool tra
                                      nullptr, s_));
     mask_inpaint = drawn + (size_t)B * L;
   }
-  T2P_TRY(launch_dsm_perturb(b.coords_6d, z, stdv, mean_coef, b.mask_pair, mask_inpaint, tc_.cond_flags, B, Cx, L, perturbed, mask, num_elem, s_,
+  T2P_TRY(launch_dsm_perturb(b.coords_6d, z, stdv, mean_coef, mask_pair, mask_inpaint, cond_flags, B, Cx, L, perturbed, mask, num_elem, s_,
                              ss_rows));
   // text-context dropout: the decisions of this pass, drawn here unless they were given.  batch.context itself stays as the caller gave
   // it; every cross-attention zeroes the dropped samples' rows of its projected K and V (st_block)
@@ -866,7 +901,7 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool tra
   T2P_ACT(x0, B, L, L, 8, false);
   T2P_TRY(launch_nchw_to_nhwc(perturbed, x0->p, B, Cx, HW, 8, s_));
   T2P_ACT(emb, B, 1, 1, nf, false);
-  T2P_TRY(launch_timestep_embedding(labels, labels_f, nullptr, emb->p, B, nf, s_));   // VP / sub-VP: the fractional label
+  T2P_TRY(launch_timestep_embedding(labels, labels_f, nullptr, emb->p, B, nf, s_));   // VP / sub-VP: the fractional label; p_loss: the integer
   TT *te1 = nullptr, *temb = nullptr;
   T2P_TRY(linear(emb, pre0_, &te1));
   T2P_TRY(linear(te1, pre1_, &temb));
@@ -917,14 +952,18 @@ int Trainer::forward_backward(const t2p_train_batch& b, const float* P, bool tra
     d_o = grad(o);
     if (!d_o) return T2P_ERR_HIP;
   }
-  T2P_TRY(launch_dsm_loss(o->p, 8, z, stdv, scale, mask, num_elem, B, Cx, L, loss_sum, d_o, 8, score_out, s_));
+  if (ploss_) T2P_TRY(launch_ploss_loss(ploss_ == 1, o->p, 8, z, scale, mask, num_elem, B, Cx, L, loss_sum, d_o, 8, score_out, s_));
+  else T2P_TRY(launch_dsm_loss(o->p, 8, z, stdv, scale, mask, num_elem, B, Cx, L, loss_sum, d_o, 8, score_out, s_));
   T2P_TRY(launch_dsm_finish(loss_sum, num_elem, B, loss_dev, s_));
   // 16-bit modes: seed the backward pass with S dL/do (S a power of two: exact in fp32) and divide S out of the flat gradient buffer.
   // VE: S = 2^round(log2(B C L L)), known on the host (std / sigma[label] is about 1, so the seed is about 2 r / (num_elem B)).
   // VP / sub-VP: the seed carries std |scale| = up to 1 / sigma_min with scale_by_sigma (the sigma table is indexed by a label that
   // grows with t) and a residual r of that size, so a fixed S overflows f16 at large t: S is chosen on the device as the largest
   // power of two with S max|dL/do| <= 64, the magnitude the VE seed has.
-  const bool dev_scale = backward && plumbing16_ && sde_ != T2P_SDE_VE;
+  // p_loss: r = o / sigmas[t] - z has no std / sigma ratio that stays near 1 -- with scale_by_sigma the residual and the seed both carry
+  // 1 / sigmas[t], up to 1 / sigma_min, and a fixed S overflows f16 at the last timesteps as under VP: S on the device there too; without
+  // scale_by_sigma the seed is 2 r / (num_elem B) or +-1 / (num_elem B) and the VE step's host S holds.
+  const bool dev_scale = backward && plumbing16_ && (sde_ != T2P_SDE_VE || (ploss_ != 0 && mc_.scale_by_sigma));
   const float S = !plumbing16_ ? 1.f : std::ldexp(1.f, (int)std::lround(std::log2((double)B * Cx * HW)));
   float* s2 = nullptr;                            // device pair {S, 1 / S} of the VP / sub-VP 16-bit step
   if (dev_scale) {
@@ -961,6 +1000,9 @@ int Trainer::loss(const t2p_train_batch& b, bool backward, bool use_ema, float* 
   T2P_REQUIRE(ss_pass_n_ == 0 || ss_max_sample_ < b.batch,
               "ss blocks: sample index " + std::to_string(ss_max_sample_) + " >= batch " + std::to_string(b.batch) +
                   "; nothing was computed or changed and the block list is cleared");
+  T2P_REQUIRE(!(ploss_ != 0 && !b.mask_pair) || (ss_pass_n_ == 0 && inp_request == 0),
+              "p_loss without mask_pair is the unmasked loss: it takes no ss block list and no inpaint draw; nothing was computed or changed "
+              "and the request is cleared");
   s_ = s;
   if (backward) last_loss_finite_ = false;        // the overflow guard trusts only a completed backward pass
   if (backward) T2P_HIP_CHECK(hipMemsetAsync(Gr_, 0, (size_t)total_ * 4, s));      // optimizer.zero_grad()

@@ -83,6 +83,9 @@ class Trainer {
   int set_dropout_masks(const uint8_t* const* masks, int n);
   // the SDE of the loss (get_sde_loss_fn's `sde`): T2P_SDE_VE (after build), T2P_SDE_VP (std_table: host float[num_scales]) or T2P_SDE_SUBVP
   int set_sde(int sde, double beta_min, double beta_max, const float* std_table);
+  // the DDIM sampler's objective instead of an SDE loss (sampler/diffusion_sampler.py:144-167): loss_type 1 = l1, 2 = l2; the two tables are
+  // host float[timesteps], copied.  Before the first pass, on a trainer that was not set to VP / sub-VP; the trainer keeps it
+  int set_ploss(int loss_type, int timesteps, const float* sqrt_alphas_cumprod, const float* sqrt_one_minus_alphas_cumprod);
   // block_dropout (losses.py:54-64, called at :106-107) of the NEXT loss / step / eval pass: host int32 [n][3] = (sample, start, end) and
   // the per-block decisions (host uint8 [n]) or nullptr = drawn on the device at probability p.  Consumed by that pass, then cleared
   int set_ss_blocks(const int32_t* host_blocks, int n, const uint8_t* host_drop, double p);
@@ -138,6 +141,8 @@ class Trainer {
   unsigned long long rng_inpaint() const { return (unsigned long long)(loss_calls_ * 4096 + 3); }
   // the context-dropout decisions of the running loss call (counter = the sample index); + 4 of the free ids
   unsigned long long rng_ctx() const { return (unsigned long long)(loss_calls_ * 4096 + 4); }
+  // the integer timesteps of the running loss call under the p_loss objective (counter = the sample index); + 5 of the free ids
+  unsigned long long rng_ploss_t() const { return (unsigned long long)(loss_calls_ * 4096 + 5); }
 
   // forward ops: each appends its backward to tape_
   TT* act(int B, int H, int W, int C, bool needs_grad = true);
@@ -174,6 +179,9 @@ class Trainer {
   int sde_ = T2P_SDE_VE;            // the SDE of the loss (set_sde)
   double beta_min_ = 0.0, beta_max_ = 0.0;
   float* vp_std_ = nullptr;         // VP: sqrt_1m_alphas_cumprod, float[num_scales] (the divisor of the score, models/utils.py:154)
+  int ploss_ = 0;                   // the p_loss objective (set_ploss): 0 none (the SDE loss), 1 l1, 2 l2
+  int ploss_T_ = 0;                 // its number of timesteps
+  float* ploss_tab_ = nullptr;      // device float[2][ploss_T_]: sqrt_alphas_cumprod, then sqrt_one_minus_alphas_cumprod
   int64_t step_ = 0, adam_k_ = 0, ema_k_ = 0, loss_calls_ = 0;
   int dt_ = DT_F32;                 // compute dtype of the products
   bool plumbing16_ = false;         // the 16-bit step's plumbing (16-bit modes, or an f32 trainer created under plan switch 48): every reduction

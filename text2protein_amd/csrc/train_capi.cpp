@@ -109,6 +109,14 @@ int t2p_train_set_sde(t2p_trainer* t, int sde, double beta_min, double beta_max,
   API_END
 }
 
+int t2p_train_set_ploss(t2p_trainer* t, int loss_type, int timesteps, const float* sqrt_alphas_cumprod,
+                        const float* sqrt_one_minus_alphas_cumprod) {
+  API_BEGIN
+  T2P_REQUIRE(t, "null trainer");
+  return t->impl.set_ploss(loss_type, timesteps, sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod);
+  API_END
+}
+
 int t2p_train_set_dropout_masks(t2p_trainer* t, const uint8_t* const* device_masks, int n) {
   API_BEGIN
   T2P_REQUIRE(t && n >= 0, "set_dropout_masks arguments");
@@ -382,6 +390,15 @@ int t2p_op_context_drop(float* x, int batch, int64_t row_floats, const uint8_t* 
     return T2P_ERR_HIP;
   }
   return T2P_OK;
+  API_END
+}
+
+// the integer timesteps of the p_loss objective alone, through the device function of the training pass
+int t2p_op_ploss_draw_t(uint64_t seed, uint64_t stream_id, int B, int timesteps, int32_t* out_dev, void* stream) {
+  API_BEGIN
+  T2P_REQUIRE(out_dev && B > 0, "ploss_draw_t arguments");
+  T2P_REQUIRE(timesteps >= 1 && timesteps <= (1 << 24), "ploss_draw_t: timesteps must lie in [1, 2^24]");
+  return launch_ploss_draw_t(B, timesteps, seed, stream_id, out_dev, (hipStream_t)stream);
   API_END
 }
 

@@ -136,6 +136,23 @@ int launch_dsm_loss(const float* o, long ldo, const float* z, const float* std, 
 // loss = mean_b loss_sum[b] / (num_elem[b] + 1e-8)
 int launch_dsm_finish(const double* loss_sum, const float* num_elem, int B, float* loss, hipStream_t s);
 
+// ---- the DDIM sampler's noise-prediction objective (sampler/diffusion_sampler.py:144-167: q_sample, p_loss, forward) ----------------------
+// per sample: the integer timestep t_b -- t_in[b] when given (fp32 holding an integer; clamped to [0, T - 1], NaN -> 0), else drawn:
+// t_b = ((w >> 8) T) >> 24 with w = word 0 of Philox4x32-10, training layout, counter b, stream id stream_id, key seed (T <= 2^24) --
+// then t_out[b] = labels[b] = t_b, mean_coef[b] = sqrt_ac[t_b], std[b] = sqrt_1mac[t_b] (device float[T] each): what
+// launch_dsm_perturb's mean-coefficient path and launch_timestep_embedding's integer-label path take; scale[b] = inv_sigma_table[t_b]
+// (device float[N], needs T <= N: UNetModel.forward's own division by sigmas[t], ncsnpp.py:259-261) or 1 without a table
+int launch_ploss_prepare(const float* t_in, int B, int T, const float* sqrt_ac, const float* sqrt_1mac, const float* inv_sigma_table, int N,
+                         unsigned long long seed, unsigned long long stream_id, float* t_out, float* mean_coef, float* std, int* labels,
+                         float* scale, hipStream_t s);
+// the draw alone, through the same device function: out [B] int32
+int launch_ploss_draw_t(int B, int T, unsigned long long seed, unsigned long long stream_id, int* out, hipStream_t s);
+// o: the head convolution's output NHWC [B][L L][ldo]; pred = scale[b] o, the predicted noise; r = pred - z; loss_sum[b] += sum mask |r|
+// (l1) or mask r^2 (double); d_o [B][L L][ld_do] = mask sign(r) (sign(0) = 0) or mask 2 r, times scale[b] / ((num_elem + 1e-8) B), pad
+// columns zero; pred_nchw (optional) = pred
+int launch_ploss_loss(int l1, const float* o, long ldo, const float* z, const float* scale, const unsigned char* mask, const float* num_elem,
+                      int B, int C, int L, double* loss_sum, float* d_o, long ld_do, float* pred_nchw, hipStream_t s);
+
 // ---- optimizer (losses.py:26-51: Adam, warm-up, clip_grad_norm_) and EMA (ema.py:32-49) over flat parameter buffers ------------------------
 // partial == nullptr: *out += sum g^2 with atomics (zero it first); else *out = sum g^2 in a fixed order, partial: 1024 doubles
 int launch_sumsq(const float* g, long n, double* partial, double* out, hipStream_t s);

@@ -1411,6 +1411,101 @@ int launch_dsm_finish(const double* loss_sum, const float* num_elem, int B, floa
   return T2P_OK;
 }
 
+// ---- the DDIM sampler's noise-prediction objective (sampler/diffusion_sampler.py:144-167) ----------------------------------------------
+// torch.randint(0, T) of diffusion_sampler.py:166 from one 24-bit Philox word: ((w >> 8) T) >> 24 lies in [0, T) for every T <= 2^24
+__device__ inline int ploss_draw_t(const int b, const int T, const unsigned long long seed, const unsigned long long stream_id) {
+  uint32_t c[4];
+  philox_counter_training(c, b, stream_id);
+  philox4x32_10(c, seed);
+  return (int)(((unsigned long long)(c[0] >> 8) * (unsigned long long)T) >> 24);
+}
+__global__ void ploss_prepare_kernel(const float* __restrict__ t_in, const int B, const int T, const float* __restrict__ sqrt_ac,
+                                     const float* __restrict__ sqrt_1mac, const float* __restrict__ inv_sigma_table,
+                                     const unsigned long long seed, const unsigned long long stream_id, float* __restrict__ t_out,
+                                     float* __restrict__ mean_coef, float* __restrict__ stdv, int* __restrict__ labels,
+                                     float* __restrict__ scale) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  int t;
+  if (t_in) {                                                   // clamped in float first: no conversion of a NaN or of a value past int
+    const float tf = t_in[b];
+    t = tf >= (float)(T - 1) ? T - 1 : tf > 0.f ? (int)tf : 0;
+  } else {
+    t = ploss_draw_t(b, T, seed, stream_id);
+  }
+  t = min(max(t, 0), T - 1);                                    // the table index: never out of bounds
+  t_out[b] = (float)t;
+  labels[b] = t;
+  mean_coef[b] = sqrt_ac[t];
+  stdv[b] = sqrt_1mac[t];
+  scale[b] = inv_sigma_table ? inv_sigma_table[t] : 1.f;        // UNetModel.forward's own h / sigmas[t] (ncsnpp.py:259-261)
+}
+int launch_ploss_prepare(const float* t_in, int B, int T, const float* sqrt_ac, const float* sqrt_1mac, const float* inv_sigma_table, int N,
+                         unsigned long long seed, unsigned long long stream_id, float* t_out, float* mean_coef, float* std, int* labels,
+                         float* scale, hipStream_t s) {
+  T2P_REQUIRE(B > 0 && T >= 1 && T <= (1 << 24) && sqrt_ac && sqrt_1mac && t_out && mean_coef && std && labels && scale, "ploss_prepare arguments");
+  T2P_REQUIRE(!inv_sigma_table || T <= N, "ploss_prepare: with a sigma table every timestep indexes it, timesteps <= num_scales");
+  hipLaunchKernelGGL(ploss_prepare_kernel, dim3(cdiv_l(B, 64)), dim3(64), 0, s, t_in, B, T, sqrt_ac, sqrt_1mac, inv_sigma_table, seed, stream_id,
+                     t_out, mean_coef, std, labels, scale);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+__global__ void ploss_draw_t_kernel(const int B, const int T, const unsigned long long seed, const unsigned long long stream_id,
+                                    int* __restrict__ out) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) out[b] = ploss_draw_t(b, T, seed, stream_id);
+}
+int launch_ploss_draw_t(int B, int T, unsigned long long seed, unsigned long long stream_id, int* out, hipStream_t s) {
+  T2P_REQUIRE(B > 0 && T >= 1 && T <= (1 << 24) && out, "ploss_draw_t arguments");
+  hipLaunchKernelGGL(ploss_draw_t_kernel, dim3(cdiv_l(B, 64)), dim3(64), 0, s, B, T, seed, stream_id, out);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+
+// grid (chunks, B), the geometry and the summation of dsm_loss_kernel
+template <bool L1>
+__global__ __launch_bounds__(256) void ploss_loss_kernel(const float* __restrict__ o, const long ldo, const float* __restrict__ z,
+                                                         const float* __restrict__ scale, const unsigned char* __restrict__ mask, const float* __restrict__ num_elem, const int B,
+                                                         const int C, const int HW, double* __restrict__ loss_sum, float* __restrict__ d_o,
+                                                         const long ld_do, float* __restrict__ pred_nchw) {
+  __shared__ double sh[4];
+  const int b = blockIdx.y;
+  const long per = (long)C * HW;
+  const float is = scale[b];
+  const float gscale = (L1 ? 1.f : 2.f) * is / ((num_elem[b] + 1e-8f) * (float)B);
+  double acc = 0.0;
+  for (long j = (long)blockIdx.x * 256 + threadIdx.x; j < per; j += (long)gridDim.x * 256) {
+    const int c = (int)(j / HW), p = (int)(j - (long)c * HW);
+    const long i = (long)b * per + j;
+    const float ov = o[((long)b * HW + p) * ldo + c] * is;
+    if (pred_nchw) pred_nchw[i] = ov;
+    const float r = ov - z[i];
+    const float m = mask[i] ? 1.f : 0.f;
+    acc += (double)((L1 ? fabsf(r) : r * r) * m);
+    if (d_o) {
+      const float dr = L1 ? (r > 0.f ? 1.f : r < 0.f ? -1.f : 0.f) : r;      // torch.sign: 0 at 0 (and at NaN, where the loss says so)
+      d_o[((long)b * HW + p) * ld_do + c] = gscale * dr * m;
+    }
+  }
+  acc = block_sum_256_d(acc, sh);
+  if (threadIdx.x == 0) unsafeAtomicAdd(loss_sum + b, acc);
+}
+int launch_ploss_loss(int l1, const float* o, long ldo, const float* z, const float* scale, const unsigned char* mask, const float* num_elem,
+                      int B, int C, int L, double* loss_sum, float* d_o, long ld_do, float* pred_nchw, hipStream_t s) {
+  T2P_REQUIRE(o && z && scale && mask && num_elem && loss_sum && B > 0 && B <= 65535 && C > 0 && L > 0 && ldo >= C, "ploss_loss arguments");
+  T2P_REQUIRE(!d_o || ld_do >= C, "ploss_loss: ld_do");
+  T2P_HIP_CHECK(hipMemsetAsync(loss_sum, 0, B * sizeof(double), s));
+  if (d_o && ld_do > C) T2P_HIP_CHECK(hipMemsetAsync(d_o, 0, (size_t)B * L * L * ld_do * sizeof(float), s));
+  const long per = (long)C * L * L;
+  const dim3 grid(std::min(64, cdiv_l(per, 256)), B);
+  if (l1)
+    hipLaunchKernelGGL(ploss_loss_kernel<true>, grid, dim3(256), 0, s, o, ldo, z, scale, mask, num_elem, B, C, L * L, loss_sum, d_o, ld_do, pred_nchw);
+  else
+    hipLaunchKernelGGL(ploss_loss_kernel<false>, grid, dim3(256), 0, s, o, ldo, z, scale, mask, num_elem, B, C, L * L, loss_sum, d_o, ld_do, pred_nchw);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+
 // =====================================================================================================================================
 // optimizer and EMA
 // =====================================================================================================================================

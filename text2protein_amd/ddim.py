@@ -18,8 +18,14 @@ The network is a VP-trained noise predictor called as ``model(x, t, context)`` w
   * ops   -- ``force_ops=True`` or any other callable: two model calls per step as the reference makes them, then
              t2p_op_ddim_update.
 
-Differences a caller can observe: ``cond=None`` raises (the engine needs a text context); training (``p_loss`` / ``forward``)
-lives in ``losses.py``; ``condition`` (the dict ``pc_sampler`` takes) is an extension -- frozen entries are re-imposed after every
+  p_loss(x_start, cond, t, noise) / forward(x, cond) / __call__                            :150-167
+
+Training: built on a ``losses.HipTrainModel`` the same object trains and samples -- ``ds(x, cond)`` is the reference's loss
+(integer timesteps, this sampler's tables, l1 or l2 on the noise) on the HIP train step, ``ds.ddim_sample(...)`` samples from the
+trainer's current parameters; ``losses.get_ploss_step_fn(ds, ...)`` is the whole ``step_fn``.  On any other model ``p_loss`` /
+``forward`` raise.  ``p_loss`` takes ``cond`` before ``t``, as every method of this class does.
+
+Differences a caller can observe: ``cond=None`` raises (the engine needs a text context); ``condition`` (the dict ``pc_sampler`` takes) is an extension -- frozen entries are re-imposed after every
 update, without it no length-conditioned or inpainting model could be sampled this way.
 """
 from __future__ import annotations
@@ -143,10 +149,44 @@ class DiffusionSampler:
                      float(self.sqrt_recipm1_alphas_cumprod[t]), 0., 0., 0., clip_scheme == 'static', True, 0, 0)
         return self.w * eps_c + (1 - self.w) * eps_u, x0
 
-    def p_loss(self, *_a, **_k):
-        raise T2PError("training runs through text2protein_amd.losses (get_step_fn / get_sde_loss_fn), not the DDIM sampler")
+    def p_loss(self, x_start, cond, t, noise=None, *, batch=None, backward=False, return_pred=False):
+        """diffusion_sampler.py:150-163 on the HIP train step, when ``self.model`` is a ``losses.HipTrainModel`` (which takes this sampler's
+        tables and ``loss_type`` on first use and keeps them): the loss as a float, or ``(loss, pred_noise)`` with ``return_pred``.
+        ``t``: integer timesteps [B] inside ``[0, timesteps)``, or None = drawn on the device; ``noise``: None = drawn on the device.
+        ``backward`` leaves d loss / d parameters in the model's gradient buffer (``model.apply()`` takes the optimizer step;
+        ``losses.get_ploss_step_fn`` is the whole ``step_fn``).  ``batch`` (an extension, like ``condition`` in ``ddim_sample``): a dict with
+        ``mask_pair`` and, under the inpainting condition, ``mask_inpaint`` selects the masked form -- the mask of the SDE loss, frozen
+        entries clean in ``x_noisy``, per-sample normalisation.  Without it: the reference's loss, every element counts.  Any other
+        model (a ``HipScoreModel``, a callable, None) cannot train here and is refused."""
+        from . import losses
+        if not isinstance(self.model, losses.HipTrainModel):
+            raise T2PError("training runs through text2protein_amd.losses: build the sampler on losses.get_train_model(config) "
+                           "(a HipTrainModel) to use p_loss / forward, or drive it with losses.get_ploss_step_fn")
+        if self.loss_type not in ('l1', 'l2'):
+            raise NotImplementedError(f'Loss type "{self.loss_type}" not implemented')
+        cfg = self.model.config
+        want = (int(cfg.data.num_channels), int(cfg.data.max_res_num), int(cfg.data.max_res_num))
+        if not torch.is_tensor(x_start) or x_start.dim() != 4 or tuple(x_start.shape[1:]) != want or x_start.shape[0] < 1:
+            raise T2PError(f"p_loss: x_start must be a tensor (B, {want[0]}, {want[1]}, {want[2]}), got "
+                           f"{tuple(x_start.shape) if torch.is_tensor(x_start) else type(x_start).__name__}")
+        if cond is None:
+            raise T2PError("cond is required: the engine needs a text context")
+        losses.check_ploss_t(t, self.timesteps, x_start.shape[0])
+        if noise is not None and tuple(noise.shape) != tuple(x_start.shape):
+            raise T2PError(f"p_loss: noise has shape {tuple(noise.shape)}, x_start {tuple(x_start.shape)}")
+        b = dict(coords_6d=x_start, context=cond)
+        if batch is not None:
+            if batch.get("mask_pair") is None:
+                raise T2PError("p_loss: `batch` selects the masked loss and must hold mask_pair")
+            b.update({k: batch[k] for k in ("mask_pair", "mask_inpaint") if batch.get(k) is not None})
+        self.model.set_ploss(self)
+        return self.model.loss(b, t=t, z=noise, backward=backward, return_score=return_pred)
 
-    forward = __call__ = p_loss
+    def forward(self, x, cond=None, **kw):
+        """diffusion_sampler.py:165-167: ``p_loss`` at timesteps drawn on the device (the trainer's Philox, not ``torch.randint``)."""
+        return self.p_loss(x, cond, None, **kw)
+
+    __call__ = forward
 
     # ---- sampling ------------------------------------------------------------------------------------------------------
     def _update(self, x, eps_c, eps_u, z, mask, x_initial, x_out, x_out2, x0_out, sqrt_recip, sqrt_recipm1, sqrt_an, c, sigma,

@@ -16,6 +16,10 @@ signatures, so a training script reads the same:
     step_fn = get_step_fn(sde, train=True, optimize_fn=optimization_manager(config))
     loss = step_fn(state, batch, condition=config.model.condition)
 
+The DDIM sampler's own objective (``DiffusionSampler.p_loss``, sampler/diffusion_sampler.py:144-167) is a second objective of the same
+step: ``get_ploss_step_fn(diffusion, train, ...)`` in place of ``get_step_fn(sde, train, ...)``, or ``diffusion.p_loss`` /
+``diffusion(x, cond)`` on a ``DiffusionSampler`` built on the model (``HipTrainModel.set_ploss``).
+
 There is no CPU fallback: without a HIP device ``HipTrainModel`` raises.
 """
 from __future__ import annotations
@@ -296,6 +300,21 @@ class HipTrainModel:
             check(self.lib.t2p_train_set_sde(self._h, _lib.SDE_SUBVP, key[1], key[2], None))
         self._sde = key
 
+    def set_ploss(self, diffusion):
+        """The DDIM sampler's own objective (``DiffusionSampler.p_loss``, diffusion_sampler.py:144-167) instead of an SDE loss: integer
+        timesteps in ``[0, diffusion.timesteps)``, the sampler's ``sqrt_alpha_cumprod`` / ``sqrt_one_minus_alphas_cumprod`` tables (float32,
+        from whatever ``betas`` it was built with; ``timesteps`` is not tied to ``model.num_scales``) and ``diffusion.loss_type`` ('l1' or
+        'l2').  ``DiffusionSampler.p_loss`` / ``get_ploss_step_fn`` call this on first use; a model stays with the objective it was given."""
+        key = _ploss_key(diffusion)
+        if self._sde is not None:
+            if self._sde != key:
+                raise T2PError(f"this model trains under {self._sde[0]}{self._sde[1:]}; it cannot switch to {key[0]}{key[1:]}")
+            return
+        a = diffusion.sqrt_alpha_cumprod.detach().to("cpu", torch.float32).contiguous()
+        s = diffusion.sqrt_one_minus_alphas_cumprod.detach().to("cpu", torch.float32).contiguous()
+        check(self.lib.t2p_train_set_ploss(self._h, key[1], key[2], C.c_void_p(a.data_ptr()), C.c_void_p(s.data_ptr())))
+        self._sde = key
+
     def set_dropout_masks(self, masks):
         """Parity runs: NHWC uint8 keep-masks (device tensors), one per residual block in forward order; None / [] = Philox."""
         masks = [m.to(self.device, torch.uint8).contiguous() for m in (masks or [])]
@@ -358,14 +377,18 @@ class HipTrainModel:
 
     def _batch(self, batch, t=None, z=None):
         dev = self.device
-        hold = [batch["coords_6d"].to(dev, torch.float32).contiguous(), batch["mask_pair"].to(dev, torch.uint8).contiguous(),
+        # under the p_loss objective a batch without mask_pair is the reference's unmasked loss (and its mask_inpaint is not passed on)
+        unmasked = self._sde is not None and self._sde[0] == "p_loss" and batch.get("mask_pair") is None
+        hold = [batch["coords_6d"].to(dev, torch.float32).contiguous(),
+                None if unmasked else batch["mask_pair"].to(dev, torch.uint8).contiguous(),
                 batch["context"].to(dev, torch.float32).contiguous()]
         tb = TrainBatch()
-        tb.coords_6d, tb.mask_pair, tb.context = hold[0].data_ptr(), hold[1].data_ptr(), hold[2].data_ptr()
+        tb.coords_6d, tb.mask_pair, tb.context = hold[0].data_ptr(), None if unmasked else hold[1].data_ptr(), hold[2].data_ptr()
         tb.batch, tb.tokens = hold[0].shape[0], hold[2].shape[1]
         if hold[2].shape[2] != self.config.model.context_dim:
             raise T2PError("context width differs from model.context_dim")
-        for key, val, dt in (("mask_inpaint", batch.get("mask_inpaint"), torch.uint8), ("t", t, torch.float32), ("z", z, torch.float32)):
+        for key, val, dt in (("mask_inpaint", None if unmasked else batch.get("mask_inpaint"), torch.uint8), ("t", t, torch.float32),
+                             ("z", z, torch.float32)):
             if val is not None:
                 v = val.to(dev, dt).contiguous()
                 hold.append(v)
@@ -447,6 +470,35 @@ def _sde_key(sde):
     if isinstance(sde, subVPSDE):
         return ("subVPSDE", float(sde.beta_0), float(sde.beta_1), int(sde.N))
     raise NotImplementedError(f"SDE class {sde.__class__.__name__} not yet supported.")
+
+
+_PLOSS_TYPES = {"l1": 1, "l2": 2}
+
+
+def _ploss_key(diffusion):
+    """("p_loss", loss type, timesteps, a checksum of the two tables) of a ``DiffusionSampler``; a ``loss_type`` other than 'l1' / 'l2'
+    raises the reference's error (diffusion_sampler.py:160-161)."""
+    import zlib
+    if diffusion.loss_type not in _PLOSS_TYPES:
+        raise NotImplementedError(f'Loss type "{diffusion.loss_type}" not implemented')
+    tabs = torch.stack([diffusion.sqrt_alpha_cumprod, diffusion.sqrt_one_minus_alphas_cumprod]).detach().to("cpu", torch.float32).contiguous()
+    if tabs.shape[1] != int(diffusion.timesteps):
+        raise T2PError(f"the sampler's tables hold {tabs.shape[1]} entries, timesteps is {diffusion.timesteps}")
+    return ("p_loss", _PLOSS_TYPES[diffusion.loss_type], int(diffusion.timesteps), zlib.crc32(tabs.numpy().tobytes()))
+
+
+def check_ploss_t(t, timesteps, batch_size=None):
+    """``t`` of ``p_loss``: None (drawn on the device) or an integer tensor [B] inside ``[0, timesteps)``; anything else raises ``T2PError``
+    before any native call (the kernel clamps the table index; range and integrality are checked here)."""
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or t.dtype not in (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64):
+        raise T2PError("p_loss: t must be an integer tensor of timesteps (torch.long), one per sample")
+    if t.dim() != 1 or (batch_size is not None and t.shape[0] != int(batch_size)):
+        raise T2PError(f"p_loss: t must have shape ({batch_size},), got {tuple(t.shape)}")
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= int(timesteps)):
+        raise T2PError(f"p_loss: t outside [0, {int(timesteps)}): min {int(t.min())}, max {int(t.max())}")
+    return t
 
 
 class _ParamHandle:
@@ -624,6 +676,54 @@ def get_sde_loss_fn(sde, train, eps=1e-5, block_dropout=0.2, block_dropout_draw=
     return loss_fn
 
 
+def _run_step(state, batch, condition, t, z, set_objective, train, optimize_fn, dist, world, block_dropout, block_dropout_draw,
+              inpaint_mask_draw, context_dropout, context_dropout_draw):
+    """The body of ``step_fn`` (losses.py:165-186) whatever the objective: ``set_objective(model)`` gives the model its SDE
+    (``get_step_fn``) or the DDIM sampler's p_loss (``get_ploss_step_fn``) on first use; everything after it is the same."""
+    model = state["model"]
+    set_objective(model)
+    if condition_flags(condition) != model._tc.cond_flags:
+        raise T2PError("`condition` differs from the model.condition the model was created with")
+    if "context" not in batch:
+        producer = state.get("llm")
+        if producer is None:
+            raise T2PError("the batch holds no `context`; put a TextContextProducer under state['llm']")
+        batch = dict(batch, context=producer(batch["caption"]))
+    if train:
+        if optimize_fn is not None:
+            optimize_fn(state["optimizer"], model.parameters(), step=state["step"])
+        _set_batch_ss_blocks(model, batch, condition, block_dropout, block_dropout_draw)
+        batch = _draw_batch_inpaint_mask(model, batch, condition, inpaint_mask_draw)
+        _request_context_drop(model, batch, context_dropout, context_dropout_draw)
+        prev = model.get_step()
+        model.set_step(state["step"])
+        if world == 1:
+            try:
+                loss = model.step(batch, t=t, z=z)            # zero_grad, loss, backward, optimize_fn, ema.update
+            except T2PError:
+                model.set_step(*prev)                         # a refused 16-bit step leaves the counters as they were
+                raise
+        else:
+            from . import distributed as D
+            try:
+                loss = model.loss(batch, t=t, z=z, backward=True)
+            except T2PError:
+                model.set_step(*prev)                         # a refused pass (a block outside the batch) changes nothing
+                raise
+            D.allreduce_mean_(model.grad_view(), dist)        # one collective over the whole gradient
+            loss = D.mean_over_ranks(loss, dist, model.device)
+            try:
+                model.apply()
+            except T2PError:
+                model.set_step(*prev)                         # as above: a refused 16-bit step leaves the counters as they were
+                raise
+        state["step"] += 1
+        return loss
+    _set_batch_ss_blocks(model, batch, condition, block_dropout, block_dropout_draw)
+    batch = _draw_batch_inpaint_mask(model, batch, condition, inpaint_mask_draw)
+    return model.eval_loss(batch, t=t, z=z)                  # ema.store / copy_to / loss / restore (losses.py:177-183)
+
+
 def get_step_fn(sde, train, optimize_fn=None, dist=None, block_dropout=0.2, block_dropout_draw="host", inpaint_mask_draw=None,
                 context_dropout=0.0, context_dropout_draw="device"):
     """losses.py:140-186.  ``block_dropout`` / ``block_dropout_draw`` / ``inpaint_mask_draw``: as in ``get_sde_loss_fn`` (each rank drops the blocks and draws the mask of its shard).  ``dist`` (an initialised ``torch.distributed`` module, text2protein_amd.distributed.init_process_group):
@@ -643,47 +743,35 @@ def get_step_fn(sde, train, optimize_fn=None, dist=None, block_dropout=0.2, bloc
     world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
 
     def step_fn(state, batch, condition=None, t=None, z=None):
-        model = state["model"]
-        model.set_sde(sde)
-        if condition_flags(condition) != model._tc.cond_flags:
-            raise T2PError("`condition` differs from the model.condition the model was created with")
-        if "context" not in batch:
-            producer = state.get("llm")
-            if producer is None:
-                raise T2PError("the batch holds no `context`; put a TextContextProducer under state['llm']")
-            batch = dict(batch, context=producer(batch["caption"]))
-        if train:
-            if optimize_fn is not None:
-                optimize_fn(state["optimizer"], model.parameters(), step=state["step"])
-            _set_batch_ss_blocks(model, batch, condition, block_dropout, block_dropout_draw)
-            batch = _draw_batch_inpaint_mask(model, batch, condition, inpaint_mask_draw)
-            _request_context_drop(model, batch, context_dropout, context_dropout_draw)
-            prev = model.get_step()
-            model.set_step(state["step"])
-            if world == 1:
-                try:
-                    loss = model.step(batch, t=t, z=z)            # zero_grad, loss, backward, optimize_fn, ema.update
-                except T2PError:
-                    model.set_step(*prev)                         # a refused 16-bit step leaves the counters as they were
-                    raise
-            else:
-                from . import distributed as D
-                try:
-                    loss = model.loss(batch, t=t, z=z, backward=True)
-                except T2PError:
-                    model.set_step(*prev)                         # a refused pass (a block outside the batch) changes nothing
-                    raise
-                D.allreduce_mean_(model.grad_view(), dist)        # one collective over the whole gradient
-                loss = D.mean_over_ranks(loss, dist, model.device)
-                try:
-                    model.apply()
-                except T2PError:
-                    model.set_step(*prev)                         # as above: a refused 16-bit step leaves the counters as they were
-                    raise
-            state["step"] += 1
-            return loss
-        _set_batch_ss_blocks(model, batch, condition, block_dropout, block_dropout_draw)
-        batch = _draw_batch_inpaint_mask(model, batch, condition, inpaint_mask_draw)
-        return model.eval_loss(batch, t=t, z=z)                  # ema.store / copy_to / loss / restore (losses.py:177-183)
+        return _run_step(state, batch, condition, t, z, lambda model: model.set_sde(sde), train, optimize_fn, dist, world, block_dropout,
+                         block_dropout_draw, inpaint_mask_draw, context_dropout, context_dropout_draw)
+
+    return step_fn
+
+
+def get_ploss_step_fn(diffusion, train, optimize_fn=None, dist=None, masked=True, block_dropout=0.2, block_dropout_draw="host",
+                      inpaint_mask_draw=None, context_dropout=0.0, context_dropout_draw="device"):
+    """``get_step_fn`` for the DDIM sampler's own objective (``DiffusionSampler.p_loss``, diffusion_sampler.py:144-167): ``diffusion`` is the
+    ``text2protein_amd.ddim.DiffusionSampler`` whose tables and ``loss_type`` the model takes on first use (``HipTrainModel.set_ploss``).
+    ``step_fn(state, batch, condition=None, t=None, z=None)``: ``t`` = integer timesteps in ``[0, diffusion.timesteps)`` or None = drawn
+    on the device, ``z`` = the noise or None.  Everything else -- optimize_fn, the per-batch requests, data-parallel training under
+    ``dist``, the evaluation loss under the EMA with ``train=False`` -- is ``get_step_fn``'s, through the same body.
+
+    ``masked=True`` (the default): the mask of the SDE loss (``batch["mask_pair"]`` x the conditional mask of ``condition``); frozen entries
+    reach the network clean, as ``ddim_sample(condition=...)`` re-imposes them.  ``masked=False``: the reference's loss as written, every
+    element counts; ``mask_pair`` / ``mask_inpaint`` are not passed on, and no block list or inpainting mask is requested."""
+    _ploss_key(diffusion)
+    _check_draw(block_dropout_draw)
+    _check_inpaint_draw(inpaint_mask_draw)
+    _check_context_dropout(context_dropout, context_dropout_draw)
+    context_dropout = float(context_dropout)
+    world = dist.get_world_size() if dist is not None and dist.is_initialized() else 1
+
+    def step_fn(state, batch, condition=None, t=None, z=None):
+        check_ploss_t(t, diffusion.timesteps, batch["coords_6d"].shape[0])
+        if not masked:
+            batch = {k: v for k, v in batch.items() if k not in ("mask_pair", "mask_inpaint", "ss_indices")}
+        return _run_step(state, batch, condition, t, z, lambda model: model.set_ploss(diffusion), train, optimize_fn, dist, world, block_dropout,
+                         block_dropout_draw, None if not masked else inpaint_mask_draw, context_dropout, context_dropout_draw)
 
     return step_fn
