@@ -507,6 +507,10 @@ int t2p_op_gemm(int dtype, const void* A, int a_f32, const void* Bw, void* C, in
  * the residual stream between blocks in f16 mode */
 int t2p_op_gemm_r16(int dtype, const void* A, int a_f32, const void* Bw, void* C, int c_f32, int M, int N, int K, int64_t lda,
                     int64_t ldb, int64_t ldc, const float* bias_n, const void* residual16, float alpha, void* stream);
+/* the feed-forward's first product with the GEGLU gate in the epilogue: A [M][K] and Bw [N][K] in the 16-bit compute dtype, the rows
+ * of Bw (and bias_n [N], optional) interleaved (value_j, gate_j); C [M][ldc >= N / 2] (compute dtype) = value * gelu_erf(gate).
+ * T2P_ERR_INVALID when the product does not take the fused epilogue */
+int t2p_op_gemm_geglu(int dtype, const void* A, const void* Bw, void* C, int M, int N, int K, int64_t ldc, const float* bias_n, void* stream);
 /* x: NHWC in the given layout; w: [Cout][3][3][Cin] compute dtype; out fp32 NHWC */
 int t2p_op_conv3x3(int dtype, const void* x, int a_f32, const void* w, const float* bias, float* out, int batch,
                    int H, int W, int Cin, int Cout, int upsample, void* stream);
@@ -727,6 +731,8 @@ int t2p_profile_begin(void);
  * WRONG results exist only in a library built with -DT2P_ABLATION (python -m text2protein_amd.build --ablation)
  * and are refused (status 1) by the product build. */
 int t2p_debug_set(int key, int value);
+/* launches of the row-resident K = 512 GEMM (plan switch 49) since the library was loaded: lets a test see which plan a launch took */
+int64_t t2p_debug_rowres_launches(void);
 /* 1 when the library was built with -DT2P_ABLATION (never the shipped one) */
 int t2p_built_with_ablation(void);
 int t2p_profile_end(double* out9);

@@ -130,6 +130,7 @@ SIGNATURES = {
                              _i, _i, _i, _vp]),
     "t2p_op_input_conv": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "t2p_op_gemm_r16": (_i, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _i64, _vp, _vp, _f, _vp]),
+    "t2p_op_gemm_geglu": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i64, _vp, _vp]),
     "t2p_op_conv3x3": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "t2p_op_groupnorm": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _f, _i, _i, _vp, _i, _vp]),
     "t2p_op_layernorm": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _f, _vp]),
@@ -147,6 +148,7 @@ SIGNATURES = {
     "t2p_op_philox_normal": (_i, [_vp, _i64, _u64, _u64, _vp]),
     "t2p_profile_begin": (_i, []),
     "t2p_debug_set": (_i, [_i, _i]),
+    "t2p_debug_rowres_launches": (_i64, []),
     "t2p_op_decode_6d": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "t2p_op_encode_6d": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "t2p_op_embedding_gather": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i, _vp, _vp]),

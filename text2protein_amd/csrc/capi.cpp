@@ -320,12 +320,41 @@ int t2p_op_ddim_update(const float* x, const float* eps_c, const float* eps_u, c
 }
 
 // ---- operators ------------------------------------------------------------------------------------
+// The op entries get bare weights: where launch_gemm would take the row-resident kernel (plan switch 49), its copy of the weights
+// is made here, on the launch's stream, into a buffer that grows as needed (the engine makes that copy once per load)
+static void* g_op_rf = nullptr;
+static size_t g_op_rf_alloc = 0;
+static int attach_op_rowres(GemmParams& p, hipStream_t stream) {
+  if (!gemm_rowres_planned(p) || p.ldb < 512 || p.ldb % 8 != 0) return T2P_OK;
+  const size_t bytes = (size_t)p.N * 1024;
+  if (g_op_rf_alloc < bytes) {
+    if (g_op_rf) { T2P_HIP_CHECK(hipDeviceSynchronize()); T2P_HIP_CHECK(hipFree(g_op_rf)); g_op_rf = nullptr; g_op_rf_alloc = 0; }
+    T2P_HIP_CHECK(hipMalloc(&g_op_rf, bytes));
+    g_op_rf_alloc = bytes;
+  }
+  T2P_TRY(launch_rowres_pack(p.dtype, p.Bw, p.ldb, g_op_rf, p.N, stream));
+  p.Bw_rf = g_op_rf;
+  return T2P_OK;
+}
+
 int t2p_op_gemm(int dtype, const void* A, int a_f32, const void* Bw, void* C, int c_f32, int M, int N, int K, int64_t lda,
                 int64_t ldb, int64_t ldc, const float* bias_n, const float* residual, float alpha, void* stream) {
   API_BEGIN
   GemmParams p;
   p.dtype = dtype; p.A0 = A; p.a_f32 = a_f32; p.C0 = K; p.lda0 = lda; p.Bw = Bw; p.ldb = ldb; p.M = M; p.N = N;
   p.bias_n = bias_n; p.R = residual; p.ldr = ldc; p.alpha = alpha; p.C = C; p.c_f32 = c_f32; p.ldc = ldc;
+  T2P_TRY(attach_op_rowres(p, (hipStream_t)stream));
+  return launch_gemm(p, (hipStream_t)stream);
+  API_END
+}
+
+int t2p_op_gemm_geglu(int dtype, const void* A, const void* Bw, void* C, int M, int N, int K, int64_t ldc, const float* bias_n, void* stream) {
+  API_BEGIN
+  GemmParams p;
+  p.dtype = dtype; p.A0 = A; p.a_f32 = 0; p.C0 = K; p.lda0 = K; p.Bw = Bw; p.ldb = K; p.M = M; p.N = N;
+  p.bias_n = bias_n; p.C = C; p.c_f32 = 0; p.ldc = ldc; p.geglu = 1;
+  T2P_REQUIRE(gemm_fuses_geglu(p), "gemm_geglu: the product does not take the fused GEGLU epilogue (16-bit LDS-DMA plans, N % 4 == 0, ldc % 2 == 0)");
+  T2P_TRY(attach_op_rowres(p, (hipStream_t)stream));
   return launch_gemm(p, (hipStream_t)stream);
   API_END
 }
@@ -351,6 +380,7 @@ int t2p_op_gemm_r16(int dtype, const void* A, int a_f32, const void* Bw, void* C
   p.dtype = dtype; p.A0 = A; p.a_f32 = a_f32; p.C0 = K; p.lda0 = lda; p.Bw = Bw; p.ldb = ldb; p.M = M; p.N = N;
   p.bias_n = bias_n; p.R = (const float*)residual16; p.r_lowp = 1; p.ldr = ldc; p.alpha = alpha; p.C = C; p.c_f32 = c_f32; p.ldc = ldc;
   T2P_TRY(attach_op_ws(p));
+  T2P_TRY(attach_op_rowres(p, (hipStream_t)stream));
   return launch_gemm(p, (hipStream_t)stream);
   API_END
 }
@@ -850,6 +880,8 @@ int t2p_op_apply_mask(float* x, const uint8_t* mask, const float* x_initial, int
   API_END
 }
 
+int64_t t2p_debug_rowres_launches(void) { return (int64_t)t2p::g_rowres_launches; }
+
 int t2p_debug_set(int key, int value) {
   if (key == 10) { g_op_ws_bytes = (size_t)value << 20; return T2P_OK; }
   if (key == 11) { set_gemm_force_nsplit(value); return T2P_OK; }
@@ -878,6 +910,11 @@ int t2p_debug_set(int key, int value) {
   if (key == 46) { t2p::g_attn_proj = value != 0; return T2P_OK; }
   if (key == 47) { set_gemm_dxs(value != 0); return T2P_OK; }
   if (key == 48) { t2p::g_train_plumbing16 = value != 0; return T2P_OK; }
+  if (key == 49) {
+    if (value < 0 || value > 2) { set_last_error("plan switch 49 takes 0 (off), 1 (the planner's choice) or 2 (wherever eligible)"); return T2P_ERR_INVALID; }
+    t2p::g_rowres = value;
+    return T2P_OK;
+  }
   if (key == 34) { set_gemm_a_norm(value != 0); return T2P_OK; }
   if (key == 32) { g_attn_merged = value != 0; return T2P_OK; }
   if (key == 33) { g_ffpo_merged = value != 0; return T2P_OK; }

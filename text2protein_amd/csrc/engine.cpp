@@ -538,6 +538,14 @@ int Engine::pack_frag(void** slot, const void* w, int N, int K) {
   return launch_sf_frag_major(cfg_.compute_dtype, w, *slot, N, K, pack_stream_);
 }
 
+// the row-resident GEMM's copy of a packed K = 512 projection (rowgemm.hip), on the stream of the running load: a refresh of the
+// weights on the device re-makes it from the re-packed matrix
+int Engine::pack_rowres(DevLinear* l) {
+  T2P_TRY(dest(&l->w_rf, (size_t)l->N * l->K * 2));
+  load_stats_[0] += (int64_t)l->N * l->K * 2; load_stats_[1] += (int64_t)l->N * l->K * 2; load_stats_[2] += 1;
+  return launch_rowres_pack(cfg_.compute_dtype, l->w, l->K, l->w_rf, l->N, pack_stream_);
+}
+
 int Engine::pack_linear(const std::string& wname, const std::string& bname, int N, int K, DevLinear* out, bool conv3x3, bool nin,
                         int force_dtype, int cin_pad) {
   const int dt = force_dtype >= 0 ? force_dtype : cfg_.compute_dtype;
@@ -723,6 +731,11 @@ int Engine::pack_weights() {
           T2P_TRY(pack_frag(&l.fm_ff1, l.ff1.w, 8 * ci, ci));
         }
       }
+      if (dt != DT_F32 && ci == 512) {
+        // the K = 512 projections the row-resident GEMM takes at the 32 x 32 level (plan switch 49)
+        for (DevLinear* pl : {&l.proj_in, &l.a1_qkv, &l.a1_out, &l.a2_q, &l.a2_out, &l.ff1})
+          if (pl->w && pl->K == 512 && pl->N % 64 == 0) T2P_TRY(pack_rowres(pl));
+      }
       if (dt != DT_F32 && ci % 64 == 0) {
         // proj_out(t + ff2(g)) = [W_po W_ff2 | W_po] [g ; t] + (W_po b_ff2 + b_po), the bias accumulated in double
         T2P_SRC(wpo, p + ".proj_out.weight", (int64_t)ci * ci);
@@ -836,7 +849,7 @@ int Engine::linear(const void* a, bool a_is_f32, const DevLinear& w, long rows, 
   GemmParams p;
   p.dtype = dtype();
   p.A0 = a; p.a_f32 = a_is_f32 || p.dtype == DT_F32; p.C0 = w.K; p.lda0 = w.K;
-  p.Bw = w.w; p.ldb = w.K;
+  p.Bw = w.w; p.ldb = w.K; p.Bw_rf = w.w_rf;
   p.M = (int)rows; p.N = w.N;
   p.bias_n = use_bias ? w.b : nullptr;
   p.R = residual; p.ldr = w.N; p.r_lowp = (residual && r_lowp) ? 1 : 0;
@@ -1450,7 +1463,7 @@ int Engine::st_block(Layer& L, const Act& x, Act* out, int B, hipStream_t s) {
     POOL_GET(g, void*, (size_t)rows * 4 * C * es);
     GemmParams p;
     p.dtype = dt; p.A0 = ln; p.a_f32 = dt == DT_F32; p.C0 = C; p.lda0 = C;
-    p.Bw = L.ff1.w; p.ldb = C; p.M = (int)rows; p.N = 8 * C; p.bias_n = L.ff1.b;
+    p.Bw = L.ff1.w; p.ldb = C; p.Bw_rf = L.ff1.w_rf; p.M = (int)rows; p.N = 8 * C; p.bias_n = L.ff1.b;
     p.C = g; p.c_f32 = 0; p.ldc = 4 * C; p.geglu = 1;
     T2P_TRY(attach_ws(p));
     StEntryArgs e;

@@ -60,6 +60,7 @@ struct DevLinear {      // weights [N][K] in compute dtype (+ fp32 bias)
   void* w = nullptr;
   float* b = nullptr;
   int N = 0, K = 0;     // K = taps * Cin for convolutions
+  void* w_rf = nullptr;  // K = 512 projections, 16-bit modes: the row-resident GEMM's copy of w (GemmParams::Bw_rf, launch_rowres_pack)
 };
 struct DevNorm {
   float* gamma = nullptr;
@@ -166,6 +167,7 @@ class Engine {
   const float* psrc(const std::string& name, int64_t numel);
   int pack(int kind, void* dst, int64_t off, int dtype, std::initializer_list<const float*> srcs, std::initializer_list<int64_t> dims);
   int pack_frag(void** slot, const void* w, int N, int K);
+  int pack_rowres(DevLinear* l);
   int pack_linear(const std::string& wname, const std::string& bname, int N, int K, DevLinear* out,
                   bool conv3x3 = false, bool nin = false, int force_dtype = -1, int cin_pad = 0);
   int pack_stack2(const std::string& w0, const std::string& b0, const std::string& w1, const std::string& b1,

@@ -24,12 +24,12 @@
 #include <vector>
 
 #include "t2p_common.h"
+#include "gemm_mfma.h"
+#include "t2p_kernels.h"
 
 namespace t2p {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 
 [[maybe_unused]] static constexpr int ROWB = 144;  // LDS row stride in bytes: 128 data + 16 pad
 
@@ -110,18 +110,10 @@ template <> struct Mma<f16_t> {
   }
 };
 
-typedef float f32x4_res_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2_res_t __attribute__((ext_vector_type(2)));
 // residual operand: fp32, or the compute dtype when GemmParams::r_lowp (element index, not bytes)
 template <typename TC> __device__ inline float res_load1(const float* R, long idx, int lowp) {
   if constexpr (sizeof(TC) == 2) { if (lowp) return to_f32(((const TC*)R)[idx]); }
   return R[idx];
-}
-template <typename TC> __device__ inline f32x4_res_t unpack4(u32x2_res_t u) {     // four 16-bit values -> fp32
-  TC e[4];
-  e[0] = __builtin_bit_cast(TC, (uint16_t)u.x); e[1] = __builtin_bit_cast(TC, (uint16_t)(u.x >> 16));
-  e[2] = __builtin_bit_cast(TC, (uint16_t)u.y); e[3] = __builtin_bit_cast(TC, (uint16_t)(u.y >> 16));
-  return (f32x4_res_t){to_f32(e[0]), to_f32(e[1]), to_f32(e[2]), to_f32(e[3])};
 }
 template <typename TC> __device__ inline float4 res_load4(const float* R, long idx, int lowp) {
   if constexpr (sizeof(TC) == 2) {
@@ -367,31 +359,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmParams p) {
 //     the same XCD and share its L2
 // Requirements (else v1 runs): 16-bit compute dtype, A in the compute dtype, C0 % 64 == 0 and
 // C1 % 64 == 0, M >= 256, N >= 64, every operand smaller than 2 GiB.
-typedef int v4i_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-#define T2P_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
-[[maybe_unused]] static constexpr unsigned DMA_OOB = 0x80000000u;   // >= any num_records we accept -> zeros
 
-// erf-GELU for the fused GEGLU epilogue (16-bit outputs only): Abramowitz-Stegun 7.1.26, |error| of
-// erf <= 1.5e-7 -- far below the fp16 / bf16 rounding of the result -- in a dozen VALU operations
-// instead of the branchy libm erff.
-__device__ inline float gelu_erf_fast(float g) {
-  const float x = g * 0.70710678118654752440f, ax = fabsf(x);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.f));
-  float q = fmaf(t, 1.061405429f, -1.453152027f);
-  q = fmaf(q, t, 1.421413741f);
-  q = fmaf(q, t, -0.284496736f);
-  q = fmaf(q, t, 0.254829592f);
-  const float e = __builtin_amdgcn_exp2f(-ax * ax * 1.44269504088896340736f);
-  const float erf_abs = fmaf(-q * t, e, 1.f);
-  return 0.5f * g * (1.f + copysignf(erf_abs, x));
-}
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-// two fp32 values rounded to the compute dtype, packed low / high
-template <typename TC> __device__ inline uint32_t pack2(float a, float b) {
-  const TC x = from_f32<TC>(a), y = from_f32<TC>(b);
-  return (uint32_t)__builtin_bit_cast(uint16_t, x) | ((uint32_t)__builtin_bit_cast(uint16_t, y) << 16);
-}
 
 // MODE 0: plain GEMM rows; 1: 3x3 convolution; 2: 3x3 convolution reading a half-resolution source
 //
@@ -404,23 +372,8 @@ template <int I> __device__ inline void lds_read_b128(u32x4_t& dst, unsigned add
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(I * 4096));
 }
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-template <typename TC> struct Mma16;
-template <> struct Mma16<bf16_t> {
-  __device__ static inline void run(const u32x4_t& a, const u32x4_t& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-  }
-};
-template <> struct Mma16<f16_t> {
-  __device__ static inline void run(const u32x4_t& a, const u32x4_t& b, f32x4_t& c) {
-    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
-  }
-};
 #if T2P_PART_DMA
 __device__ inline bool g_stagger_dbg(int dbg) { return (dbg & 128) == 0; }   // debug bit 128 turns the stagger off
-template <int I> __device__ inline void lds_read_b128_2k(u32x4_t& dst, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(I * 2048));
-}
 template <int I> __device__ inline void lds_read_b128_1k(u32x4_t& dst, unsigned addr) {
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(I * 1024));
 }
@@ -521,15 +474,6 @@ __device__ __forceinline__ void lean_slab(const float* sp, const __amdgpu_buffer
 }
 
 
-// buffer descriptor covering `bytes` from `base`: everything beyond reads as zero / is dropped on store.  Built from
-// readfirstlane'd scalars so that hipcc keeps it in SGPRs (no waterfall loop around the DMA).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, int bytes) {
-  const unsigned long long b = (unsigned long long)base;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b);
-  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
-  const int nb = __builtin_amdgcn_readfirstlane(bytes);
-  return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, nb, 0x00020000);
-}
 
 // Epilogue of the LDS-DMA kernels: the accumulators of a BM x BN tile (8 or 4 wavefronts, WM x WN) -> bias / time-embedding
 // bias / residual / GEGLU / GroupNorm column statistics -> C, staged through this wave's 16 KiB slice of the (idle) LDS ring.
@@ -769,10 +713,7 @@ __device__ __forceinline__ void dma_epilogue(const GemmParams& p, unsigned char*
 // [32 + 8 g, 32 + 8 g + 8) of its row: two 16-byte stores per 16-row tile in 16 bits, each instruction covering 16 rows
 // x 64 contiguous bytes -- no LDS round trip (the staged epilogue writes 256 KiB of accumulators per tile through a
 // 64 B/clk LDS store path and reads them back), half the store instructions, and the LDS ring stays free.
-__device__ __forceinline__ int hperm(int rho) {       // LDS row (0..63) of a wave's weight block -> channel of the block
-  const int j = rho >> 4, g = (rho >> 2) & 3, v = rho & 3;
-  return 32 * (j >> 1) + 8 * g + 4 * (j & 1) + v;
-}
+// (hperm: gemm_mfma.h)
 // sum over the 16 lanes of a DPP row (lane & 15), fixed order: every lane ends with the total
 __device__ __forceinline__ float row16_sum(float x) {
   x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
@@ -2672,6 +2613,15 @@ static int launch_thin_conv(const GemmParams& p, hipStream_t stream) {
   return launch_thin_conv_ch<TC, 128>(a, stream);           // 128 or 256 channels: one or two passes
 }
 
+// launch_gemm takes the row-resident kernel (rowgemm.hip), given its copy of the weights: switch 49 at 2: wherever it is eligible; at 1:
+// from 128 workgroups of 128 rows on, and where the plan it replaces is the 256 x 256 16x16x32 kernel, whose bits it reproduces
+bool gemm_rowres_planned(const GemmParams& p) {
+  if (!g_rowres || g_dbg || !dma_eligible(p) || !gemm_rowres_eligible(p)) return false;
+  const DmaPlan plan = dma_plan(p);
+  if (plan.nsplit != 1) return false;
+  return g_rowres == 2 || (p.M / 128 >= 128 && plan.geom == 1 && g_dma_ring == 2);
+}
+
 int launch_gemm(const GemmParams& p, hipStream_t stream) {
   const int vec = p.dtype == DT_F32 ? 4 : 8;
   const int Ctot = p.C0 + p.C1;
@@ -2733,6 +2683,24 @@ int launch_gemm(const GemmParams& p, hipStream_t stream) {
       T2P_HIP_CHECK(hipEventRecord(rec.a, stream));
     }
     const int rc = p.dtype == DT_BF16 ? launch_thin_conv<bf16_t>(p, stream) : launch_thin_conv<f16_t>(p, stream);
+    if (g_prof_on) {
+      T2P_HIP_CHECK(hipEventRecord(rec.b, stream));
+      g_prof.push_back(rec);
+    }
+    return rc;
+  }
+  if (p.Bw_rf && gemm_rowres_planned(p)) {
+    // the K = 512 projections on the row-resident kernel (rowgemm.hip): same results as the 256 x 256 plan, bit for bit
+    ProfRec rec;
+    if (g_prof_on) {
+      T2P_HIP_CHECK(hipEventCreate(&rec.a));
+      T2P_HIP_CHECK(hipEventCreate(&rec.b));
+      prof_shape(rec, p);
+      rec.flops = 2.0 * p.M * p.N * (double)p.C0; rec.kind = 1; rec.name = gemm_rowres_kernel_name(p.dtype);
+      rec.bytes = (double)p.M * p.C0 * 2 + (double)p.N * p.C0 * 2 + (double)p.M * (p.geglu ? p.N / 2 : p.N) * 2 + (p.R ? (double)p.M * p.N * 2 : 0.0);
+      T2P_HIP_CHECK(hipEventRecord(rec.a, stream));
+    }
+    const int rc = launch_gemm_rowres(p, stream);
     if (g_prof_on) {
       T2P_HIP_CHECK(hipEventRecord(rec.b, stream));
       g_prof.push_back(rec);

@@ -163,8 +163,16 @@ struct GemmParams {
   void* c_frag = nullptr;
   int frag_col0 = 0, frag_ns = 0;
   long frag_bstride = 0;
+  // optional: the copy of Bw ([N][512], ldb as above) that launch_rowres_pack made, for the row-resident kernel (rowgemm.hip);
+  // launch_gemm takes that kernel when the copy is there and gemm_rowres_planned(p)
+  const void* Bw_rf = nullptr;
 };
 bool gemm_writes_frag_major(const GemmParams& p);
+// the row-resident K = 512 kernel covers the launch (shape and epilogue) / launch_gemm would take it, given GemmParams::Bw_rf
+bool gemm_rowres_eligible(const GemmParams& p);
+bool gemm_rowres_planned(const GemmParams& p);
+extern long g_rowres_launches;
+extern int g_rowres;       // plan switch 49: 0 off, 1 the planner's choice (gemm_rowres_planned, gemm.hip), 2 wherever eligible
 
 int launch_gemm(const GemmParams& p, hipStream_t stream);
 bool gemm_fuses_col_stats(const GemmParams& p);

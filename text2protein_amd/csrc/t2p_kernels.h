@@ -261,6 +261,12 @@ bool st_entry_eligible(const StEntryArgs& a);
 int launch_st_entry(const StEntryArgs& a, hipStream_t s);
 // out = W [N][K] (16-bit, row-major) re-ordered so that every MFMA fragment of 16 rows x 32 K is 1 KiB contiguous (same size)
 int launch_sf_frag_major(int dtype, const void* W, void* out, int N, int K, hipStream_t s);
+// ---- row-resident GEMM for the K = 512 projections (rowgemm.hip; plan switch 49, gemm_rowres_eligible in t2p_common.h) ---------------
+// p.Bw_rf = the copy launch_rowres_pack made of the weights: piece (slice s, 32-deep step t, column tile j, lane l) of 16 bytes at
+// (((s 16 + t) 4 + j) 64 + l) 16 holds W[64 s + hperm(16 j + l % 16)][32 t + 8 (l / 16) .. + 8) -- what lane l feeds the MFMA
+int launch_gemm_rowres(const GemmParams& p, hipStream_t s);
+const char* gemm_rowres_kernel_name(int dtype);
+int launch_rowres_pack(int dtype, const void* W, long ldb, void* out, int N, hipStream_t s);   // W [N][ldb] 16-bit, K = 512; out N x 512
 bool small_conv_eligible(const SmallConvArgs& a);
 int launch_small_conv_gn(const SmallConvArgs& a, hipStream_t s);
 

@@ -354,4 +354,26 @@ int launch_weight_pack(const WeightPack& pack, hipStream_t s) {
   }
 }
 
+// ---- the row-resident GEMM's weights (rowgemm.hip) --------------------------------------------------------------------------------
+// A packed 16-bit matrix [N][ldb] with K = 512 re-ordered (values moved, not converted) so that what a wavefront feeds one
+// v_mfma_f32_16x16x32 -- 16 permuted channels x 32 k, 16 bytes per lane -- is 1 KiB contiguous, and the four column tiles of a
+// 32-deep step follow one another: 16-byte piece ((slice 16 + step) 4 + j) 64 + lane.  Made once per load of the weights.
+__global__ __launch_bounds__(256) void rowres_pack_kernel(const uint4* __restrict__ W, long ldb8, uint4* __restrict__ out, long npieces) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= npieces) return;
+  const int lane = (int)(i & 63), j = (int)((i >> 6) & 3), step = (int)((i >> 8) & 15);
+  const long slice = i >> 12;
+  // MFMA row 16 j + (lane & 15) of the slice is channel hperm(.) (gemm_mfma.h), written out here: r = lane & 15 -> g = r / 4, v = r % 4
+  const int r = lane & 15, ch = 32 * (j >> 1) + 8 * (r >> 2) + 4 * (j & 1) + (r & 3);
+  out[i] = W[(slice * 64 + ch) * ldb8 + 4 * step + (lane >> 4)];
+}
+int launch_rowres_pack(int dtype, const void* W, long ldb, void* out, int N, hipStream_t s) {
+  T2P_REQUIRE(W && out && N > 0 && N % 64 == 0 && ldb >= 512 && ldb % 8 == 0 && (dtype == DT_F16 || dtype == DT_BF16), "rowres_pack arguments");
+  T2P_REQUIRE(((uintptr_t)W % 16) == 0 && ((uintptr_t)out % 16) == 0, "rowres_pack: 16-byte aligned matrices");
+  const long n = (long)N * 64;                           // 16-byte pieces of N x 512 16-bit values
+  hipLaunchKernelGGL(rowres_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint4*)W, ldb / 8, (uint4*)out, n);
+  T2P_HIP_CHECK(hipGetLastError());
+  return T2P_OK;
+}
+
 }  // namespace t2p
