@@ -711,6 +711,27 @@ int t2p_op_decode_6d(const float* x, int batch, int channels, int L, float* clip
  * than 0 / 1, blocks with channels = 5, any other channel count.  nres is read back on the host: the call synchronises the stream. */
 int t2p_op_encode_6d(const float* xyz, const int32_t* nres, const uint8_t* atom_ok, int batch, int channels, int L,
                      const int32_t* host_blocks, int n_blocks, float* coords_6d, uint8_t* mask_pair, void* stream);
+/* Backbones from decoded maps, in place of the reference's PyRosetta stage (sampling_rosetta.py:98-160) -- restraint-free: known pairs
+ * (dist < known_below, upper triangle), geodesic completion, classical MDS, stress_steps refinement steps on the Cb trace, N / CA / C
+ * from phi, theta and the featuriser's virtual-Cb identity, the mirror image told apart by chain closure.  absval =
+ * (batch, 4, L*L) fp32 and lengths = (batch) int32, both on the device, as t2p_op_decode_6d writes them; L <= 512.  Outputs, device:
+ * xyz = (batch, L, 3, 3) fp32, zero past lengths[b]; status[b] = 0 ok, 1 when the known-pair graph is disconnected or a residue had
+ * fewer than 3 neighbours (dist <= 12) or a singular system -- such a residue takes the offsets of the nearest framed residue and
+ * placed[b * L + i] = 1 -- and -1 for an improper mask (coordinates zero); diag = (batch, 16) double: hand kept (0 = the embedding whose
+ * axes rise along the chain, 1 = its mirror), closure error mean | |C_i - N_i+1| - 1.329 | of hand 0 and of hand 1, stress rms over the
+ * known pairs, the four restraint scores (dist, omega, theta, phi) and their four counts as t2p_op_restraint_score gives them,
+ * unreachable pairs, the three leading eigenvalues.  Every output is finite.  workspace = t2p_op_fold_ws(batch, L) bytes on the device
+ * (-1: L out of range).  Everything is enqueued on `stream`; nothing is read back. */
+int64_t t2p_op_fold_ws(int batch, int L);
+int t2p_op_fold_6d(const float* absval, const int32_t* lengths, int batch, int L, float known_below, int stress_steps, float dist_std,
+                   float angle_std, float* xyz, int32_t* status, uint8_t* placed, double* diag, void* workspace, int64_t workspace_bytes,
+                   void* stream);
+/* The reference's restraint set (load_constraints, rosetta_min/utils.py:119-206) scored on given backbones xyz = (batch, L, 3, 3) with
+ * the harmonic forms Rosetta applies, in double, Cb being the virtual Cb: out8 = (batch, 8) double = sums over dist (i < j,
+ * 0 < d <= 12, ((|Cb_i - Cb_j| - d) / dist_std)^2), omega (i < j, omega != 0, d <= 12, circular), theta (ordered pairs a != b with
+ * d[a][b] <= 12, circular) and phi (the same pairs, harmonic), angle_std in degrees, then the four counts.  Workspace as above. */
+int t2p_op_restraint_score(const float* xyz, const float* absval, const int32_t* lengths, int batch, int L, float dist_std, float angle_std,
+                           double* out8, void* workspace, int64_t workspace_bytes, void* stream);
 /* text context = embed_tokens(ids), sampling_6d.py:134-137: out[(b,t)][:] = table[ids[(b,t)]][:] as fp32; the table
  * ([vocab][dim], fp32 / bf16 / f16 by table_dtype) stays resident.  *bad_flag (device int, zeroed by the caller) is
  * set to 1 when an id falls outside [0, vocab). */

@@ -16,6 +16,10 @@ Differences, all at the edges of the hot path:
     synthetic (``--context synthetic``).
   * ``--decode`` additionally writes ``decoded_<id>.npz`` per sample: the reference's first folding stage
     (sampling_rosetta.py:69-96: mask rounding, crop, clip, inverse scaling) done on the device.
+  * ``--fold`` (implies ``--decode``) additionally folds every decoded sample to an N / CA / C backbone on the device
+    (text2protein_amd/fold.py: restraint-free, in place of the PyRosetta stage of sampling_rosetta.py:98-160) and writes
+    ``folded_<id>.pdb`` and ``fold_<id>.json`` (status, hand, closure errors, stress, restraint scores); one line is printed per
+    chain whose status is not 0.
   * ``--pdb FILE [--chain A] [--mask_info 1:5,10:15] [--sse LETTERS|FILE]``: the conditions of ``config.model.condition``
     from one chain of a PDB file (utils.py:122-137).  The reference goes through biotite there (and is broken, SURVEY.md 2
     row 10); here the backbone is read by a small reader of our own and featurised on the GPU (text2protein_amd/encode.py:
@@ -88,6 +92,9 @@ def main():
                              "builds from --pdb, utils.py:84-137): a torch file holding {'coords_6d': (B or 1, C, L, L) in "
                              "[-1, 1], 'lengths': ints or 'aa_str': strings}, or the word 'synthetic' (U(-1, 1) maps, 100 residues)")
     parser.add_argument("--decode", action="store_true", help="also write decoded_<id>.npz (sampling_rosetta.py:69-96)")
+    parser.add_argument("--fold", action="store_true",
+                        help="also fold every decoded sample to an N / CA / C backbone on the GPU (text2protein_amd/fold.py; implies "
+                             "--decode): folded_<id>.pdb and fold_<id>.json (status, hand, closure, stress, restraint scores)")
     parser.add_argument("--gpus", type=int, default=1, help="start this many ranks (one per GPU) when not under torch.distributed.run")
     parser.add_argument("--global_batch_norm", action="store_true",
                         help="Langevin batch means over every rank's chains (the reference's DataParallel semantics)")
@@ -303,7 +310,7 @@ def main():
                 suffix = f"_{it}" if args.n_iter > 1 else ""
                 with open(workdir.joinpath(f"sampled_{sid}{suffix}.pkl"), "wb") as f:
                     pkl.dump(generated[i].unsqueeze(0), f)
-            if args.decode:
+            if args.decode or args.fold:
                 import numpy as np
                 from text2protein_amd.decode import NAMES, decode_6d_batch
                 lengths, clipped, absval = decode_6d_batch(sample)
@@ -318,6 +325,21 @@ def main():
                         arrs[nm] = clipped[i, c, :Lb * Lb].reshape(Lb, Lb).cpu().numpy()
                         arrs[nm + "_abs"] = absval[i, c, :Lb * Lb].reshape(Lb, Lb).cpu().numpy()
                     np.savez(workdir.joinpath(f"decoded_{sid}{suffix}.npz"), **arrs)
+                if args.fold:
+                    import json
+                    from text2protein_amd import fold as F
+                    xyz, status, placed, diag = F.fold_maps_batch(absval, lengths)
+                    xyz = xyz.cpu().numpy()
+                    for i, (sid, d) in enumerate(zip(out_ids, F.diagnostics(status, placed, diag, lengths))):
+                        if d["status"] < 0:         # reported above
+                            continue
+                        suffix = f"_{it}" if args.n_iter > 1 else ""
+                        F.write_backbone_pdb(workdir.joinpath(f"folded_{sid}{suffix}.pdb"), xyz[i, :d["L"]])
+                        with open(workdir.joinpath(f"fold_{sid}{suffix}.json"), "w") as f:
+                            json.dump(d, f)
+                        if d["status"] != 0:
+                            print(f"sample {sid}: fold status {d['status']} ({d['unreachable_pairs']} unreachable pairs, "
+                                  f"{len(d['placed'])} residues placed without a frame of their own)")
             print(f"[{it + 1} / {args.n_iter}] save samples to {workdir} ({n} score evaluations per chain)")
     if dist is not None:
         dist.destroy_process_group()

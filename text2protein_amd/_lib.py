@@ -151,6 +151,10 @@ SIGNATURES = {
     "t2p_debug_rowres_launches": (_i64, []),
     "t2p_op_decode_6d": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "t2p_op_encode_6d": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    # backbones from decoded maps (csrc/fold.hip)
+    "t2p_op_fold_ws": (_i64, [_i, _i]),
+    "t2p_op_fold_6d": (_i, [_vp, _vp, _i, _i, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "t2p_op_restraint_score": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _i64, _vp]),
     "t2p_op_embedding_gather": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     "t2p_profile_end": (_i, [C.POINTER(C.c_double)]),
     "t2p_profile_dominant": (_i, [C.POINTER(C.c_double), C.c_char_p, C.c_int]),

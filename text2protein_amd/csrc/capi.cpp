@@ -867,6 +867,25 @@ int t2p_op_encode_6d(const float* xyz, const int32_t* nres, const uint8_t* atom_
   API_END
 }
 
+int64_t t2p_op_fold_ws(int batch, int L) { return (int64_t)fold6d_workspace_bytes(batch, L); }
+
+int t2p_op_fold_6d(const float* absval, const int32_t* lengths, int batch, int L, float known_below, int stress_steps, float dist_std,
+                   float angle_std, float* xyz, int32_t* status, uint8_t* placed, double* diag, void* workspace, int64_t workspace_bytes,
+                   void* stream) {
+  API_BEGIN
+  return launch_fold6d(absval, lengths, batch, L, known_below, stress_steps, dist_std, angle_std, xyz, status, placed, diag, workspace,
+                       (long)workspace_bytes, (hipStream_t)stream);
+  API_END
+}
+
+int t2p_op_restraint_score(const float* xyz, const float* absval, const int32_t* lengths, int batch, int L, float dist_std, float angle_std,
+                           double* out8, void* workspace, int64_t workspace_bytes, void* stream) {
+  API_BEGIN
+  return launch_restraint_score(xyz, absval, lengths, batch, L, dist_std, angle_std, out8, 8, workspace, (long)workspace_bytes,
+                                (hipStream_t)stream);
+  API_END
+}
+
 int t2p_op_embedding_gather(const void* table, int table_dtype, const int32_t* ids, float* out, int64_t n_tokens, int dim, int vocab,
                             int32_t* bad_flag, void* stream) {
   API_BEGIN

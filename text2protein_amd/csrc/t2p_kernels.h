@@ -284,6 +284,17 @@ int launch_decode6d(const float* x, int B, int C, int L, float* clipped, float* 
 int launch_encode6d(const float* xyz, const int* nres, const unsigned char* atom_ok, int B, int C, int L, const int* blocks, const int* pairs,
                     int npairs, float* coords_6d, unsigned char* mask_pair, hipStream_t s);
 int launch_embedding_gather(const void* table, int dtype, const int* ids, float* out, long ntok, int dim, int vocab, int* bad, hipStream_t s);
+// ---- after the decode: backbones from the maps (fold.hip) ----
+// absval / lengths as launch_decode6d writes them -> xyz [B][L][3][3] (N, CA, C), status [B] (0 ok, 1 degraded, -1 improper mask),
+// placed [B][L] (1 = residue without a frame of its own), diag [B][16] double.  The geodesic matrix of a chain stays in LDS up to
+// FOLD_LDS_MAX residues per map side and lives in the workspace above; FOLD_MAX_L bounds the coordinate arrays kept in LDS.
+constexpr int FOLD_LDS_MAX = 128, FOLD_MAX_L = 512;
+long fold6d_workspace_bytes(int B, int L);           // -1 when L is out of range
+int launch_fold6d(const float* absval, const int* lengths, int B, int L, float known_below, int stress_steps, float dist_std, float angle_std_deg,
+                  float* xyz, int* status, unsigned char* placed, double* diag, void* workspace, long workspace_bytes, hipStream_t s);
+// the four restraint sums and their counts of given backbones: out[b * stride + 0..7] (double)
+int launch_restraint_score(const float* xyz, const float* absval, const int* lengths, int B, int L, float dist_std, float angle_std_deg,
+                           double* out, int stride, void* workspace, long workspace_bytes, hipStream_t s);
 
 // ---- weight packing on the device (weightpack.hip) -----------------------------------------------------------------------------
 // One packing = one kind applied to fp32 sources, written to dst in `dtype`.  Engine::pack_weights decides which packings a network
