@@ -726,6 +726,35 @@ int64_t t2p_op_fold_ws(int batch, int L);
 int t2p_op_fold_6d(const float* absval, const int32_t* lengths, int batch, int L, float known_below, int stress_steps, float dist_std,
                    float angle_std, float* xyz, int32_t* status, uint8_t* placed, double* diag, void* workspace, int64_t workspace_bytes,
                    void* stream);
+/* TM-align on the device, what the reference does with its backbones next: tm/TMalign.py:36-61 (tm_score, max_min_avg_tm_score),
+ * :63-160 (train_gen_tm_compare), utils.py:150-158 (run_tmalign, one subprocess of tm/TMalign.cpp per pair) and play.py:49-61.  The
+ * default path of TMalign.cpp for n_pairs pairs of CA traces, one workgroup per pair, in double.
+ *   xyz_a = (n_a, La, atoms_a, 3), xyz_b = (n_b, Lb, atoms_b, 3) fp32 on the device; atoms = 3: the N / CA / C layout of t2p_op_fold_6d,
+ *   of which atom 1 is read; atoms = 1: a bare CA trace.  len_a (n_a), len_b (n_b) int32; nothing past len[c] is read.
+ *   pairs = (n_pairs, 2) int32 on the device (index into a, index into b), or NULL for all n_a x n_b pairs in row-major order.
+ * Chain a is TM-align's Chain_1, the one superimposed; chain b is Chain_2.  Outputs, device:
+ *   out8[p] = TM-score normalised by len_a, by len_b, RMSD of the pairs within score_d8 (rmsd0), their count n_ali8, d0 for len_a, d0
+ *   for len_b, the search stage's TMmax, the index 0..4 of the seed that produced the final alignment (get_initial, get_initial_ss,
+ *   get_initial5, get_initial_ssplus, get_initial_fgt);
+ *   b2a = (n_pairs, Lb) or NULL: for each residue of b the aligned residue of a among the pairs within score_d8 (the alignment
+ *   TM-align prints), else -1; -1 past len_b;
+ *   rot12 = (n_pairs, 12) or NULL: t[3] then u[3][3] of the superposition of a onto b that belongs to the score normalised by len_b
+ *   (what TM-align's -m prints);
+ *   status[p] = 0, or 1 when a chain of the pair is shorter than 5 or longer than TM_MAX_L = 256 residues (or than La / Lb): out8 and
+ *   rot12 are then zero, the map -1, and the other pairs are unaffected.  TM-align's own floor is 3 residues, but its seeds degenerate
+ *   below min_ali = 5, and no chain here is shorter than data.min_res_num = 40.
+ *   status[p] is also 1, with the same zero outputs, when a coordinate of either chain inside its length is not finite or exceeds
+ *   1e6 in magnitude: every distance would be NaN and TM-align's own threshold-relaxation loops would never end (the reference's
+ *   process hangs on such a file); the kernel checks both traces as it loads them and additionally caps those loops.
+ * workspace = t2p_op_tm_align_ws(n_pairs, La, Lb) bytes on the device: a fixed 256 bytes whatever the arguments, or -1 when La or Lb
+ * is above TM_MAX_L or any of the three is not positive.  Its first int32 is a flag the call zeroes and the kernel sets when a pair
+ * index lies outside its set (that pair gets status 1); the caller reads it after the call, as with t2p_op_embedding_gather's
+ * bad_flag.  Refused before launch: a workspace too small, atoms other than 1 or 3, non-positive counts.  Everything is enqueued on
+ * `stream`; nothing is read back. */
+int64_t t2p_op_tm_align_ws(int n_pairs, int La, int Lb);
+int t2p_op_tm_align(const float* xyz_a, const int32_t* len_a, int n_a, int La, int atoms_a, const float* xyz_b, const int32_t* len_b, int n_b,
+                    int Lb, int atoms_b, const int32_t* pairs, int n_pairs, double* out8, int32_t* b2a, double* rot12, int32_t* status,
+                    void* workspace, int64_t workspace_bytes, void* stream);
 /* The reference's restraint set (load_constraints, rosetta_min/utils.py:119-206) scored on given backbones xyz = (batch, L, 3, 3) with
  * the harmonic forms Rosetta applies, in double, Cb being the virtual Cb: out8 = (batch, 8) double = sums over dist (i < j,
  * 0 < d <= 12, ((|Cb_i - Cb_j| - d) / dist_std)^2), omega (i < j, omega != 0, d <= 12, circular), theta (ordered pairs a != b with
@@ -754,6 +783,10 @@ int t2p_profile_begin(void);
 int t2p_debug_set(int key, int value);
 /* launches of the row-resident K = 512 GEMM (plan switch 49) since the library was loaded: lets a test see which plan a launch took */
 int64_t t2p_debug_rowres_launches(void);
+/* not part of the stable ABI (a measurement aid of tools/bench_tmalign.py and tests/test_gpu_tmalign.py): out4 (host) = the wavefronts
+ * and the dynamic LDS bytes of a t2p_op_tm_align workgroup at padded lengths La, Lb, then the kernel's registers per lane and scratch
+ * bytes per lane as the loaded code object reports them */
+int t2p_debug_tm_align_info(int La, int Lb, int32_t* out4);
 /* 1 when the library was built with -DT2P_ABLATION (never the shipped one) */
 int t2p_built_with_ablation(void);
 int t2p_profile_end(double* out9);

@@ -20,6 +20,11 @@ Differences, all at the edges of the hot path:
     (text2protein_amd/fold.py: restraint-free, in place of the PyRosetta stage of sampling_rosetta.py:98-160) and writes
     ``folded_<id>.pdb`` and ``fold_<id>.json`` (status, hand, closure errors, stress, restraint scores); one line is printed per
     chain whose status is not 0.
+  * ``--tm_ref PATH`` (repeatable; a ``.pdb`` file or a directory of them, read with ``--chain``; implies ``--fold``) scores the
+    folded chains with TM-align on the device (text2protein_amd/tmalign.py, in place of the reference's one TMalign process per
+    pair: tm/TMalign.py:36-160, utils.py:150-158): every chain against every reference and the chains against each other.
+    ``tm_scores.json`` holds per sample min / max / avg / std over the references (normalised by the reference, as ``tm_score``
+    does), the closest reference with both normalisations, and the pairwise matrix with its mean; one line is printed per sample.
   * ``--pdb FILE [--chain A] [--mask_info 1:5,10:15] [--sse LETTERS|FILE]``: the conditions of ``config.model.condition``
     from one chain of a PDB file (utils.py:122-137).  The reference goes through biotite there (and is broken, SURVEY.md 2
     row 10); here the backbone is read by a small reader of our own and featurised on the GPU (text2protein_amd/encode.py:
@@ -95,6 +100,11 @@ def main():
     parser.add_argument("--fold", action="store_true",
                         help="also fold every decoded sample to an N / CA / C backbone on the GPU (text2protein_amd/fold.py; implies "
                              "--decode): folded_<id>.pdb and fold_<id>.json (status, hand, closure, stress, restraint scores)")
+    parser.add_argument("--tm_ref", type=str, action="append", default=None, metavar="PATH",
+                        help="score every folded chain with TM-align on the GPU (text2protein_amd/tmalign.py) against reference chains: "
+                             "PATH is a .pdb file or a directory of them, read with --chain; may be repeated; implies --fold; writes "
+                             "tm_scores.json (per sample min / max / avg / std over the references, the closest one, and the pairwise "
+                             "matrix of the samples)")
     parser.add_argument("--gpus", type=int, default=1, help="start this many ranks (one per GPU) when not under torch.distributed.run")
     parser.add_argument("--global_batch_norm", action="store_true",
                         help="Langevin batch means over every rank's chains (the reference's DataParallel semantics)")
@@ -120,6 +130,14 @@ def main():
             raise SystemExit("--pc_guidance_w guides the predictor-corrector loop: with --sampler ddim give --guidance_w")
         if args.pc_guidance_w != args.pc_guidance_w or args.pc_guidance_w in (float("inf"), float("-inf")):
             raise SystemExit("--pc_guidance_w must be finite")
+    tm_ref_files = None
+    if args.tm_ref is not None:                                         # host only: the paths are checked before anything touches a device
+        from text2protein_amd.tmalign import reference_files
+        try:
+            tm_ref_files = reference_files(args.tm_ref)
+        except ValueError as e:
+            raise SystemExit(str(e))
+        args.fold = True
     replace = args.inpaint_mode == "replace"
     if replace:
         if args.sampler == "ddim":
@@ -166,6 +184,13 @@ def main():
     if rank == 0:
         workdir.mkdir(parents=True, exist_ok=True)
 
+    tm_refs = None
+    if tm_ref_files is not None and rank == 0:                          # read once; a chain TM-align cannot take stops the run here
+        from text2protein_amd import tmalign as TM
+        try:
+            tm_refs = TM.read_chains(tm_ref_files, args.chain) + ([os.path.basename(p) for p in tm_ref_files],)
+        except ValueError as e:
+            raise SystemExit(f"--tm_ref: {e}")
     pdb_condition = None
     if args.pdb is not None:
         sse = args.sse
@@ -329,8 +354,18 @@ def main():
                     import json
                     from text2protein_amd import fold as F
                     xyz, status, placed, diag = F.fold_maps_batch(absval, lengths)
-                    xyz = xyz.cpu().numpy()
-                    for i, (sid, d) in enumerate(zip(out_ids, F.diagnostics(status, placed, diag, lengths))):
+                    xyz_dev, xyz = xyz, xyz.cpu().numpy()
+                    chains = F.diagnostics(status, placed, diag, lengths)
+                    tm = None
+                    if tm_refs is not None:         # every folded chain against every reference, and the samples against each other
+                        keep = [i for i, d in enumerate(chains) if d["status"] >= 0]
+                        if keep:
+                            tm = TM.score_samples(xyz_dev[keep], torch.as_tensor([chains[i]["L"] for i in keep], dtype=torch.int32),
+                                                  [out_ids[i] for i in keep], *tm_refs)
+                            suffix = f"_{it}" if args.n_iter > 1 else ""
+                            with open(workdir.joinpath(f"tm_scores{suffix}.json"), "w") as f:
+                                json.dump(tm, f)
+                    for i, (sid, d) in enumerate(zip(out_ids, chains)):
                         if d["status"] < 0:         # reported above
                             continue
                         suffix = f"_{it}" if args.n_iter > 1 else ""
@@ -340,6 +375,15 @@ def main():
                         if d["status"] != 0:
                             print(f"sample {sid}: fold status {d['status']} ({d['unreachable_pairs']} unreachable pairs, "
                                   f"{len(d['placed'])} residues placed without a frame of their own)")
+                        if tm is not None:
+                            t = tm["samples"][str(sid)]
+                            if t["scored"]:
+                                print(f"sample {sid}: TM to {len(tm['references'])} references min {t['sample_min']:.4f} max {t['sample_max']:.4f} "
+                                      f"avg {t['sample_avg']:.4f} std {t['sample_std']:.4f}, closest {t['closest']} "
+                                      f"(TM {t['tm_by_reference']:.4f} by the reference, {t['tm_by_sample']:.4f} by the sample)")
+                            else:
+                                print(f"sample {sid}: not scored -- " + (f"{t['L']} residues, outside the 5 to 256 TM-align takes"
+                                                                          if t["why"] == "sample" else "no reference chain TM-align can take"))
             print(f"[{it + 1} / {args.n_iter}] save samples to {workdir} ({n} score evaluations per chain)")
     if dist is not None:
         dist.destroy_process_group()

@@ -154,6 +154,10 @@ SIGNATURES = {
     # backbones from decoded maps (csrc/fold.hip)
     "t2p_op_fold_ws": (_i64, [_i, _i]),
     "t2p_op_fold_6d": (_i, [_vp, _vp, _i, _i, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    # TM-align on folded backbones (csrc/tmalign.hip)
+    "t2p_op_tm_align_ws": (_i64, [_i, _i, _i]),
+    "t2p_op_tm_align": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "t2p_debug_tm_align_info": (_i, [_i, _i, _vp]),
     "t2p_op_restraint_score": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _i64, _vp]),
     "t2p_op_embedding_gather": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     "t2p_profile_end": (_i, [C.POINTER(C.c_double)]),

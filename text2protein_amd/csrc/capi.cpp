@@ -886,6 +886,23 @@ int t2p_op_restraint_score(const float* xyz, const float* absval, const int32_t*
   API_END
 }
 
+int64_t t2p_op_tm_align_ws(int n_pairs, int La, int Lb) { return (int64_t)tm_align_workspace_bytes(n_pairs, La, Lb); }
+
+int t2p_op_tm_align(const float* xyz_a, const int32_t* len_a, int n_a, int La, int atoms_a, const float* xyz_b, const int32_t* len_b, int n_b,
+                    int Lb, int atoms_b, const int32_t* pairs, int n_pairs, double* out8, int32_t* b2a, double* rot12, int32_t* status,
+                    void* workspace, int64_t workspace_bytes, void* stream) {
+  API_BEGIN
+  return launch_tm_align(xyz_a, len_a, n_a, La, atoms_a, xyz_b, len_b, n_b, Lb, atoms_b, pairs, n_pairs, out8, b2a, rot12, status, workspace,
+                         (long)workspace_bytes, (hipStream_t)stream);
+  API_END
+}
+
+int t2p_debug_tm_align_info(int La, int Lb, int32_t* out4) {
+  API_BEGIN
+  return tm_align_info(La, Lb, out4);
+  API_END
+}
+
 int t2p_op_embedding_gather(const void* table, int table_dtype, const int32_t* ids, float* out, int64_t n_tokens, int dim, int vocab,
                             int32_t* bad_flag, void* stream) {
   API_BEGIN

@@ -296,6 +296,18 @@ int launch_fold6d(const float* absval, const int* lengths, int B, int L, float k
 int launch_restraint_score(const float* xyz, const float* absval, const int* lengths, int B, int L, float dist_std, float angle_std_deg,
                            double* out, int stride, void* workspace, long workspace_bytes, hipStream_t s);
 
+// ---- scoring folded backbones: TM-align (tmalign.hip) ----
+// The default path of the reference's tm/TMalign.cpp for pairs of CA traces: xyz_* [n][L][atoms][3] fp32 (atoms = 3: N / CA / C, atom 1
+// is read; atoms = 1: a CA trace), len_* [n]; pairs [n_pairs][2] or null = all n_a x n_b pairs, row-major.  One workgroup per pair.
+// out8 [n_pairs][8] double, b2a [n_pairs][Lb] (or null), rot12 [n_pairs][12] (or null), status [n_pairs].  TM_MAX_L is every shipped
+// data.max_res_num: it bounds the registers a lane holds (TM_MAX_L / 64 residues) and the LDS of a workgroup.
+constexpr int TM_MAX_L = 256;
+long tm_align_workspace_bytes(int n_pairs, int La, int Lb);          // -1 when La or Lb is out of range
+int tm_align_info(int La, int Lb, int* out4);     // wavefronts and dynamic LDS bytes of a workgroup; the kernel's registers and scratch
+int launch_tm_align(const float* xyz_a, const int* len_a, int n_a, int La, int atoms_a, const float* xyz_b, const int* len_b, int n_b, int Lb,
+                    int atoms_b, const int* pairs, int n_pairs, double* out8, int* b2a, double* rot12, int* status, void* workspace,
+                    long workspace_bytes, hipStream_t s);
+
 // ---- weight packing on the device (weightpack.hip) -----------------------------------------------------------------------------
 // One packing = one kind applied to fp32 sources, written to dst in `dtype`.  Engine::pack_weights decides which packings a network
 // needs; the host load path runs them through weight_pack_host (engine.cpp), the device refresh through launch_weight_pack: same bits.

@@ -5,9 +5,10 @@ The four decoded maps determine an N / CA / C backbone directly: 
 all pairs by shortest paths, embedded by classical MDS and refined by ``stress_steps`` gradient steps on the known pairs; phi gives every
 residue's CA - Cb direction, theta the azimuth of N about it and the featuriser's virtual-Cb identity then gives C; of the two mirror
 images the one whose consecutive C and N close the chain is kept.  ``t2p_op_fold_6d`` does all of it for a whole batch in five launches;
-there is no CPU path.  Rosetta's minimisation, relax / design, side chains and TM-align are not here; the reference's restraint set
+there is no CPU path.  Rosetta's minimisation, relax / design and side chains are not here; the reference's restraint set
 (``load_constraints``, rosetta_min/utils.py:119-206) is scored on the result with the harmonic forms Rosetta applies, so chains can be
-ranked the way ``sampling_rosetta.py`` ranks its runs.
+ranked the way ``sampling_rosetta.py`` ranks its runs.  TM-align, which the reference runs on the backbones next, is
+``text2protein_amd/tmalign.py``: it takes the ``xyz`` this module leaves on the device.
 
 ``known_below`` defaults to 19.0 A (an encoded far pair decodes to exactly 20).  No trained checkpoint exists in this repository, so
 the best value for SAMPLED maps is not measured; the default is only known to work on maps encoded from real geometry.
