@@ -761,6 +761,33 @@ int t2p_op_tm_align(const float* xyz_a, const int32_t* len_a, int n_a, int La, i
  * d[a][b] <= 12, circular) and phi (the same pairs, harmonic), angle_std in degrees, then the four counts.  Workspace as above. */
 int t2p_op_restraint_score(const float* xyz, const float* absval, const int32_t* lengths, int batch, int L, float dist_std, float angle_std,
                            double* out8, void* workspace, int64_t workspace_bytes, void* stream);
+/* Refinement of backbones against the same restraint set, the stage the reference runs between the maps and TM-align
+ * (rosetta_min/run.py) -- not Rosetta: a Cartesian L-BFGS on N / CA / C, in double, one persistent workgroup per chain, nothing read back.
+ * The energy: the four restraint terms of t2p_op_restraint_score with the same sets and forms, less the theta restraints whose target phi
+ * lies within arm_min degrees of 0 or 180 and the omega restraints for which phi_ij or phi_ji does, counted for sep_lo <= |i - j| <
+ * sep_hi; plus bonds (N-CA 1.458, CA-C 1.525, C-N 1.329, sigma 0.02 A), angles (N-CA-C 111.0, CA-C-N 116.2, C-N-CA 121.7, sigma 3
+ * degrees), peptide planarity (dihedral CA C N CA about 180, sigma 6 degrees), each ((x - x0) / sigma)^2, and the repulsion
+ * max(0, 3.8 - |CA_i - CA_j|)^2 over j - i >= 2.  E = w_dist dist + w_ang (omega + theta + phi) + bond + angle + pept + w_rep rep.
+ *   xyz_in = (batch, L, 3, 3) fp32, absval = (batch, 4, L*L) fp32 and lengths = (batch) int32 as t2p_op_fold_6d takes and writes them;
+ *   L <= 256.  schedule = n_stages (1..8) x 6 doubles on the HOST: sep_lo, sep_hi, w_dist, w_ang, w_rep, max_iter.  Per stage: L-BFGS
+ *   (8 pairs), Armijo backtracking (c1 1e-4, halving, 20 trials), steepest descent on a non-descent direction or after a failed line
+ *   search, stop at max|g| < 1e-3.  dist_std in A, angle_std and arm_min in degrees.
+ * Outputs, device: xyz_out = (batch, L, 3, 3) fp32, zero past lengths[b]; status[b] = 0 ok, 1 a stage ended on a failed line search
+ * (the coordinates are the best accepted), 2 a coordinate of the start is not finite (zeros), -1 lengths[b] < 2 or > L (zeros);
+ * diag = (batch, 16) double: E at the start under the last stage's weights, E at the end, the eight unweighted terms at the end (dist,
+ * omega, theta, phi, bond, angle, pept, rep), line searches run, energy evaluations, final max|g|, final mean closure error
+ * | |C_i - N_i+1| - 1.329 |, stages completed, 0.  Every output is finite.  workspace = t2p_op_refine_ws(batch, L) bytes on the device
+ * (-1: L above 256 or an argument not positive).  Two calls give the same bits, whatever batch or padding a chain sits in. */
+int64_t t2p_op_refine_ws(int batch, int L);
+int t2p_op_refine_backbone(const float* xyz_in, const float* absval, const int32_t* lengths, int batch, int L, const double* schedule,
+                           int n_stages, float dist_std, float angle_std, float arm_min, float* xyz_out, int32_t* status, double* diag,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+/* One evaluation of that energy, by the device functions the minimiser calls: stage = 6 doubles on the host (max_iter ignored);
+ * out9 = (batch, 9) double = the eight unweighted terms and the weighted total, grad = (batch, L, 3, 3) double = the gradient of the
+ * total, zero past lengths[b]; all zero for a chain t2p_op_refine_backbone would give status 2 or -1.  Workspace as above. */
+int t2p_op_restraint_energy(const float* xyz, const float* absval, const int32_t* lengths, int batch, int L, const double* stage,
+                            float dist_std, float angle_std, float arm_min, double* out9, double* grad, void* workspace,
+                            int64_t workspace_bytes, void* stream);
 /* text context = embed_tokens(ids), sampling_6d.py:134-137: out[(b,t)][:] = table[ids[(b,t)]][:] as fp32; the table
  * ([vocab][dim], fp32 / bf16 / f16 by table_dtype) stays resident.  *bad_flag (device int, zeroed by the caller) is
  * set to 1 when an id falls outside [0, vocab). */

@@ -20,6 +20,11 @@ Differences, all at the edges of the hot path:
     (text2protein_amd/fold.py: restraint-free, in place of the PyRosetta stage of sampling_rosetta.py:98-160) and writes
     ``folded_<id>.pdb`` and ``fold_<id>.json`` (status, hand, closure errors, stress, restraint scores); one line is printed per
     chain whose status is not 0.
+  * ``--refine`` (implies ``--fold``) additionally minimises every folded chain against the restraint set on the device
+    (text2protein_amd/refine.py: a staged L-BFGS over the reference's restraints plus ideal-geometry terms, the step
+    rosetta_min/run.py takes between the maps and TM-align -- without Rosetta's own energy terms, relax or side chains; maps of
+    at most 256 residues) and writes ``refined_<id>.pdb`` next to ``folded_<id>.pdb``; ``fold_<id>.json`` gains a ``"refine"`` block
+    (status, energies, the eight terms, iterations, evaluations, closure).  With ``--tm_ref`` the refined chains are the ones scored.
   * ``--tm_ref PATH`` (repeatable; a ``.pdb`` file or a directory of them, read with ``--chain``; implies ``--fold``) scores the
     folded chains with TM-align on the device (text2protein_amd/tmalign.py, in place of the reference's one TMalign process per
     pair: tm/TMalign.py:36-160, utils.py:150-158): every chain against every reference and the chains against each other.
@@ -100,6 +105,10 @@ def main():
     parser.add_argument("--fold", action="store_true",
                         help="also fold every decoded sample to an N / CA / C backbone on the GPU (text2protein_amd/fold.py; implies "
                              "--decode): folded_<id>.pdb and fold_<id>.json (status, hand, closure, stress, restraint scores)")
+    parser.add_argument("--refine", action="store_true",
+                        help="also minimise every folded chain against the restraint set on the GPU (text2protein_amd/refine.py; implies "
+                             "--fold; at most 256 residues): refined_<id>.pdb next to folded_<id>.pdb, a \"refine\" block in fold_<id>.json; "
+                             "--tm_ref then scores the refined chains")
     parser.add_argument("--tm_ref", type=str, action="append", default=None, metavar="PATH",
                         help="score every folded chain with TM-align on the GPU (text2protein_amd/tmalign.py) against reference chains: "
                              "PATH is a .pdb file or a directory of them, read with --chain; may be repeated; implies --fold; writes "
@@ -137,6 +146,8 @@ def main():
             tm_ref_files = reference_files(args.tm_ref)
         except ValueError as e:
             raise SystemExit(str(e))
+        args.fold = True
+    if args.refine:
         args.fold = True
     replace = args.inpaint_mode == "replace"
     if replace:
@@ -356,6 +367,16 @@ def main():
                     xyz, status, placed, diag = F.fold_maps_batch(absval, lengths)
                     xyz_dev, xyz = xyz, xyz.cpu().numpy()
                     chains = F.diagnostics(status, placed, diag, lengths)
+                    refined = None
+                    if args.refine:                 # minimised against the restraint set; these are the chains scored below
+                        from text2protein_amd import refine as R
+                        try:
+                            xyz_dev, r_status, r_diag = R.refine_backbone_batch(xyz_dev, absval, lengths)
+                        except ValueError as e:
+                            raise SystemExit(f"--refine: {e}")
+                        refined = xyz_dev.cpu().numpy()
+                        for d, r in zip(chains, R.diagnostics(r_status, r_diag, lengths)):
+                            d["refine"] = r
                     tm = None
                     if tm_refs is not None:         # every folded chain against every reference, and the samples against each other
                         keep = [i for i, d in enumerate(chains) if d["status"] >= 0]
@@ -370,6 +391,10 @@ def main():
                             continue
                         suffix = f"_{it}" if args.n_iter > 1 else ""
                         F.write_backbone_pdb(workdir.joinpath(f"folded_{sid}{suffix}.pdb"), xyz[i, :d["L"]])
+                        if refined is not None:
+                            F.write_backbone_pdb(workdir.joinpath(f"refined_{sid}{suffix}.pdb"), refined[i, :d["L"]])
+                            if d["refine"]["status"] != 0:
+                                print(f"sample {sid}: refine status {d['refine']['status']}")
                         with open(workdir.joinpath(f"fold_{sid}{suffix}.json"), "w") as f:
                             json.dump(d, f)
                         if d["status"] != 0:

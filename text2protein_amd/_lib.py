@@ -159,6 +159,10 @@ SIGNATURES = {
     "t2p_op_tm_align": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "t2p_debug_tm_align_info": (_i, [_i, _i, _vp]),
     "t2p_op_restraint_score": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _i64, _vp]),
+    # refinement of folded backbones against the restraint set (csrc/refine.hip)
+    "t2p_op_refine_ws": (_i64, [_i, _i]),
+    "t2p_op_refine_backbone": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "t2p_op_restraint_energy": (_i, [_vp, _vp, _vp, _i, _i, _vp, _f, _f, _f, _vp, _vp, _vp, _i64, _vp]),
     "t2p_op_embedding_gather": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     "t2p_profile_end": (_i, [C.POINTER(C.c_double)]),
     "t2p_profile_dominant": (_i, [C.POINTER(C.c_double), C.c_char_p, C.c_int]),

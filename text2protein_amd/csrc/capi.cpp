@@ -886,6 +886,26 @@ int t2p_op_restraint_score(const float* xyz, const float* absval, const int32_t*
   API_END
 }
 
+int64_t t2p_op_refine_ws(int batch, int L) { return (int64_t)refine_workspace_bytes(batch, L); }
+
+int t2p_op_refine_backbone(const float* xyz_in, const float* absval, const int32_t* lengths, int batch, int L, const double* schedule,
+                           int n_stages, float dist_std, float angle_std, float arm_min, float* xyz_out, int32_t* status, double* diag,
+                           void* workspace, int64_t workspace_bytes, void* stream) {
+  API_BEGIN
+  return launch_refine_backbone(xyz_in, absval, lengths, batch, L, schedule, n_stages, dist_std, angle_std, arm_min, xyz_out, status, diag,
+                                workspace, (long)workspace_bytes, (hipStream_t)stream);
+  API_END
+}
+
+int t2p_op_restraint_energy(const float* xyz, const float* absval, const int32_t* lengths, int batch, int L, const double* stage,
+                            float dist_std, float angle_std, float arm_min, double* out9, double* grad, void* workspace,
+                            int64_t workspace_bytes, void* stream) {
+  API_BEGIN
+  return launch_restraint_energy(xyz, absval, lengths, batch, L, stage, dist_std, angle_std, arm_min, out9, grad, workspace,
+                                 (long)workspace_bytes, (hipStream_t)stream);
+  API_END
+}
+
 int64_t t2p_op_tm_align_ws(int n_pairs, int La, int Lb) { return (int64_t)tm_align_workspace_bytes(n_pairs, La, Lb); }
 
 int t2p_op_tm_align(const float* xyz_a, const int32_t* len_a, int n_a, int La, int atoms_a, const float* xyz_b, const int32_t* len_b, int n_b,

@@ -296,6 +296,20 @@ int launch_fold6d(const float* absval, const int* lengths, int B, int L, float k
 int launch_restraint_score(const float* xyz, const float* absval, const int* lengths, int B, int L, float dist_std, float angle_std_deg,
                            double* out, int stride, void* workspace, long workspace_bytes, hipStream_t s);
 
+// ---- refinement of folded backbones against the restraint set (refine.hip) ----
+// One workgroup per chain, a persistent staged L-BFGS in double; REFINE_MAX_L bounds the five coordinate-sized vectors a workgroup keeps
+// in LDS (18 KB each at 256 residues) and is every shipped data.max_res_num, like TM_MAX_L.  A stage is six doubles on the host:
+// sep_lo, sep_hi, w_dist, w_ang, w_rep, max_iter.
+constexpr int REFINE_MAX_L = 256, REFINE_MAX_STAGES = 8;
+long refine_workspace_bytes(int B, int L);           // -1 when L is out of range
+int launch_refine_backbone(const float* xyz_in, const float* absval, const int* lengths, int B, int L, const double* schedule, int n_stages,
+                           float dist_std, float angle_std_deg, float arm_min_deg, float* xyz_out, int* status, double* diag, void* workspace,
+                           long workspace_bytes, hipStream_t s);
+// one evaluation of the same energy: out9 [B][9] (eight unweighted terms, weighted total), grad [B][L][3][3], both double
+int launch_restraint_energy(const float* xyz, const float* absval, const int* lengths, int B, int L, const double* stage6, float dist_std,
+                            float angle_std_deg, float arm_min_deg, double* out9, double* grad, void* workspace, long workspace_bytes,
+                            hipStream_t s);
+
 // ---- scoring folded backbones: TM-align (tmalign.hip) ----
 // The default path of the reference's tm/TMalign.cpp for pairs of CA traces: xyz_* [n][L][atoms][3] fp32 (atoms = 3: N / CA / C, atom 1
 // is read; atoms = 1: a CA trace), len_* [n]; pairs [n_pairs][2] or null = all n_a x n_b pairs, row-major.  One workgroup per pair.

@@ -7,8 +7,9 @@ residue's CA - Cb direction, theta the azimuth of N about it and the featuriser'
 images the one whose consecutive C and N close the chain is kept.  ``t2p_op_fold_6d`` does all of it for a whole batch in five launches;
 there is no CPU path.  Rosetta's minimisation, relax / design and side chains are not here; the reference's restraint set
 (``load_constraints``, rosetta_min/utils.py:119-206) is scored on the result with the harmonic forms Rosetta applies, so chains can be
-ranked the way ``sampling_rosetta.py`` ranks its runs.  TM-align, which the reference runs on the backbones next, is
-``text2protein_amd/tmalign.py``: it takes the ``xyz`` this module leaves on the device.
+ranked the way ``sampling_rosetta.py`` ranks its runs.  A minimisation against that restraint set -- a Cartesian L-BFGS, not Rosetta's
+energy -- is ``text2protein_amd/refine.py`` (``fold_6d_batch(..., refine=True)``).  TM-align, which the reference runs on the backbones
+next, is ``text2protein_amd/tmalign.py``: it takes the ``xyz`` this module leaves on the device.
 
 ``known_below`` defaults to 19.0 A (an encoded far pair decodes to exactly 20).  No trained checkpoint exists in this repository, so
 the best value for SAMPLED maps is not measured; the default is only known to work on maps encoded from real geometry.
@@ -79,21 +80,31 @@ def fold_maps_batch(absval, lengths, known_below=19.0, stress_steps=300, dist_st
     return xyz, status, placed, diag
 
 
-def fold_6d_batch(samples, known_below=19.0, stress_steps=300, dist_std=2.0, angle_std=10.0):
+def fold_6d_batch(samples, known_below=19.0, stress_steps=300, dist_std=2.0, angle_std=10.0, refine=False, schedule=None, arm_min=None):
     """``samples``: (B, C, L, L) float32 on the device, as the samplers return them.  Decodes and folds.  Returns a dict: ``xyz``
     (B, L, 3, 3), ``status`` (B,), ``placed`` (B, L), ``diag`` (B, 16) device tensors, ``absval`` (the decoded maps the fold read,
     (B, 4, L*L) on the device), ``lengths`` (B,) int32 on the host and
     ``chains``, the host diagnostics (one dict per chain: status, residues placed without a frame, hand kept, both closure errors,
-    stress rms, the four restraint scores and their counts)."""
+    stress rms, the four restraint scores and their counts).
+
+    ``refine=True`` then minimises every chain against the restraint set (text2protein_amd/refine.py; ``schedule`` and ``arm_min`` as
+    there, at most 256 residues): ``xyz`` is the refined backbone, ``xyz_fold`` the fold's own, ``refine`` the per-chain diagnostics
+    of the minimisation and ``refine_status`` / ``refine_diag`` its device tensors.  ``status``, ``diag`` and ``chains`` stay the fold's."""
     lengths, _, absval = decode_6d_batch(samples)
     xyz, status, placed, diag = fold_maps_batch(absval, lengths, known_below, stress_steps, dist_std, angle_std)
-    return {"xyz": xyz, "status": status, "placed": placed, "diag": diag, "lengths": lengths, "absval": absval,
-            "chains": diagnostics(status, placed, diag, lengths)}
+    out = {"xyz": xyz, "status": status, "placed": placed, "diag": diag, "lengths": lengths, "absval": absval,
+           "chains": diagnostics(status, placed, diag, lengths)}
+    if refine:
+        from . import refine as R
+        rx, rstatus, rdiag = R.refine_backbone_batch(xyz, absval, lengths, schedule, dist_std, angle_std, R.ARM_MIN if arm_min is None else arm_min)
+        out.update(xyz=rx, xyz_fold=xyz, refine_status=rstatus, refine_diag=rdiag, refine=R.diagnostics(rstatus, rdiag, lengths))
+    return out
 
 
 def fold_6d(samples, **kw):
     """One dict per chain, like ``decode_6d``: the diagnostics plus ``xyz`` (L, 3, 3) float32 numpy.  An improper mask raises
-    ``ValueError`` with the reference's message (sampling_rosetta.py:72-73)."""
+    ``ValueError`` with the reference's message (sampling_rosetta.py:72-73).  With ``refine=True`` ``xyz`` is the refined backbone and
+    every dict gains ``xyz_fold`` and ``refine`` (that chain's minimisation diagnostics)."""
     if samples.dim() == 3:
         samples = samples.unsqueeze(0)
     r = fold_6d_batch(samples, **kw)
@@ -102,7 +113,10 @@ def fold_6d(samples, **kw):
     for b, d in enumerate(r["chains"]):
         if d["status"] < 0:
             raise ValueError("Terminated due to improper masking channel...")
-        out.append(dict(d, xyz=xyz[b, :d["L"]].copy()))
+        one = dict(d, xyz=xyz[b, :d["L"]].copy())
+        if "refine" in r:
+            one.update(xyz_fold=r["xyz_fold"][b, :d["L"]].cpu().numpy(), refine=r["refine"][b])
+        out.append(one)
     return out
 
 
