@@ -801,13 +801,18 @@ int t2p_op_apply_mask(float* x, const uint8_t* mask, const float* x_initial, int
 int t2p_profile_begin(void);
 /* Plan switches for tests and A/B measurements: they select between kernel geometries / fusions that all
  * produce correct results (key 0 LDS-DMA GEMM on/off, 2 tile geometry, 3 split-K, 4..25 individual fusions and
- * kernel forms -- the full list with one line each: tools/README.md; text2protein_amd/csrc/capi.cpp; key 48, read by t2p_train_create:
+ * kernel forms -- the full list is the key table next to t2p_debug_set, with every default and one line each in
+ * text2protein_amd/csrc/plan.h and tools/README.md; key 48, read by t2p_train_create:
  * the 16-bit training step's fixed-order reductions, scaled backward seed and overflow guard on f32 products).  Key 1 is the
  * timing-only ablation mask of the LDS-DMA kernel: its bits 128 / 256 (DMA issue order) and 4096 (LDS-staged instead of
  * register epilogue), results unchanged, are always accepted, the bits that skip work and so produce
  * WRONG results exist only in a library built with -DT2P_ABLATION (python -m text2protein_amd.build --ablation)
  * and are refused (status 1) by the product build. */
 int t2p_debug_set(int key, int value);
+/* the current value of a plan switch (0 / 1 for the on / off switches, MiB for key 10); status 1 for an unknown key or a null pointer */
+int t2p_debug_get(int key, int* value);
+/* the short lowercase name of a plan switch (its member of t2p::Plan), or NULL for an unknown key */
+const char* t2p_debug_key_name(int key);
 /* launches of the row-resident K = 512 GEMM (plan switch 49) since the library was loaded: lets a test see which plan a launch took */
 int64_t t2p_debug_rowres_launches(void);
 /* not part of the stable ABI (a measurement aid of tools/bench_tmalign.py and tests/test_gpu_tmalign.py): out4 (host) = the wavefronts

@@ -33,7 +33,7 @@ TDT = {0: torch.float32, 1: torch.bfloat16, 2: torch.float16}
 TC_NAME = {1: "bf16_t", 2: "f16_t"}
 F32_TOL = dict(y=2e-6, dx=3e-6, dw=3e-6, colsum=2e-5)
 TOL16 = dict(y=OP_TOL, dx=OP_TOL, dw=OP_TOL, colsum=2e-5)
-GEOM_SWITCH = {(256, 128): 1, (128, 128): 2, (256, 256): 3, (512, 128): 4}      # plan switch 2 (gemm.hip: g_dma_geom)
+GEOM_SWITCH = {(256, 128): 1, (128, 128): 2, (256, 256): 3, (512, 128): 4}      # plan switch 2 (plan.h: dma_geom)
 PAD_SENTINEL = 12345.0
 
 

@@ -148,6 +148,8 @@ SIGNATURES = {
     "t2p_op_philox_normal": (_i, [_vp, _i64, _u64, _u64, _vp]),
     "t2p_profile_begin": (_i, []),
     "t2p_debug_set": (_i, [_i, _i]),
+    "t2p_debug_get": (_i, [_i, C.POINTER(_i)]),
+    "t2p_debug_key_name": (C.c_char_p, [_i]),
     "t2p_debug_rowres_launches": (_i64, []),
     "t2p_op_decode_6d": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "t2p_op_encode_6d": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
@@ -284,11 +286,16 @@ def load(build_if_missing: bool = True):
 
 
 def set_plan_switches(spec: str):
-    """Measurement tools only (bench.py --plan, tools/): "key=value,key=value" -> t2p_debug_set (include/t2p.h).
-    The product path never calls this and reads no environment variable."""
+    """Measurement tools only (bench.py --plan, tools/): "key=value,key=value" -> t2p_debug_set (include/t2p.h); a key is its
+    number or its name (t2p_debug_key_name).  The product path never calls this and reads no environment variable."""
     lib = load()
     for kv in filter(None, (spec or "").split(",")):
         k, v = kv.split("=")
+        if not k.strip().lstrip("-").isdigit():
+            keys = [i for i in range(256) if lib.t2p_debug_key_name(i) == k.strip().encode()]
+            if not keys:
+                raise T2PError(f"bad plan switch {kv}: no key has that name")
+            k = keys[0]
         if lib.t2p_debug_set(int(k), int(v)) != 0:
             msg = lib.t2p_last_error()
             raise T2PError(f"bad plan switch {kv}: {msg.decode() if msg else '?'}")

@@ -603,9 +603,8 @@ __global__ __launch_bounds__(512) void attn_strip_kernel(const StripArgs a) {
     }
 }
 
-bool g_attn_strip = true;       // plan switch 29
 bool attention_strip_eligible(int dtype, int heads, int nq, int nk, int d, long ldq, long ldk, long ldvt, long ldo) {
-  if (!g_attn_strip || dtype == DT_F32 || heads != 1 || nq != nk) return false;
+  if (!g_plan.attn_strip || dtype == DT_F32 || heads != 1 || nq != nk) return false;
   if (d != 256 && d != 512 && d != 1024) return false;
   if (nk < 8 || nk > 1024 || nk % 8 != 0) return false;
   if (d == 1024 && nk > 512) return false;             // 64 x 1024 query strip + 64 x 1024 probability strip: beyond the LDS budget

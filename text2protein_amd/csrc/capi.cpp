@@ -4,7 +4,6 @@
 #include "ddim.h"
 #include "engine.h"
 #include "sampler.h"
-#include "train.h"   // g_train_plumbing16 (plan switch 48)
 
 using namespace t2p;
 
@@ -20,7 +19,7 @@ using namespace t2p;
     return T2P_ERR_STATE;                              \
   }
 
-namespace t2p { extern bool g_pre_conv_mfma, g_gn_apply_cols; void layer_profile_begin(); int layer_profile_end(std::string* out);
+namespace t2p { void layer_profile_begin(); int layer_profile_end(std::string* out);
 void debug_tap_set(int index, float* dst, long capacity); void debug_tap_shape(long out[4]); }
 extern "C" {
 
@@ -360,16 +359,17 @@ int t2p_op_gemm_geglu(int dtype, const void* A, const void* Bw, void* C, int M, 
 }
 
 static void* g_op_ws = nullptr;
-static size_t g_op_ws_bytes = 0, g_op_ws_alloc = 0;
-// development switch (t2p_debug_set key 10): a split-K workspace for the op entries, so that they can take that plan
+static size_t g_op_ws_alloc = 0;
+// development switch (t2p_debug_set key 10, MiB): a split-K workspace for the op entries, so that they can take that plan
 static int attach_op_ws(GemmParams& p) {
-  if (!g_op_ws_bytes) return T2P_OK;
-  if (g_op_ws_alloc < g_op_ws_bytes) {
+  const size_t bytes = (size_t)g_plan.op_ws_mib << 20;
+  if (!bytes) return T2P_OK;
+  if (g_op_ws_alloc < bytes) {
     if (g_op_ws) { T2P_HIP_CHECK(hipDeviceSynchronize()); T2P_HIP_CHECK(hipFree(g_op_ws)); g_op_ws = nullptr; g_op_ws_alloc = 0; }
-    T2P_HIP_CHECK(hipMalloc(&g_op_ws, g_op_ws_bytes));
-    g_op_ws_alloc = g_op_ws_bytes;
+    T2P_HIP_CHECK(hipMalloc(&g_op_ws, bytes));
+    g_op_ws_alloc = bytes;
   }
-  p.ws = g_op_ws; p.ws_bytes = g_op_ws_bytes;
+  p.ws = g_op_ws; p.ws_bytes = bytes;
   return T2P_OK;
 }
 
@@ -521,7 +521,7 @@ int t2p_op_groupnorm(const float* x0, const float* x1, int C0, int C1, int batch
     GroupNormApplyArgs g;
     g.x0 = x0; g.x1 = x1; g.C0 = C0; g.C1 = C1; g.B = batch; g.H = H; g.W = W; g.G = groups; g.gamma = gamma; g.beta = beta;
     g.silu = silu; g.down = down; g.out = out; g.dtype = dtype; g.eps = eps;
-    if (g_gn_small && gn_small_eligible(g)) return launch_gn_small(g, s);
+    if (g_plan.gn_small && gn_small_eligible(g)) return launch_gn_small(g, s);
   }
   const int nparts = gn_num_chunks(a.HW) * ((C + 1023) / 1024);
   float* ws = nullptr;
@@ -581,7 +581,7 @@ int t2p_op_attention(int dtype, const void* q, int64_t ldq, const void* k, int64
   API_BEGIN
   T2P_REQUIRE(workspace && ((uintptr_t)workspace % 256) == 0, "workspace must be 256-byte aligned");
   hipStream_t s = (hipStream_t)stream;
-  if (g_flash_attention && attention_flash_eligible(dtype, d, ldq, ldk, ldvt, (long)heads * d))
+  if (g_plan.flash_attention && attention_flash_eligible(dtype, d, ldq, ldk, ldvt, (long)heads * d))
     return launch_attention_flash(dtype, q, ldq, k, ldk, vt, ldvt, out, batch, heads, nq, nk, d, scale, s);
   if (attention_strip_eligible(dtype, heads, nq, nk, d, ldq, ldk, ldvt, d))
     return launch_attention_strip(dtype, q, ldq, k, ldk, vt, ldvt, out, d, batch, nq, d, scale, s);
@@ -938,65 +938,89 @@ int t2p_op_apply_mask(float* x, const uint8_t* mask, const float* x_initial, int
 
 int64_t t2p_debug_rowres_launches(void) { return (int64_t)t2p::g_rowres_launches; }
 
+// ---- plan switches (plan.h): one row per key of t2p_debug_set / t2p_debug_get / t2p_debug_key_name ----
+struct PlanKey {
+  enum Rule { ANY, POSITIVE, RANGE, MASK };   // ANY: stored as given; POSITIVE: values <= 0 change nothing (and are no error);
+                                              // RANGE: lo..hi, else refused; MASK: bits outside `hi` refused (product build only)
+  int key; const char* name;
+  bool Plan::*b = nullptr;     // a bool switch (value != 0), or
+  int Plan::*i = nullptr;      // an int switch under `rule`
+  Rule rule = ANY; int lo = 0, hi = 0;
+  const char* refusal = nullptr;     // the message of a RANGE / MASK refusal
+  constexpr PlanKey(int key, const char* name, bool Plan::*b) : key(key), name(name), b(b) {}
+  constexpr PlanKey(int key, const char* name, int Plan::*i, Rule rule = ANY, int lo = 0, int hi = 0, const char* refusal = nullptr)
+      : key(key), name(name), i(i), rule(rule), lo(lo), hi(hi), refusal(refusal) {}
+};
+static constexpr PlanKey kPlanKeys[] = {
+    {0, "dma", &Plan::dma},
+    {1, "dbg", &Plan::dbg, PlanKey::MASK, 0, 128 | 256 | 4096 | 8192, "ablation bits that skip work exist only in a -DT2P_ABLATION build"},
+    {2, "dma_geom", &Plan::dma_geom},
+    {3, "splitk", &Plan::splitk},
+    {4, "raw_copies", &Plan::raw_copies},
+    {5, "flash_attention", &Plan::flash_attention},
+    {6, "fuse_gn_stats", &Plan::fuse_gn_stats},
+    {7, "fuse_geglu", &Plan::fuse_geglu},
+    {8, "dma_ring", &Plan::dma_ring},
+    {9, "lowp_h1", &Plan::lowp_h1},
+    {10, "op_ws_mib", &Plan::op_ws_mib},
+    {11, "force_nsplit", &Plan::force_nsplit},
+    {12, "midsplit", &Plan::midsplit},
+    {13, "gn_small", &Plan::gn_small},
+    {14, "lowp_residual", &Plan::lowp_residual},
+    {15, "thin_conv", &Plan::thin_conv},
+    {17, "gn_apply16", &Plan::gn_apply16},
+    {20, "layernorm16", &Plan::layernorm16},
+    {21, "up4", &Plan::up4},
+    {22, "deep_ring", &Plan::deep_ring},
+    {23, "fuse_shortcut", &Plan::fuse_shortcut},
+    {25, "qkv_fused", &Plan::qkv_fused},
+    {26, "pre_conv_mfma", &Plan::pre_conv_mfma},
+    {27, "gn_apply_cols", &Plan::gn_apply_cols},
+    {28, "post_gn", &Plan::post_gn},
+    {29, "attn_strip", &Plan::attn_strip},
+    {30, "split_tiles", &Plan::split_tiles, PlanKey::POSITIVE},
+    {31, "split_target", &Plan::split_target, PlanKey::POSITIVE},
+    {32, "attn_merged", &Plan::attn_merged},
+    {33, "ffpo_merged", &Plan::ffpo_merged},
+    {34, "a_norm", &Plan::a_norm},
+    {36, "small_conv", &Plan::small_conv},
+    {38, "pre_conv_split", &Plan::pre_conv_split},
+    {39, "st_fuse", &Plan::st_fuse},
+    {40, "st_tail", &Plan::st_tail},
+    {41, "small_conv_fm", &Plan::small_conv_fm},
+    {42, "st_ffpo", &Plan::st_ffpo},
+    {43, "st_tail_rows", &Plan::st_tail_rows},
+    {45, "attn_fm", &Plan::attn_fm},
+    {46, "attn_proj", &Plan::attn_proj},
+    {47, "dxs", &Plan::dxs},
+    {48, "train_plumbing16", &Plan::train_plumbing16},
+    {49, "rowres", &Plan::rowres, PlanKey::RANGE, 0, 2, "plan switch 49 takes 0 (off), 1 (the planner's choice) or 2 (wherever eligible)"},
+};
+static const PlanKey* plan_key(int key) {
+  for (const PlanKey& k : kPlanKeys)
+    if (k.key == key) return &k;
+  return nullptr;
+}
+
 int t2p_debug_set(int key, int value) {
-  if (key == 10) { g_op_ws_bytes = (size_t)value << 20; return T2P_OK; }
-  if (key == 11) { set_gemm_force_nsplit(value); return T2P_OK; }
-  if (key == 12) { set_gemm_midsplit(value != 0); return T2P_OK; }
-  if (key == 13) { g_gn_small = value != 0; return T2P_OK; }
-  if (key == 14) { g_lowp_residual = value != 0; return T2P_OK; }
-  if (key == 15) { set_gemm_thin_conv(value != 0); return T2P_OK; }
-  if (key == 17) { g_gn_apply16 = value != 0; return T2P_OK; }
-  if (key == 20) { g_layernorm16 = value != 0; return T2P_OK; }
-  if (key == 21) { set_gemm_up4(value != 0); return T2P_OK; }
-  if (key == 22) { set_gemm_deep_ring(value != 0); return T2P_OK; }
-  if (key == 23) { set_gemm_fuse_shortcut(value != 0); return T2P_OK; }
-  if (key == 25) { g_qkv_fused = value != 0; return T2P_OK; }
-  if (key == 26) { t2p::g_pre_conv_mfma = value != 0; return T2P_OK; }
-  if (key == 27) { t2p::g_gn_apply_cols = value != 0; return T2P_OK; }
-  if (key == 28) { set_gemm_post_gn(value != 0); return T2P_OK; }
-  if (key == 29) { t2p::g_attn_strip = value != 0; return T2P_OK; }
-  if (key == 36) { t2p::g_small_conv = value != 0; return T2P_OK; }
-  if (key == 38) { t2p::g_pre_conv_split = value != 0; return T2P_OK; }
-  if (key == 39) { t2p::g_st_fuse = value != 0; return T2P_OK; }
-  if (key == 40) { t2p::g_st_tail = value != 0; return T2P_OK; }
-  if (key == 41) { t2p::g_small_conv_fm = value != 0; return T2P_OK; }
-  if (key == 42) { t2p::g_st_ffpo = value != 0; return T2P_OK; }
-  if (key == 43) { t2p::g_st_tail_rows = value; return T2P_OK; }
-  if (key == 45) { t2p::g_attn_fm = value != 0; return T2P_OK; }
-  if (key == 46) { t2p::g_attn_proj = value != 0; return T2P_OK; }
-  if (key == 47) { set_gemm_dxs(value != 0); return T2P_OK; }
-  if (key == 48) { t2p::g_train_plumbing16 = value != 0; return T2P_OK; }
-  if (key == 49) {
-    if (value < 0 || value > 2) { set_last_error("plan switch 49 takes 0 (off), 1 (the planner's choice) or 2 (wherever eligible)"); return T2P_ERR_INVALID; }
-    t2p::g_rowres = value;
-    return T2P_OK;
-  }
-  if (key == 34) { set_gemm_a_norm(value != 0); return T2P_OK; }
-  if (key == 32) { g_attn_merged = value != 0; return T2P_OK; }
-  if (key == 33) { g_ffpo_merged = value != 0; return T2P_OK; }
-  if (key == 30) { set_gemm_split_consts(value, 0); return T2P_OK; }
-  if (key == 31) { set_gemm_split_consts(0, value); return T2P_OK; }
-  if (key == 0) set_gemm_dma(value != 0);
-  else if (key == 1) {
+  const PlanKey* k = plan_key(key);
+  if (!k) return T2P_ERR_INVALID;
+  if (k->b) { g_plan.*k->b = value != 0; return T2P_OK; }
+  bool refused = k->rule == PlanKey::RANGE && (value < k->lo || value > k->hi);
 #ifndef T2P_ABLATION
-    if (value & ~(128 | 256 | 4096 | 8192)) {        // (8192: the general register epilogue where the specialised one would run -- same results)
-      set_last_error("ablation bits that skip work exist only in a -DT2P_ABLATION build");
-      return T2P_ERR_INVALID;
-    }
+  refused = refused || (k->rule == PlanKey::MASK && (value & ~k->hi));
 #endif
-    set_gemm_debug(value);
-  }
-  else if (key == 2) set_gemm_geom(value);
-  else if (key == 3) set_gemm_splitk(value != 0);
-  else if (key == 4) g_raw_copies = value != 0;
-  else if (key == 5) g_flash_attention = value != 0;
-  else if (key == 6) g_fuse_gn_stats = value != 0;
-  else if (key == 7) g_fuse_geglu = value != 0;
-  else if (key == 8) set_gemm_ring(value);
-  else if (key == 9) g_lowp_h1 = value != 0;
-  else return T2P_ERR_INVALID;
+  if (refused) { set_last_error(k->refusal); return T2P_ERR_INVALID; }
+  if (k->rule != PlanKey::POSITIVE || value > 0) g_plan.*k->i = value;
   return T2P_OK;
 }
+int t2p_debug_get(int key, int* value) {
+  const PlanKey* k = plan_key(key);
+  if (!k || !value) return T2P_ERR_INVALID;
+  *value = k->b ? (int)(g_plan.*k->b) : g_plan.*k->i;
+  return T2P_OK;
+}
+const char* t2p_debug_key_name(int key) { const PlanKey* k = plan_key(key); return k ? k->name : nullptr; }
 
 #ifdef T2P_ABLATION
 extern "C" int t2p_ablation_dxs_stamps(unsigned long long* out, int n) { return t2p::dxs_stamps_read(out, n); }

@@ -13,16 +13,6 @@
 
 namespace t2p {
 
-bool g_fuse_gn_stats = true;
-bool g_fuse_geglu = true;
-bool g_lowp_h1 = true;
-bool g_gn_small = true;
-bool g_lowp_residual = true;
-bool g_raw_copies = true;
-bool g_flash_attention = true;
-bool g_attn_merged = true;    // AttnBlockpp: NIN_2 . NIN_3 as one projection, output epilogue in the attention kernel (plan switch 32)
-bool g_ffpo_merged = true;    // SpatialTransformer: ff.net.2 and proj_out as one GEMM over [g | t] (plan switch 33)
-bool g_qkv_fused = true;      // self-attention: one q | k | v projection, V read row-major by the fused kernel (plan switch 25)
 static thread_local std::string g_last_error;
 void set_last_error(const std::string& msg) { g_last_error = msg; }
 const char* get_last_error() { return g_last_error.c_str(); }
@@ -836,7 +826,7 @@ int Engine::gemm(GemmParams& p, hipStream_t s) {
 int Engine::gemm_stats(GemmParams& p, float** cstats, hipStream_t s) {
   *cstats = nullptr;
   T2P_TRY(attach_ws(p));          // the fuse predicate depends on the split-K decision
-  if (g_fuse_gn_stats && (gemm_fuses_col_stats(p) || gemm_fuses_col_stats_lowp(p))) {
+  if (g_plan.fuse_gn_stats && (gemm_fuses_col_stats(p) || gemm_fuses_col_stats_lowp(p))) {
     *cstats = (float*)pool_.get((size_t)(p.M / 64) * p.N * 2 * 4);
     if (!*cstats) return T2P_ERR_HIP;
     p.col_stats = *cstats;
@@ -876,7 +866,7 @@ int Engine::group_norm(const Act& x, const Act* x1, const DevNorm& n, float eps,
     g.x0 = (const float*)x.p; g.x1 = x1 ? (const float*)x1->p : nullptr; g.C0 = x.C; g.C1 = x1 ? x1->C : 0;
     g.B = B; g.H = x.H; g.W = x.W; g.G = n.G; g.gamma = n.gamma; g.beta = n.beta; g.silu = silu; g.down = down;
     g.dtype = dtype(); g.x0_lowp = x.lowp; g.eps = eps;
-    if (g_gn_small && gn_small_eligible(g)) {
+    if (g_plan.gn_small && gn_small_eligible(g)) {
       const size_t bytes = (size_t)B * x.H * x.W * C * dtype_size(dtype());
       POOL_GET(o, void*, bytes);
       g.out = o;
@@ -953,7 +943,7 @@ int Engine::res_block(Layer& L, const Act& x, const Act* skip, Act* out, int B, 
   // anyway) also emits it in the compute dtype, so the shortcut GEMM takes the LDS-DMA kernel
   void* xraw = nullptr;
   // (a 16-bit residual stream is already in the GEMM operand format: no raw copy)
-  const bool want_raw = g_raw_copies && L.has_conv2 && !L.down && dt != DT_F32 && !x.lowp;
+  const bool want_raw = g_plan.raw_copies && L.has_conv2 && !L.down && dt != DT_F32 && !x.lowp;
   T2P_TRY(group_norm(x, skip, L.gn0, 1e-6f, 1, L.down, B, &a0, s, want_raw ? &xraw : nullptr));
   // ---- 8x8 / 4x4 maps: each convolution with everything around it in ONE launch (small_conv_gn_kernel): a workgroup owns whole
   // samples x whole groups, so GroupNorm_1 + SiLU (conv0) and the first norm of the block that follows (conv1) need no second
@@ -979,7 +969,7 @@ int Engine::res_block(Layer& L, const Act& x, const Act* skip, Act* out, int B, 
     c1.gn_gamma = c1.groups ? hint.norm->gamma : nullptr; c1.gn_beta = c1.groups ? hint.norm->beta : nullptr;
     if (L.has_conv2) { c1.X0 = a0; c1.X1 = c1.CX1 ? a0 : nullptr; } else { c1.R = a0; }
     if (small_conv_eligible(c0) && small_conv_eligible(c1)) {
-      if (g_small_conv_fm && c0.ldw % 32 == 0 && c1.ldw % 32 == 0) {
+      if (g_plan.small_conv_fm && c0.ldw % 32 == 0 && c1.ldw % 32 == 0) {
         // fragment-major weight copies (whole cache lines per fragment load), made the first time the block takes this path
         if (!L.fm_conv0) {
           // never under a stream capture (the conversions would be recorded, not run, and the copies stay uninitialised: every later
@@ -1021,7 +1011,7 @@ int Engine::res_block(Layer& L, const Act& x, const Act* skip, Act* out, int B, 
         pre = pool_.get((size_t)rows_out * Cout * dtype_size(dt));
         if (!pre) return T2P_ERR_HIP;
       }
-      if (Ho * Wo == 64 && g_fuse_gn_stats) {
+      if (Ho * Wo == 64 && g_plan.fuse_gn_stats) {
         o_stats = (float*)pool_.get((size_t)(rows_out / 64) * Cout * 2 * 4);
         if (!o_stats) return T2P_ERR_HIP;
       }
@@ -1059,8 +1049,8 @@ int Engine::res_block(Layer& L, const Act& x, const Act* skip, Act* out, int B, 
     } else {
     // (maps of <= 64 pixels go through the single-launch GroupNorm, which takes its own statistics:
     // h1 stays fp32 there so that they are still taken from unrounded values)
-    if (g_lowp_h1 && dt != DT_F32 && g_fuse_gn_stats && gemm_fuses_col_stats(p) && (Ho * Wo) % 64 == 0 &&
-        !(g_gn_small && Ho * Wo <= 64)) {
+    if (g_plan.lowp_h1 && dt != DT_F32 && g_plan.fuse_gn_stats && gemm_fuses_col_stats(p) && (Ho * Wo) % 64 == 0 &&
+        !(g_plan.gn_small && Ho * Wo <= 64)) {
       p.c_f32 = 0;
       h1_lowp = gemm_fuses_col_stats_lowp(p);
       if (!h1_lowp) p.c_f32 = 1;
@@ -1153,7 +1143,7 @@ int Engine::res_block(Layer& L, const Act& x, const Act* skip, Act* out, int B, 
     pre = pool_.get((size_t)rows_out * Cout * dtype_size(dt));
     if (!pre) return T2P_ERR_HIP;
     pc.gn_gamma = hint.norm->gamma; pc.gn_beta = hint.norm->beta; pc.gn_groups = hint.norm->G; pc.gn_silu = hint.silu; pc.gn_eps = 1e-6f;
-    if ((Ho * Wo) % 64 == 0 && g_fuse_gn_stats) {
+    if ((Ho * Wo) % 64 == 0 && g_plan.fuse_gn_stats) {
       o_stats = (float*)pool_.get((size_t)(rows_out / 64) * Cout * 2 * 4);
       if (!o_stats) return T2P_ERR_HIP;
       pc.col_stats = o_stats;
@@ -1175,7 +1165,7 @@ int Engine::res_block(Layer& L, const Act& x, const Act* skip, Act* out, int B, 
 int Engine::attention(const void* q, long ldq, const void* k, long ldk, const void* vt, long ldvt, void* out, int B,
                       int heads, int nq, int nk, int d, float scale, hipStream_t s) {
   const int dt = dtype();
-  if (g_flash_attention && attention_flash_eligible(dt, d, ldq, ldk, ldvt, (long)heads * d))
+  if (g_plan.flash_attention && attention_flash_eligible(dt, d, ldq, ldk, ldvt, (long)heads * d))
     return launch_attention_flash(dt, q, ldq, k, ldk, vt, ldvt, out, B, heads, nq, nk, d, scale, s);
   if (attention_strip_eligible(dt, heads, nq, nk, d, ldq, ldk, ldvt, d))
     return launch_attention_strip(dt, q, ldq, k, ldk, vt, ldvt, out, d, B, nq, d, scale, s);
@@ -1225,8 +1215,8 @@ int Engine::attn_block(Layer& L, const Act& x, Act* out, int B, hipStream_t s) {
   const size_t es = dtype_size(dt);
   const long rows = (long)B * n, npad = (long)round_up((size_t)n, 8);
   const bool olp = res_lowp();
-  const bool merged = g_attn_merged && L.v3.w && attention_strip_eligible(dt, 1, n, n, C, 2 * C, 2 * C, npad, C) && (!x.lowp || olp);
-  if (merged && x.lowp && L.fm_qk && g_attn_proj) {
+  const bool merged = g_plan.attn_merged && L.v3.w && attention_strip_eligible(dt, 1, n, n, C, 2 * C, 2 * C, npad, C) && (!x.lowp || olp);
+  if (merged && x.lowp && L.fm_qk && g_plan.attn_proj) {
     // C = 256: GroupNorm apply, q | k and the transposed value projection as ONE launch over 32-row blocks (attn_proj_kernel)
     AttnProjArgs e;
     e.dtype = dt; e.B = B; e.n = n; e.C = C; e.npad = npad;
@@ -1240,7 +1230,7 @@ int Engine::attn_block(Layer& L, const Act& x, Act* out, int B, hipStream_t s) {
       POOL_GET(vt2, void*, (size_t)B * C * npad * es);
       e.qk = qk2; e.vt = vt2;
       void* kfm2 = nullptr;
-      if (g_attn_fm && npad == n && attention_strip_frag_major_ok(dt, n, C)) {     // K and V^T in the order the attention kernel streams them
+      if (g_plan.attn_fm && npad == n && attention_strip_frag_major_ok(dt, n, C)) {     // K and V^T in the order the attention kernel streams them
         kfm2 = pool_.get((size_t)rows * C * es);
         if (!kfm2) return T2P_ERR_HIP;
         e.k_fm = kfm2;
@@ -1250,7 +1240,7 @@ int Engine::attn_block(Layer& L, const Act& x, Act* out, int B, hipStream_t s) {
       const float att_scale2 = 1.f / std::sqrt((float)C);
       POOL_GET(y, float*, (size_t)rows * C * (olp ? es : 4));
       float* y_stats = nullptr;
-      if (g_fuse_gn_stats && n % 64 == 0) {
+      if (g_plan.fuse_gn_stats && n % 64 == 0) {
         y_stats = (float*)pool_.get((size_t)(rows / 64) * C * 2 * 4);
         if (!y_stats) return T2P_ERR_HIP;
       }
@@ -1282,7 +1272,7 @@ int Engine::attn_block(Layer& L, const Act& x, Act* out, int B, hipStream_t s) {
   pv.nz0 = B; pv.sA_z0 = 0; pv.sB_z0 = (long)n * C; pv.c_f32 = 0; pv.ldc = npad; pv.sC_z0 = (long)C * npad;
   T2P_TRY(attach_ws(pv));
   bool fm = false;
-  if (merged && g_attn_fm && npad == n && attention_strip_frag_major_ok(dt, n, C)) {
+  if (merged && g_plan.attn_fm && npad == n && attention_strip_frag_major_ok(dt, n, C)) {
     GemmParams tq = pq, tv = pv;
     tq.rows_per_batch = n; tq.frag_col0 = C; tq.frag_ns = C / 32; tq.frag_bstride = (long)n * C; tq.c_frag = qk;     // (placeholder pointers)
     tv.frag_col0 = 0; tv.frag_ns = n / 32; tv.frag_bstride = (long)n * C; tv.c_frag = qk; tv.C = qk;
@@ -1313,7 +1303,7 @@ int Engine::attn_block(Layer& L, const Act& x, Act* out, int B, hipStream_t s) {
     pool_.put(a);
     POOL_GET(y, float*, (size_t)rows * C * (olp ? es : 4));
     float* y_stats = nullptr;
-    if (g_fuse_gn_stats && n % 64 == 0) {
+    if (g_plan.fuse_gn_stats && n % 64 == 0) {
       y_stats = (float*)pool_.get((size_t)(rows / 64) * C * 2 * 4);
       if (!y_stats) return T2P_ERR_HIP;
     }
@@ -1348,14 +1338,8 @@ int Engine::attn_block(Layer& L, const Act& x, Act* out, int B, hipStream_t s) {
 // too: every workgroup streams 1.15 MB of weights for it, which pays only when the launch fills the chip (>= 8192 rows: cfg3
 // 16.26 -> 16.19 ms per step; at cfg5's 4096 rows 10.53 -> 10.55, so the three separate launches stay there).  With row-major weights
 // (half of every fetched line unused, each line fetched twice) the chain was slower everywhere: 16.83 -> 16.88 ms at cfg3.
-bool g_st_tail = true;
 // development key 43: fewest rows for which the block's last chain (with the third product) is taken; without the third product
 // (plan switch 42 off) the chain needs twice as many (measured at cfg5's 4096 rows: +0.02 ms without, -0.06 ms with it)
-int g_st_tail_rows = 4096;
-bool g_attn_proj = true;       // plan switch 46: the projections of an AttnBlockpp in one launch at C = 256 (attn_proj_kernel)
-bool g_attn_fm = true;         // plan switch 45: fragment-major K / V^T for the wide-head attention kernel (where the shapes allow it)
-bool g_st_ffpo = true;         // plan switch 42: the merged ff.net.2 / proj_out product inside the chain after the cross-attention
-bool g_small_conv_fm = true;   // plan switch 41: the small-map convolution kernel reads fragment-major weight copies
 int Engine::st_block(Layer& L, const Act& x, Act* out, int B, hipStream_t s) {
   const int C = x.C, n = x.H * x.W, dt = dtype(), heads = cfg_.n_heads, d = C / heads;
   const size_t es = dtype_size(dt);
@@ -1365,13 +1349,13 @@ int Engine::st_block(Layer& L, const Act& x, Act* out, int B, hipStream_t s) {
   // the block's own residual stream t: fp32, or the compute dtype together with the stream between blocks
   const bool tl = res_lowp();
   POOL_GET(t, float*, (size_t)rows * C * (tl ? es : 4));
-  const bool qkv_flash = g_qkv_fused && L.a1_qkv.w && g_flash_attention && attention_flash_eligible(dt, d, 3 * C, 3 * C, 3 * C, C);
+  const bool qkv_flash = g_plan.qkv_fused && L.a1_qkv.w && g_plan.flash_attention && attention_flash_eligible(dt, d, 3 * C, 3 * C, 3 * C, C);
   // GroupNorm -> proj_in -> LayerNorm_1 -> q | k | v as ONE launch where the row-block kernel applies (stfuse.hip)
   char* qkv_pre = nullptr;
   // the block's last launch (plan switch 42): to_out + residual -> LayerNorm_3 -> ff.net.0 (GEGLU) -> [g | t] W_ffpo + x in one kernel;
   // its column sums are accumulated by pairs of workgroups into a buffer the entry kernel zeroes
-  const bool mega = tl && x.lowp && qkv_flash && g_st_tail && g_st_ffpo && g_ffpo_merged && L.fm_ffpo && L.fm_ff1 && rows >= g_st_tail_rows && n % 64 == 0 &&
-                    g_fuse_geglu && L.a2_out.b && L.ff1.b;
+  const bool mega = tl && x.lowp && qkv_flash && g_plan.st_tail && g_plan.st_ffpo && g_plan.ffpo_merged && L.fm_ffpo && L.fm_ff1 && rows >= g_plan.st_tail_rows && n % 64 == 0 &&
+                    g_plan.fuse_geglu && L.a2_out.b && L.ff1.b;
   float* y2 = nullptr;
   float* y2_stats = nullptr;
   if (tl && x.lowp && qkv_flash) {
@@ -1386,7 +1370,7 @@ int Engine::st_block(Layer& L, const Act& x, Act* out, int B, hipStream_t s) {
     e.w_qkv = L.fm_qkv; e.n2 = 3 * C;
     // (no column sums and no producer-side norm -- the 4 x 4 level: the GroupNorm as its own small launch, the rest of the chain here)
     void* a_small = nullptr;
-    if (!normed && !x.cstats && L.proj_in.b && L.fm_in && g_st_fuse) {
+    if (!normed && !x.cstats && L.proj_in.b && L.fm_in && g_plan.st_fuse) {
       StEntryArgs probe = e;
       probe.x = x.p; probe.cstats = nullptr;
       if (st_entry_eligible(probe)) {
@@ -1400,7 +1384,7 @@ int Engine::st_block(Layer& L, const Act& x, Act* out, int B, hipStream_t s) {
       if (mega) {
         y2 = (float*)pool_.get((size_t)rows * C * es);
         if (!y2) return T2P_ERR_HIP;
-        if (g_fuse_gn_stats) {
+        if (g_plan.fuse_gn_stats) {
           y2_stats = (float*)pool_.get((size_t)(rows / 64) * C * 2 * 4);
           if (!y2_stats) return T2P_ERR_HIP;
           e.zero = y2_stats; e.zero_n = (long)(rows / 64) * C * 2;
@@ -1470,7 +1454,7 @@ int Engine::st_block(Layer& L, const Act& x, Act* out, int B, hipStream_t s) {
     e.dtype = dt; e.B = B; e.n = n; e.C = C; e.x = o; e.w_in = L.fm_out2; e.b_in = L.a2_out.b; e.res = t;
     e.ln_gamma = L.ln3.gamma; e.ln_beta = L.ln3.beta; e.ln_eps = 1e-5f; e.w_qkv = L.fm_ff1; e.b2 = L.ff1.b; e.n2 = 8 * C; e.geglu = 1;
     e.t = t; e.qkv = g;
-    const bool tail_chain = tl && qkv_pre && g_st_tail && (y2 || rows >= 2 * g_st_tail_rows) && L.fm_ff1 && g_fuse_geglu && gemm_fuses_geglu(p) && L.a2_out.b && L.ff1.b && st_entry_eligible(e);
+    const bool tail_chain = tl && qkv_pre && g_plan.st_tail && (y2 || rows >= 2 * g_plan.st_tail_rows) && L.fm_ff1 && g_plan.fuse_geglu && gemm_fuses_geglu(p) && L.a2_out.b && L.ff1.b && st_entry_eligible(e);
     if (tail_chain && y2) {
       e.w3 = L.fm_ffpo; e.b3 = L.ffpo.b; e.res3 = x.p; e.y = y2; e.y_stats = y2_stats; e.qkv = nullptr;
       T2P_REQUIRE(st_entry_eligible(e), "row chain with the third product");
@@ -1487,7 +1471,7 @@ int Engine::st_block(Layer& L, const Act& x, Act* out, int B, hipStream_t s) {
       T2P_TRY(launch_layernorm(t, L.ln3.gamma, L.ln3.beta, ln, dt, rows, C, 1e-5f, s, tl));
     }
     if (tail_chain) {
-    } else if (g_fuse_geglu && gemm_fuses_geglu(p)) {
+    } else if (g_plan.fuse_geglu && gemm_fuses_geglu(p)) {
       T2P_TRY(gemm(p, s));                       // value * gelu(gate) in the GEMM epilogue
     } else {
       POOL_GET(u, float*, (size_t)rows * 8 * C * 4);
@@ -1495,7 +1479,7 @@ int Engine::st_block(Layer& L, const Act& x, Act* out, int B, hipStream_t s) {
       T2P_TRY(launch_geglu(u, g, dt, rows, 4 * C, s, 1));
       pool_.put(u);
     }
-    if (g_ffpo_merged && tl && L.ffpo.w) {
+    if (g_plan.ffpo_merged && tl && L.ffpo.w) {
       // ff.net.2 and proj_out as ONE product over [g | t] (Layer::ffpo): x + proj_out(t + ff2(g)), attention.py:213-215, 259-263
       pool_.put(o);
       const bool olp2 = res_lowp();
@@ -1522,7 +1506,7 @@ int Engine::st_block(Layer& L, const Act& x, Act* out, int B, hipStream_t s) {
   float* y_stats = nullptr;
   if (tl) {                                              // t already is a GEMM operand
     T2P_TRY(linear(t, false, L.proj_out, rows, y, !olp, x.p, 1.f, s, true, &y_stats, x.lowp));
-  } else if (dt != DT_F32 && g_raw_copies) {
+  } else if (dt != DT_F32 && g_plan.raw_copies) {
     T2P_TRY(launch_convert(t, ln, dt, rows * C, s));     // residual stream -> compute dtype (reuses the LN buffer)
     T2P_TRY(linear(ln, false, L.proj_out, rows, y, !olp, x.p, 1.f, s, true, &y_stats, x.lowp));
   } else {
@@ -1645,7 +1629,7 @@ int Engine::score(const float* x, const int* labels, const int* step_counter, fl
   if ((Cx == 5 || Cx == 8) && pre_conv_direct_) {
     // 16-bit modes: the GroupNorm column statistics of h0 (read by the first block and, through the skip stack, by the last
     // stage) come out of the input convolution instead of two passes over the tensor
-    if (hlp && g_fuse_gn_stats && pre_conv_fuses_col_stats(L, arch_.nf) && !(g_gn_small && HW <= 64)) {
+    if (hlp && g_plan.fuse_gn_stats && pre_conv_fuses_col_stats(L, arch_.nf) && !(g_plan.gn_small && HW <= 64)) {
       h0_stats = (float*)pool_.get((size_t)B * (HW / 64) * arch_.nf * 2 * 4);
       if (!h0_stats) return T2P_ERR_HIP;
     }

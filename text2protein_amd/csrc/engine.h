@@ -192,7 +192,7 @@ class Engine {
              float alpha, hipStream_t s, bool use_bias = true, float** cstats = nullptr, bool r_lowp = false);
   // the residual stream between blocks is stored in the compute dtype (f16 mode only): halves the HBM-bound
   // traffic of GroupNorm-apply and of the residual / output halves of the block-closing GEMM epilogues
-  bool res_lowp() const { return g_lowp_residual && cfg_.compute_dtype == DT_F16; }
+  bool res_lowp() const { return g_plan.lowp_residual && cfg_.compute_dtype == DT_F16; }
 
   t2p_model_config cfg_;
   NetArch arch_;

@@ -144,8 +144,6 @@ inline void prof_shape(ProfRec& r, const GemmParams& p) {
 struct DmaPlan { int geom, nsplit; };
 extern bool g_prof_on;
 extern std::vector<ProfRec> g_prof;
-extern int g_dma_ring, g_dbg;
-extern bool g_up4, g_deep_ring, g_dxs;
 int num_cus();
 DmaPlan dma_plan(const GemmParams& p);
 int launch_splitk_reduce(const GemmParams& p, int nsplit, hipStream_t stream);
@@ -1892,20 +1890,6 @@ static int launch_t(const GemmParams& p, hipStream_t stream) {
   return T2P_OK;
 }
 
-// 128 x 64 wave-tile geometries: 2 = 2 + 2 ring stages with v_mfma_16x16x32 (default: +5 % over the
-// 32x32x16 shape, it sustains a higher clock); 1 = 2 + 2 stages, 32x32x16; 0 = 3 A + 2 B stages
-// (160 KiB; measured equal to 1)
-int g_dma_ring = 2;
-void set_gemm_ring(int v) { g_dma_ring = v; }
-bool g_dxs = true;            // plan switch 47: full-resolution 3x3 convolutions on the dx-shared-stage kernel (gemm_dxs_kernel) where eligible
-void set_gemm_dxs(bool on) { g_dxs = on; }
-static int g_dma_geom = 0;   // 0 auto, 1 force 256x128x3, 2 force 128x128x2, 3 force 256x256x2, 4 force 512x128x2
-static bool g_splitk = true;
-static int g_force_nsplit = 0;   // development: > 0 forces that split-K factor wherever a workspace is attached
-void set_gemm_force_nsplit(int v) { g_force_nsplit = v; }
-static bool g_use_dma = true;
-bool g_deep_ring = true;    // small launches of the 128 x 128 geometry on a 4-stage ring (plan switch 22)
-void set_gemm_deep_ring(bool on) { g_deep_ring = on; }
 int num_cus() {
   static int n[16] = {0};
   int dev = 0;
@@ -1916,14 +1900,9 @@ int num_cus() {
   }
   return n[dev];
 }
-bool g_up4 = true;          // up-sampling 3x3 convolutions as four 2x2 phase convolutions where the caller supplies Bw4 (plan switch 21)
-void set_gemm_up4(bool on) { g_up4 = on; }
-int g_dbg = 0;   // timing-only ablations (results are wrong when non-zero): 1 no epilogue, 2 no DMA in loop, 4 no reads/MFMA
-void set_gemm_dma(bool on) { g_use_dma = on; }
-void set_gemm_debug(int v) { g_dbg = v; }
 
 static bool dma_eligible(const GemmParams& p) {
-  if (!g_use_dma || p.dtype == DT_F32 || p.a_f32) return false;
+  if (!g_plan.dma || p.dtype == DT_F32 || p.a_f32) return false;
   if (p.C0 % 64 != 0 || p.C1 % 64 != 0) return false;   // whole 64-channel K-tiles only (else v1)
   if (p.M < 128 || p.N < 64) return false;              // small problems: v1's 64x64 tiles fill the chip better
   if (p.a_up && p.taps != 9) return false;
@@ -2167,20 +2146,7 @@ __global__ __launch_bounds__(1024) void splitk_reduce_gn_kernel(const GemmParams
   }
 }
 
-static bool g_post_gn = true;     // plan switch 28
-void set_gemm_post_gn(bool on) { g_post_gn = on; }
-void set_gemm_splitk(bool on) { g_splitk = on; }
-
-void set_gemm_geom(int v) { g_dma_geom = v; }
-
-// Tile geometry (0: 256x128x3, 1: 256x256x2, 2: 128x128x2, 3: 512x128x2) and split-K factor of a launch.
-static bool g_midsplit = false;  // mid-size problems: 256x256 tiles + split-K instead of 128x128 tiles (round 1 default; with the
-                                 // 4-stage 128x128 ring the unsplit plan is as fast and saves the second pass: -0.27 ms at cfg2)
-void set_gemm_midsplit(bool on) { g_midsplit = on; }
-
-static int g_split_tiles = 192, g_split_target = 256;     // plan constants (development keys 30 / 31)
-void set_gemm_split_consts(int tiles, int target) { if (tiles > 0) g_split_tiles = tiles; if (target > 0) g_split_target = target; }
-
+// Tile geometry (0: 256x128x3, 1: 256x256x2, 2: 128x128x2, 3: 512x128x2) and split-K factor of a launch (the switches: plan.h).
 DmaPlan dma_plan(const GemmParams& p) {
   const long z = (long)p.nz0 * p.nz1;
   const int nk = ((p.C0 + p.C1 + 63) / 64) * p.taps + (p.CX0 + p.CX1) / 64;
@@ -2188,10 +2154,10 @@ DmaPlan dma_plan(const GemmParams& p) {
   auto fits = [&](int ns) { return (size_t)ns * p.M * p.N * 4 <= p.ws_bytes; };
   const long t256 = (long)((p.M + 255) / 256) * ((p.N + 255) / 256) * z;
   int geom;
-  if (g_dma_geom == 1) geom = 0;
-  else if (g_dma_geom == 2) geom = 2;
-  else if (g_dma_geom == 3) geom = 1;
-  else if (g_dma_geom == 4) geom = 3;
+  if (g_plan.dma_geom == 1) geom = 0;
+  else if (g_plan.dma_geom == 2) geom = 2;
+  else if (g_plan.dma_geom == 3) geom = 1;
+  else if (g_plan.dma_geom == 4) geom = 3;
   else if (p.M < 256) geom = 2;
   else {
     // largest tile that still gives about one workgroup per CU: big tiles are 15-20 % more efficient
@@ -2199,11 +2165,11 @@ DmaPlan dma_plan(const GemmParams& p) {
     // workgroups is latency-bound and finishes sooner with more, smaller tiles
     const long t128 = (long)((p.M + 255) / 256) * ((p.N + 127) / 128) * z;
     const long t512 = (long)((p.M + 511) / 512) * ((p.N + 127) / 128) * z;
-    if (g_dma_geom == 5) geom = (p.N >= 256 && p.N % 256 == 0) ? 1 : 0;   // former policy, kept for A/B
+    if (g_plan.dma_geom == 5) geom = (p.N >= 256 && p.N % 256 == 0) ? 1 : 0;   // former policy, kept for A/B
     else if (p.N % 256 == 0 && t256 >= 200) geom = 1;
-    else if (g_dma_geom != 6 && p.N <= 128 && t512 >= 200) geom = 3;      // narrow outputs: tall tile, same 128x64 wave tile
+    else if (g_plan.dma_geom != 6 && p.N <= 128 && t512 >= 200) geom = 3;      // narrow outputs: tall tile, same 128x64 wave tile
     else if (t128 >= 200) geom = 0;
-    else if (g_midsplit && g_splitk && !g_force_nsplit && can_split && p.N % 256 == 0 && t256 >= 48 && nk >= 32 &&
+    else if (g_plan.midsplit && g_plan.splitk && !g_plan.force_nsplit && can_split && p.N % 256 == 0 && t256 >= 48 && nk >= 32 &&
              std::min<long>(256 / t256, nk / 8) >= 2 && fits((int)std::min<long>(256 / t256, nk / 8))) {
       // long-K problem with 48..128 big tiles (conv at the 16x16 level of cfg2): the 128x128 geometry would
       // run one 4-wave workgroup per CU (320-470 TFLOP/s measured); 256x256 tiles with the K loop split so
@@ -2215,25 +2181,23 @@ DmaPlan dma_plan(const GemmParams& p) {
   const int BM = geom == 2 ? 128 : (geom == 3 ? 512 : 256), BN = geom == 1 ? 256 : 128;
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
   int nsplit = 1;
-  if (g_force_nsplit > 0) {
-    if (can_split && g_force_nsplit > 1 && nk >= 2 * g_force_nsplit) nsplit = g_force_nsplit;
-  } else if (g_splitk && can_split && tiles < g_split_tiles && nk >= 16) {
+  if (g_plan.force_nsplit > 0) {
+    if (can_split && g_plan.force_nsplit > 1 && nk >= 2 * g_plan.force_nsplit) nsplit = g_plan.force_nsplit;
+  } else if (g_plan.splitk && can_split && tiles < g_plan.split_tiles && nk >= 16) {
     // the tile grid cannot fill the chip and the K loop is long (low-resolution levels)
     // (tiles x splits ~ one workgroup per CU: a target of 256 measured 0.2 ms per step better than 384 at cfg2 and cfg3,
     // 128 .. 192 and 320 .. 768 worse; at least 4 K-tiles per split, 2 .. 12 within noise)
-    nsplit = std::min(std::min(nk / 4, (g_split_target + tiles - 1) / tiles), 32);
+    nsplit = std::min(std::min(nk / 4, (g_plan.split_target + tiles - 1) / tiles), 32);
   }
   while (nsplit > 1 && !fits(nsplit)) --nsplit;
   // 128 x 128 tiles on at most one workgroup per CU: such a launch is bound by the latency of its K-steps (0.47 us each with
   // the 2-stage ring: every step waits for the DMA issued one step earlier), so it takes the 4-stage ring (geometry 4: the
   // same tile with three K-tiles in flight, 128 KiB of LDS)
-  if (geom == 2 && g_deep_ring && (long)tiles * nsplit * z <= num_cus()) geom = 4;
+  if (geom == 2 && g_plan.deep_ring && (long)tiles * nsplit * z <= num_cus()) geom = 4;
   return {geom, nsplit};
 }
-bool g_fuse_shortcut = true;
-void set_gemm_fuse_shortcut(bool on) { g_fuse_shortcut = on; }
 bool gemm_can_fuse_shortcut(const GemmParams& p) {
-  return g_fuse_shortcut && dma_eligible(p) && p.taps == 9 && !p.a_up;
+  return g_plan.fuse_shortcut && dma_eligible(p) && p.taps == 9 && !p.a_up;
 }
 static bool dma_uses_splitk(const GemmParams& p) { return dma_plan(p).nsplit > 1; }
 static int dma_pick_geom(const GemmParams& p) { return dma_plan(p).geom; }
@@ -2247,7 +2211,7 @@ static bool splitk_reduce_vec_ok(const GemmParams& p) {
 // the second pass can apply a following GroupNorm: split-K launch whose samples are blocks of <= 256 rows, whole groups per
 // 64-column slab, no per-chunk column statistics wanted on top
 bool gemm_fuses_post_gn(const GemmParams& p, int groups) {
-  if (!g_post_gn || !dma_eligible(p) || p.nz0 * p.nz1 != 1 || p.dtype == DT_F32 || !dma_uses_splitk(p) || !splitk_reduce_vec_ok(p)) return false;
+  if (!g_plan.post_gn || !dma_eligible(p) || p.nz0 * p.nz1 != 1 || p.dtype == DT_F32 || !dma_uses_splitk(p) || !splitk_reduce_vec_ok(p)) return false;
   const int HW = p.rows_per_batch;
   if (HW < 1 || HW > 256 || p.M % HW != 0 || p.bias_m || p.c_nchw || (p.col_stats && HW % 64 != 0)) return false;
   if (p.r_up && (HW != p.H * p.W)) return false;
@@ -2312,7 +2276,7 @@ bool gemm_fuses_col_stats(const GemmParams& p) {
 // GemmParams::c_frag: a plain product on the 256 x 256 register-epilogue kernel, 16-bit output, whole 32-row x 32-column fragments
 bool gemm_writes_frag_major(const GemmParams& p) {
   if (!dma_eligible(p) || p.taps != 1 || p.c_f32 || p.geglu || p.col_stats || p.gn_out || p.r_up || p.c_nchw) return false;
-  if (g_dma_ring != 2 || g_dma_geom != 0) return false;
+  if (g_plan.dma_ring != 2 || g_plan.dma_geom != 0) return false;
   const DmaPlan plan = dma_plan(p);
   if (plan.geom != 1 || plan.nsplit != 1 || !reg_epilogue_ok(p, 1, 0)) return false;
   if (p.frag_col0 < 0 || p.frag_col0 % 64 != 0 || (p.N - p.frag_col0) % 32 != 0 || p.frag_ns != (p.N - p.frag_col0) / 32) return false;
@@ -2328,7 +2292,7 @@ static int launch_dma_geom(const GemmParams& p, hipStream_t stream) {
   constexpr int smem = NST * BM * 128 + NSTB * BN * 128;
   constexpr int threads = WM * WN * 64;
   if constexpr (MF16 && !REGE && MODE != 3) {          // the register epilogue wherever it covers the launch
-    if (reg_epilogue_ok(p, dma_plan(p).nsplit, g_dbg)) return launch_dma_geom<TC, MODE, BM, BN, WM, WN, NST, NSTB, true, true>(p, stream);
+    if (reg_epilogue_ok(p, dma_plan(p).nsplit, g_plan.dbg)) return launch_dma_geom<TC, MODE, BM, BN, WM, WN, NST, NSTB, true, true>(p, stream);
   }
   void (*kern)(const GemmParams, const int, const int, const int);
   if constexpr (CF) kern = gemm_dma_cfrag_kernel<TC, BM, BN, WM, WN, MODE, NST, NSTB>;     // part of the output fragment-major (GemmParams::c_frag)
@@ -2361,7 +2325,7 @@ static int launch_dma_geom(const GemmParams& p, hipStream_t stream) {
     }
     T2P_HIP_CHECK(hipEventRecord(rec.a, stream));
   }
-  hipLaunchKernelGGL(kern, grid, dim3(threads), smem, stream, p, tiles_m, tiles_n, g_dbg);
+  hipLaunchKernelGGL(kern, grid, dim3(threads), smem, stream, p, tiles_m, tiles_n, g_plan.dbg);
   if (g_prof_on) T2P_HIP_CHECK(hipEventRecord(rec.b, stream));   // the main kernel only: comparable with rocprofv3's per-kernel average
   if (nsplit > 1) T2P_TRY(launch_splitk_reduce(p, nsplit, stream));
   if (g_prof_on) g_prof.push_back(rec);
@@ -2371,7 +2335,7 @@ static int launch_dma_geom(const GemmParams& p, hipStream_t stream) {
 
 // the dx-shared-stage kernel applies: a 3x3 convolution at full resolution on the 16x16x32 geometries whose tiles are whole image rows
 static bool dxs_eligible(const GemmParams& p, const DmaPlan& plan) {
-  if (!g_dxs || p.taps != 9 || p.a_up || plan.nsplit != 1 || (plan.geom != 1 && plan.geom != 3) || g_dma_ring != 2) return false;
+  if (!g_plan.dxs || p.taps != 9 || p.a_up || plan.nsplit != 1 || (plan.geom != 1 && plan.geom != 3) || g_plan.dma_ring != 2) return false;
   if (p.nz0 * p.nz1 != 1 || p.c_frag || p.geglu) return false;
   const int BM = plan.geom == 1 ? 256 : 512, HW = p.H * p.W;
   if (p.W % 64 != 0 || (p.W & (p.W - 1)) != 0 || BM % p.W != 0 || HW % BM != 0 || p.M % HW != 0) return false;
@@ -2400,7 +2364,7 @@ static int launch_dxs(const GemmParams& p, hipStream_t stream) {
                 (p.R ? (double)p.M * p.N * (p.r_lowp ? 2 : 4) : 0.0) + (p.bias_bn ? (double)(p.M / p.rows_per_batch) * p.N * 4 : 0.0);
     T2P_HIP_CHECK(hipEventRecord(rec.a, stream));
   }
-  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(WM * WN * 64), smem, stream, p, tiles_m, tiles_n, g_dbg);
+  hipLaunchKernelGGL(kern, dim3(tiles_m * tiles_n), dim3(WM * WN * 64), smem, stream, p, tiles_m, tiles_n, g_plan.dbg);
   if (g_prof_on) {
     T2P_HIP_CHECK(hipEventRecord(rec.b, stream));
     g_prof.push_back(rec);
@@ -2412,13 +2376,13 @@ static int launch_dxs(const GemmParams& p, hipStream_t stream) {
 // a 3x3 convolution on a 2x up-sampled map as four 2x2 convolutions on the source map (kernel MODE 3): the caller supplied
 // the phase weights (GemmParams::Bw4), the 16x16x32 geometries with the register epilogue run it
 static bool up4_eligible(const GemmParams& p, const DmaPlan& plan) {
-  if (!g_up4 || !p.Bw4 || p.taps != 9 || !p.a_up || plan.nsplit != 1 || (plan.geom != 1 && plan.geom != 3) || g_dma_ring != 2) return false;
+  if (!g_plan.up4 || !p.Bw4 || p.taps != 9 || !p.a_up || plan.nsplit != 1 || (plan.geom != 1 && plan.geom != 3) || g_plan.dma_ring != 2) return false;
   if (p.nz0 * p.nz1 != 1 || p.R || p.bias_m || p.geglu || p.A1) return false;
   const int Ws = p.W / 2, HWs = (p.H / 2) * (p.W / 2);
   if (p.H % 2 || p.W % 2 || Ws % 16 != 0 || HWs % 64 != 0 || p.M % (p.H * p.W) != 0) return false;
   if (p.bias_bn && p.rows_per_batch != p.H * p.W) return false;
   if ((long)p.N * p.ldb4 * 2 * 4 >= (1L << 31) - 64) return false;
-  return reg_epilogue_ok(p, 1, g_dbg);
+  return reg_epilogue_ok(p, 1, g_plan.dbg);
 }
 
 template <typename TC, int MODE>
@@ -2448,12 +2412,12 @@ int launch_dma_mode(const GemmParams& p, hipStream_t stream) {
   }
   switch (plan.geom) {
     case 1:
-      if (g_dma_ring == 2) return launch_dma_geom<TC, MODE, 256, 256, 2, 4, 2, 2, true>(p, stream);   // 16x16x32 MFMA
+      if (g_plan.dma_ring == 2) return launch_dma_geom<TC, MODE, 256, 256, 2, 4, 2, 2, true>(p, stream);   // 16x16x32 MFMA
       return launch_dma_geom<TC, MODE, 256, 256, 2, 4, 2>(p, stream);      // ring 1: the 32x32x16 MFMA shape on the same tile
     case 2: return launch_dma_geom<TC, MODE, 128, 128, 2, 2, 2>(p, stream);
     case 4: return launch_dma_geom<TC, MODE, 128, 128, 2, 2, 4>(p, stream);
     case 3:
-      if (g_dma_ring == 2) return launch_dma_geom<TC, MODE, 512, 128, 4, 2, 2, 2, true>(p, stream);
+      if (g_plan.dma_ring == 2) return launch_dma_geom<TC, MODE, 512, 128, 4, 2, 2, 2, true>(p, stream);
       return launch_dma_geom<TC, MODE, 512, 128, 4, 2, 2>(p, stream);
     default: return launch_dma_geom<TC, MODE, 256, 128, 4, 2, 3>(p, stream);
   }
@@ -2578,11 +2542,6 @@ __global__ __launch_bounds__(512) void thin_conv_kernel(const ThinConvArgs a) {
   }
 }
 
-static bool g_thin_conv = true;
-static bool g_a_norm = true;         // GroupNorm + SiLU of the head inside the head convolution's halo staging (plan switch 34)
-void set_gemm_thin_conv(bool on) { g_thin_conv = on; }
-void set_gemm_a_norm(bool on) { g_a_norm = on; }
-
 // true when launch_gemm(p) will take the thin-output kernel
 static bool thin_conv_eligible(const GemmParams& p) {
   if (p.dtype == DT_F32 || p.a_f32 || p.taps != 9 || p.a_up || !p.c_nchw || !p.c_f32) return false;
@@ -2591,7 +2550,7 @@ static bool thin_conv_eligible(const GemmParams& p) {
   return p.rows_per_batch == p.H * p.W && p.M % (p.H * p.W) == 0;
 }
 
-bool gemm_applies_a_norm(const GemmParams& p) { return g_thin_conv && g_a_norm && thin_conv_eligible(p) && p.C0 <= 256; }
+bool gemm_applies_a_norm(const GemmParams& p) { return g_plan.thin_conv && g_plan.a_norm && thin_conv_eligible(p) && p.C0 <= 256; }
 
 template <typename TC, int CH>
 static int launch_thin_conv_ch(const ThinConvArgs& a, hipStream_t stream) {
@@ -2616,10 +2575,10 @@ static int launch_thin_conv(const GemmParams& p, hipStream_t stream) {
 // launch_gemm takes the row-resident kernel (rowgemm.hip), given its copy of the weights: switch 49 at 2: wherever it is eligible; at 1:
 // from 128 workgroups of 128 rows on, and where the plan it replaces is the 256 x 256 16x16x32 kernel, whose bits it reproduces
 bool gemm_rowres_planned(const GemmParams& p) {
-  if (!g_rowres || g_dbg || !dma_eligible(p) || !gemm_rowres_eligible(p)) return false;
+  if (!g_plan.rowres || g_plan.dbg || !dma_eligible(p) || !gemm_rowres_eligible(p)) return false;
   const DmaPlan plan = dma_plan(p);
   if (plan.nsplit != 1) return false;
-  return g_rowres == 2 || (p.M / 128 >= 128 && plan.geom == 1 && g_dma_ring == 2);
+  return g_plan.rowres == 2 || (p.M / 128 >= 128 && plan.geom == 1 && g_plan.dma_ring == 2);
 }
 
 int launch_gemm(const GemmParams& p, hipStream_t stream) {
@@ -2671,7 +2630,7 @@ int launch_gemm(const GemmParams& p, hipStream_t stream) {
     T2P_REQUIRE(p.an_gamma && p.an_beta && p.an_groups > 0 && p.C0 % p.an_groups == 0 && gemm_applies_a_norm(q),
                 "a GroupNorm of the A operand rides only on the thin-output head convolution (ask gemm_applies_a_norm)");
   }
-  if (g_thin_conv && thin_conv_eligible(p)) {
+  if (g_plan.thin_conv && thin_conv_eligible(p)) {
     // the head convolution: timed as "conv on the register-staged kernel" by the profile hooks' kind 2
     ProfRec rec;
     if (g_prof_on) {

@@ -222,7 +222,6 @@ __device__ inline float silu_fast(float x) {
 // (rstd*gamma, beta - mean*rstd*gamma) are computed once, then it walks output pixels with 32-bit
 // indexing; consecutive lanes cover consecutive channels (coalesced 16-byte loads, 8/16-byte stores).
 static constexpr int GNA_PIX_PER_BLOCK = 64;      // 32 .. 256 measured equal within 0.3 % of a step
-bool g_gn_apply16 = true;     // 16-bit GroupNorm apply with 16-byte accesses (plan switch 17)
 
 template <typename TO, typename TI>
 __global__ __launch_bounds__(256) void gn_apply_kernel(GroupNormApplyArgs a, int pix_per_block) {
@@ -396,10 +395,9 @@ __global__ __launch_bounds__(256) void gn_apply_cols_kernel(GroupNormApplyArgs a
   for (; p < p_hi; p += 32) apply(*(const u4*)(src + (long)p * ld), p);
 }
 
-bool g_gn_apply_cols = true;       // plan switch 27
 bool gn_apply_cols_eligible(const GroupNormApplyArgs& a) {
   const int C = a.C0 + a.C1, HW = a.H * a.W;
-  if (!g_gn_apply_cols || !a.cs0 || (a.C1 > 0) != (a.cs1 != nullptr) || a.dtype == DT_F32 || !a.x0_lowp || a.down || a.raw_out) return false;
+  if (!g_plan.gn_apply_cols || !a.cs0 || (a.C1 > 0) != (a.cs1 != nullptr) || a.dtype == DT_F32 || !a.x0_lowp || a.down || a.raw_out) return false;
   if (a.C0 % 64 != 0 || a.C1 % 64 != 0 || C % a.G != 0 || 64 % (C / a.G) != 0) return false;
   return HW % 64 == 0 && HW <= 4096;
 }
@@ -432,7 +430,7 @@ int launch_gn_apply(const GroupNormApplyArgs& a, hipStream_t s) {
   if (ppi > 1) ppb = (ppb + ppi - 1) / ppi * ppi;
   dim3 grid((HWo + ppb - 1) / ppb, a.B, zb);
   T2P_REQUIRE(!a.x0_lowp || a.dtype != DT_F32, "16-bit GroupNorm input needs a 16-bit dtype (both sources are then 16-bit)");
-  if (g_gn_apply16 && a.x0_lowp && !a.down && !a.raw_out && a.C0 % 8 == 0 && a.C1 % 8 == 0 && C >= 64 && C <= 2048 && 256 % (C / 8) == 0) {
+  if (g_plan.gn_apply16 && a.x0_lowp && !a.down && !a.raw_out && a.C0 % 8 == 0 && a.C1 % 8 == 0 && C >= 64 && C <= 2048 && 256 % (C / 8) == 0) {
     const int ppi8 = 256 / (C / 8);
     long want8 = ((long)HWo * a.B + 2047) / 2048;
     int ppb8 = (int)std::min<long>(GNA_PIX_PER_BLOCK, std::max<long>(want8, ppi8));
@@ -594,7 +592,6 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const TI* x, const float
 
 // 16-bit in / out, C = 512 NV (512 or 1024 channels: the transformer widths at nf = 256): a wavefront owns a row, a lane
 // keeps its 8 NV elements in registers (one 16-byte load each), so the row is read once; two-pass mean / variance as above.
-bool g_layernorm16 = true;      // plan switch 20
 template <typename T, int NV>
 __global__ __launch_bounds__(256) void layernorm16_kernel(const T* x, const float* gamma, const float* beta, T* out, long rows, float eps) {
   typedef unsigned u4 __attribute__((ext_vector_type(4)));
@@ -641,7 +638,7 @@ int launch_layernorm(const float* x, const float* gamma, const float* beta, void
   T2P_REQUIRE(x && gamma && beta && out && C % 4 == 0 && rows > 0, "layernorm arguments");
   T2P_REQUIRE(!x_lowp || dtype != DT_F32, "16-bit LayerNorm input needs a 16-bit dtype");
   dim3 grid((unsigned)((rows + 3) / 4));
-  if (g_layernorm16 && x_lowp && dtype != DT_F32 && (C == 512 || C == 1024)) {
+  if (g_plan.layernorm16 && x_lowp && dtype != DT_F32 && (C == 512 || C == 1024)) {
     if (dtype == DT_F16) {
       if (C == 512) hipLaunchKernelGGL((layernorm16_kernel<f16_t, 1>), grid, dim3(256), 0, s, (const f16_t*)x, gamma, beta, (f16_t*)out, rows, eps);
       else hipLaunchKernelGGL((layernorm16_kernel<f16_t, 2>), grid, dim3(256), 0, s, (const f16_t*)x, gamma, beta, (f16_t*)out, rows, eps);
@@ -1231,10 +1228,9 @@ __global__ __launch_bounds__(256) void pre_conv_split_kernel(const float* x, con
   }
 }
 
-bool g_pre_conv_split = true;     // plan switch 38
 size_t pre_conv_split_weight_bytes(int C, int nf) { return (size_t)nf * (C == 5 ? PreSplit<5>::KP : PreSplit<8>::KP) * 2; }
 bool pre_conv_split_ok(int out_dtype, int C, int H, int W, int nf) {
-  return g_pre_conv_split && out_dtype != DT_F32 && (C == 5 || C == 8) && W % 64 == 0 && H % 2 == 0 && (nf == 256 || nf == 128 || nf == 64);
+  return g_plan.pre_conv_split && out_dtype != DT_F32 && (C == 5 || C == 8) && W % 64 == 0 && H % 2 == 0 && (nf == 256 || nf == 128 || nf == 64);
 }
 int launch_pre_conv_split_weights(const float* w, void* wsplit, int C, int nf, hipStream_t s) {
   T2P_REQUIRE(w && wsplit && (C == 5 || C == 8), "pre_conv_split_weights arguments");
@@ -1266,9 +1262,8 @@ int launch_pre_conv_split(const float* x, const void* wsplit, const float* bias,
   return T2P_OK;
 }
 
-bool g_pre_conv_mfma = true;      // plan switch 26
 static bool pre_conv_mfma_ok(int out_dtype, int C, int W, int nf) {
-  return g_pre_conv_mfma && out_dtype != DT_F32 && (C == 5 || C == 8) && W % 64 == 0 && (nf == 256 || nf == 128 || nf == 64);
+  return g_plan.pre_conv_mfma && out_dtype != DT_F32 && (C == 5 || C == 8) && W % 64 == 0 && (nf == 256 || nf == 128 || nf == 64);
 }
 
 // the thread layout (a thread = one channel, pixel groups of 4) yields whole 64-pixel chunks without atomics when:

@@ -22,7 +22,6 @@
 
 namespace t2p {
 
-int g_rowres = 1;          // plan switch 49: 0 off, 1 the planner's choice, 2 wherever gemm_rowres_eligible
 long g_rowres_launches = 0; // launches of the kernel since the library was loaded (tests: which plan a launch took)
 
 bool gemm_rowres_eligible(const GemmParams& p) {

@@ -289,10 +289,9 @@ __global__ __launch_bounds__(512) void small_conv_gn_kernel(const SmallConvArgs 
   }
 }
 
-bool g_small_conv = true;          // plan switch 36
 
 bool small_conv_eligible(const SmallConvArgs& a) {
-  if (!g_small_conv || (a.dtype != DT_F16 && a.dtype != DT_BF16)) return false;
+  if (!g_plan.small_conv || (a.dtype != DT_F16 && a.dtype != DT_BF16)) return false;
   const int HW = a.H * a.W;
   if (!((a.H == 4 && a.W == 4) || (a.H == 8 && a.W == 8))) return false;
   if (a.B <= 0 || (a.B * HW) % 64 != 0) return false;

@@ -560,7 +560,7 @@ __global__ __launch_bounds__(512) void attn_proj_kernel(const AttnProjArgs a) {
 }
 
 bool attn_proj_eligible(const AttnProjArgs& a) {
-  if (!g_st_fuse || (a.dtype != DT_F16 && a.dtype != DT_BF16) || a.C != 256) return false;
+  if (!g_plan.st_fuse || (a.dtype != DT_F16 && a.dtype != DT_BF16) || a.C != 256) return false;
   if (a.n % SF_ROWS != 0 || (long)a.B * a.n > 8192 || a.npad % 4 != 0 || a.npad < a.n) return false;
   if (a.cstats && (a.n % 64 != 0 || a.groups <= 0 || a.C % a.groups != 0)) return false;
   if (a.k_fm && a.npad != a.n) return false;
@@ -576,11 +576,10 @@ int launch_attn_proj(const AttnProjArgs& a, hipStream_t s) {
   return T2P_OK;
 }
 
-bool g_st_fuse = true;      // plan switch 39
 bool st_entry_eligible(const StEntryArgs& a) {
   // C = 256 only.  (The C = 512 instantiation of round 3 -- A fragments re-read from LDS per column tile, two column tiles of weights in
   // flight -- measured EQUAL to the separate launches at cfg2 and cfg4, twice, and was removed in round 4: DESIGN.md section 8.)
-  if (!g_st_fuse || (a.dtype != DT_F16 && a.dtype != DT_BF16) || a.C != 256) return false;
+  if (!g_plan.st_fuse || (a.dtype != DT_F16 && a.dtype != DT_BF16) || a.C != 256) return false;
   // one round of workgroups (two rounds measured slower: cfg4's 32x32 level); a workgroup's 32 rows lie in one sample, except when
   // nothing per-sample is involved (no GroupNorm inside, no column sums out): then any split of the rows will do (4 x 4 maps)
   const bool per_sample = a.cstats || a.y_stats;

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <string>
 
+#include "plan.h"
+
 namespace t2p {
 
 // ---- compute dtypes ------------------------------------------------------------------------
@@ -172,7 +174,6 @@ bool gemm_writes_frag_major(const GemmParams& p);
 bool gemm_rowres_eligible(const GemmParams& p);
 bool gemm_rowres_planned(const GemmParams& p);
 extern long g_rowres_launches;
-extern int g_rowres;       // plan switch 49: 0 off, 1 the planner's choice (gemm_rowres_planned, gemm.hip), 2 wherever eligible
 
 int launch_gemm(const GemmParams& p, hipStream_t stream);
 bool gemm_fuses_col_stats(const GemmParams& p);
@@ -180,36 +181,10 @@ bool gemm_can_fuse_shortcut(const GemmParams& p);   // p without X0 / X1: would 
 bool gemm_fuses_geglu(const GemmParams& p);
 bool gemm_fuses_col_stats_lowp(const GemmParams& p);
 bool gemm_fuses_post_gn(const GemmParams& p, int groups);   // p without gn_*: would launch_gemm apply a following GroupNorm of `groups` groups?
-void set_gemm_post_gn(bool on);
 bool gemm_applies_a_norm(const GemmParams& p);      // p without an_*: would launch_gemm normalise A0 on the fly (head convolution)?
-void set_gemm_split_consts(int tiles, int target);
-void set_gemm_dma(bool on);
-void set_gemm_debug(int v);
-void set_gemm_geom(int v);
-void set_gemm_ring(int v);
-void set_gemm_splitk(bool on);
-void set_gemm_force_nsplit(int v);
-void set_gemm_midsplit(bool on);
-void set_gemm_thin_conv(bool on);
-void set_gemm_a_norm(bool on);
-void set_gemm_up4(bool on);
-void set_gemm_deep_ring(bool on);
-void set_gemm_fuse_shortcut(bool on);
-void set_gemm_dxs(bool on);
 #ifdef T2P_ABLATION
 int dxs_stamps_read(unsigned long long* out, int n);   // measurement builds: in-kernel timeline of gemm_dxs_kernel (gemm.hip)
 #endif
-extern bool g_qkv_fused;
-extern bool g_attn_merged, g_ffpo_merged;
-extern bool g_flash_attention;   // engine / op API: fused attention kernel where eligible
-extern bool g_lowp_h1;         // engine: block-internal conv0 output stored in the compute dtype
-extern bool g_lowp_residual;   // engine: residual stream between blocks in the compute dtype (f16 mode)
-extern bool g_layernorm16;     // LayerNorm of 16-bit rows of 512 / 1024 channels: the row is read once (plan switch 20)
-extern bool g_gn_apply16;      // GroupNorm apply on 16-bit maps: 16-byte accesses, 4 pixels in flight
-extern bool g_gn_small;        // engine / op API: single-launch GroupNorm for maps of <= 64 pixels
-extern bool g_fuse_geglu;      // engine: GEGLU gating inside the ff1 GEMM epilogue
-extern bool g_fuse_gn_stats;   // engine: GroupNorm statistics from the producing GEMM epilogue
-extern bool g_raw_copies;   // engine: feed 1x1 shortcut / proj_out GEMMs with compute-dtype copies
 void profile_begin();
 int profile_end(double out[3][3]);
 int profile_dominant(double out[4], const char** name);

@@ -68,7 +68,6 @@ int launch_pre_conv(const float* x, const float* w, const float* bias, void* out
 bool pre_conv_fuses_col_stats(int W, int nf);
 // the same layer on the 16-bit matrix pipe with every fp32 operand split into two f16 terms (fp32-class accuracy, plan switch 38):
 // wsplit = the weights in that form (pre_conv_split_weight_bytes bytes, written by launch_pre_conv_split_weights from w [9][C][nf])
-extern bool g_pre_conv_split;
 size_t pre_conv_split_weight_bytes(int C, int nf);
 bool pre_conv_split_ok(int out_dtype, int C, int H, int W, int nf);
 int launch_pre_conv_split_weights(const float* w, void* wsplit, int C, int nf, hipStream_t s);
@@ -166,7 +165,6 @@ int launch_attention_flash(int dtype, const void* q, long ldq, const void* k, lo
                            void* out, int B, int heads, int nq, int nk, int d, float scale, hipStream_t s, bool v_rowmajor = false);
 
 // ---- single-head attention with a wide head (AttnBlockpp, layers.py:160-176): d = 256 / 512 / 1024, n <= 1024, one launch --------
-extern bool g_attn_strip;
 bool attention_strip_eligible(int dtype, int heads, int nq, int nk, int d, long ldq, long ldk, long ldvt, long ldo);
 // optional epilogue: out = alpha (attention + bias[channel] + residual[query][channel]), stored fp32 or in the compute dtype, with
 // the per-64-query column sums / sums of squares of the stored fp32 values (col_stats [B n / 64][d][2], n % 64 == 0)
@@ -209,7 +207,6 @@ struct SmallConvArgs {
   int groups = 0, gn_silu = 0;
   float gn_eps = 1e-6f;
 };
-extern bool g_small_conv;
 
 // ---- row-block chains of a SpatialTransformer block in one launch (stfuse.hip; plan switch 39) -------------------------------------
 // st_entry: a = GroupNorm(x) -> t = proj_in(a) + b -> LayerNorm_1(t) -> q | k | v  (model/attention.py:250-256, 208-213, 170-176)
@@ -250,13 +247,6 @@ struct AttnProjArgs {
 };
 bool attn_proj_eligible(const AttnProjArgs& a);
 int launch_attn_proj(const AttnProjArgs& a, hipStream_t s);
-extern bool g_st_fuse;
-extern bool g_small_conv_fm;   // engine.cpp (plan switch 41)
-extern bool g_attn_proj;       // engine.cpp (plan switch 46)
-extern bool g_attn_fm;         // engine.cpp (plan switch 45)
-extern int g_st_tail_rows;     // engine.cpp (development key 43)
-extern bool g_st_ffpo;         // engine.cpp (plan switch 42)
-extern bool g_st_tail;     // engine.cpp (plan switch 40)
 bool st_entry_eligible(const StEntryArgs& a);
 int launch_st_entry(const StEntryArgs& a, hipStream_t s);
 // out = W [N][K] (16-bit, row-major) re-ordered so that every MFMA fragment of 16 rows x 32 K is 1 KiB contiguous (same size)

@@ -19,7 +19,7 @@
 // The dtype is looked at in three places only: tg (which strided GEMM), conv3x3 (a convolution that has 16-bit weight copies runs on
 // them) and plumbing16_ (set in build(): which form of the reduction launchers, reduce_ws hands out their workspace or
 // null; the scaled backward seed; the overflow guard of apply()).  The first two are the PRODUCTS, the third is everything else the
-// 16-bit step does differently; plan switch 48 (g_train_plumbing16, read at build()) turns the third on in an f32 trainer, so that it
+// 16-bit step does differently; plan switch 48 (g_plan.train_plumbing16, read at build()) turns the third on in an f32 trainer, so that it
 // can be held to the reference at fp32 tolerances with every product exact.
 // The backward pass is seeded with S dL/do, S = 2^round(log2(B C L L)) (the fp32 seed is ~1e-5 at full size, at the bottom of
 // f16's normal range; under the VP / sub-VP SDE S is chosen on the device from max|dL/do|), and S is divided out of the flat gradient buffer once at the end.  Every reduction that feeds a gradient, the
@@ -34,7 +34,6 @@
 
 namespace t2p {
 
-bool g_train_plumbing16 = false;   // plan switch 48: a trainer created while it is set runs the 16-bit step's plumbing on its own products
 
 static int gn_groups_of(int c) { return std::min(c / 4, 32); }   // layers.py:282
 
@@ -116,7 +115,7 @@ int Trainer::build() {
   T2P_REQUIRE(mc_.compute_dtype == DT_F32 || mc_.compute_dtype == DT_F16 || mc_.compute_dtype == DT_BF16,
               "the training step computes in f32, f16 or bf16");
   dt_ = mc_.compute_dtype;
-  plumbing16_ = dt_ != DT_F32 || g_train_plumbing16;   // which products (dt_) and which plumbing are two questions; with it every
+  plumbing16_ = dt_ != DT_F32 || g_plan.train_plumbing16;   // which products (dt_) and which plumbing are two questions; with it every
                                                        // reduction runs in a fixed order (bitwise reproducible), without it on atomics
   T2P_REQUIRE(tc_.dropout >= 0.0 && tc_.dropout < 1.0 && tc_.ema_rate >= 0.0 && tc_.ema_rate <= 1.0, "dropout / ema_rate");
   int dev = 0;

@@ -17,10 +17,9 @@
 
 namespace t2p {
 
-// plan switch 48 (t2p_debug_set): a trainer CREATED while it is set uses everything the 16-bit step uses except the products -- the
-// fixed-order reductions, the scaled backward seed (host power of two for VE, seed_scale on the device for VP / sub-VP) and the
+// plan switch 48 (g_plan.train_plumbing16): a trainer CREATED while it is set uses everything the 16-bit step uses except the products --
+// the fixed-order reductions, the scaled backward seed (host power of two for VE, seed_scale on the device for VP / sub-VP) and the
 // overflow guard -- with tg and conv3x3 on the f32 kernels.  Off by default; the product path never sets it
-extern bool g_train_plumbing16;
 
 struct TParam {           // one learnable tensor: a slice of the flat buffers, in the reference's parameters() order
   std::string name;
