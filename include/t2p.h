@@ -711,6 +711,26 @@ int t2p_op_decode_6d(const float* x, int batch, int channels, int L, float* clip
  * than 0 / 1, blocks with channels = 5, any other channel count.  nres is read back on the host: the call synchronises the stream. */
 int t2p_op_encode_6d(const float* xyz, const int32_t* nres, const uint8_t* atom_ok, int batch, int channels, int L,
                      const int32_t* host_blocks, int n_blocks, float* coords_6d, uint8_t* mask_pair, void* stream);
+/* Secondary structure from CA traces, the annotation the reference asks biotite for (struc.annotate_sse, dataset.py:121-123): P-SEA
+ * (Labesse et al. 1997) with its published thresholds as biotite applies them, restated in DESIGN.md 8i, which is normative -- no
+ * biotite release is the yardstick.  One workgroup per chain, in double from the fp32 coordinates.
+ *   xyz = (batch, L, atoms, 3) fp32 on the device; atoms = 3: the N / CA / C layout of t2p_op_fold_6d and t2p_op_encode_6d, of which
+ *   atom 1 is read; atoms = 1: a bare CA trace (the convention of t2p_op_tm_align).  len = (batch) int32; nothing past len[b] is read.
+ *   atom_ok = (batch, L, atoms) uint8 or NULL (every atom present).  A residue whose CA is absent has no CA; a residue whose CA
+ *   coordinate is not finite or exceeds 1e6 in magnitude is treated as absent and status[b] = 1.
+ *   target = (batch, L) uint8 letters or NULL.
+ * Outputs, device, every element written:
+ *   letters = (batch, L) uint8: ASCII 'a' (helix) / 'b' (strand) / 'c' inside the length, 0 past it.  A residue without a CA is 'c'
+ *   (the reference drops such a chain, dataset.py:124);
+ *   counts = (batch, 12) int32: residues a, b, c; runs of a of at least 4 and runs of b of at least 4 (the blocks of
+ *   encode.sse_blocks); residues with target a and, of those, the ones labelled a; the same two for b (all four 0 without a target);
+ *   residues without a CA; 0; 0;
+ *   status[b] = 0, 1 as above, or -1 when len[b] lies outside [1, L]: that chain's letters and counts are then zero.
+ * Refused before launch (status and message): L outside [1, 512] (the fold's limit), atoms other than 1 or 3, batch <= 0, a null xyz,
+ * len, letters, counts or status.  No workspace; everything is enqueued on `stream`; nothing is read back; only integers are counted,
+ * so two calls give the same bits. */
+int t2p_op_annotate_sse(const float* xyz, const int32_t* len, const uint8_t* atom_ok, int batch, int L, int atoms, const uint8_t* target,
+                        uint8_t* letters, int32_t* counts, int32_t* status, void* stream);
 /* Backbones from decoded maps, in place of the reference's PyRosetta stage (sampling_rosetta.py:98-160) -- restraint-free: known pairs
  * (dist < known_below, upper triangle), geodesic completion, classical MDS, stress_steps refinement steps on the Cb trace, N / CA / C
  * from phi, theta and the featuriser's virtual-Cb identity, the mirror image told apart by chain closure.  absval =

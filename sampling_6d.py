@@ -34,8 +34,13 @@ Differences, all at the edges of the hot path:
     from one chain of a PDB file (utils.py:122-137).  The reference goes through biotite there (and is broken, SURVEY.md 2
     row 10); here the backbone is read by a small reader of our own and featurised on the GPU (text2protein_amd/encode.py:
     dataset.py:114-168, :200-239, :396-450).  The secondary-structure letters of an 8-channel model (biotite's P-SEA in the
-    reference) are an input: ``--sse`` takes one of a / b / c per residue, or a file holding them.  Without ``--mask_info``
-    the reference's default "1:5,10:15" applies.
+    reference) are an input: ``--sse`` takes one of a / b / c per residue, or a file holding them, or the word ``psea``: the
+    letters are then computed from the chain's CA trace on the GPU (text2protein_amd/encode.py ``annotate_sse_batch``: P-SEA
+    as DESIGN.md 8i states it).  Without ``--mask_info`` the reference's default "1:5,10:15" applies.
+  * ``--ss_check`` (implies ``--fold``) annotates every folded chain the same way and adds an ``"sse"`` block to ``fold_<id>.json``:
+    the letters and counts of the folded chain (and of the refined chain with ``--refine``) and, on an 8-channel model whose
+    ``ss`` condition came from ``--pdb`` or ``--inpaint_coords``, the helix and strand agreement with the condition's own blocks
+    (``encode.sse_target``); one line is printed per sample that has such a target.
   * ``--inpaint_coords <file.pt|synthetic>`` gives the same conditions from maps featurised elsewhere: built exactly as
     ``get_condition_from_batch`` does (utils.py:84-106).  ``--mask_info`` without either source is an error.
   * ``checkpoint`` may be the word ``synthetic`` (hash-generated weights, no file needed).
@@ -78,7 +83,7 @@ def main():
                         help="inpainting residue ranges (reference default '1:5,10:15'); needs --pdb or --inpaint_coords")
     parser.add_argument("--sse", type=str, default=None,
                         help="with --pdb and an 8-channel model: the chain's secondary-structure letters (one of a/b/c per residue), "
-                             "or a file holding them")
+                             "a file holding them, or the word psea (computed from the CA trace on the GPU)")
     parser.add_argument("--tag", type=str, default="test")
     parser.add_argument("--device", type=str, default="cuda")
     parser.add_argument("--batch_size", type=int, default=32)
@@ -109,6 +114,10 @@ def main():
                         help="also minimise every folded chain against the restraint set on the GPU (text2protein_amd/refine.py; implies "
                              "--fold; at most 256 residues): refined_<id>.pdb next to folded_<id>.pdb, a \"refine\" block in fold_<id>.json; "
                              "--tm_ref then scores the refined chains")
+    parser.add_argument("--ss_check", action="store_true",
+                        help="also annotate the secondary structure of every folded (and refined) chain on the GPU (P-SEA; implies --fold): "
+                             "an \"sse\" block in fold_<id>.json with the letters, the counts and, where the ss condition came from --pdb or "
+                             "--inpaint_coords on an 8-channel model, the agreement with the condition's blocks")
     parser.add_argument("--tm_ref", type=str, action="append", default=None, metavar="PATH",
                         help="score every folded chain with TM-align on the GPU (text2protein_amd/tmalign.py) against reference chains: "
                              "PATH is a .pdb file or a directory of them, read with --chain; may be repeated; implies --fold; writes "
@@ -147,7 +156,7 @@ def main():
         except ValueError as e:
             raise SystemExit(str(e))
         args.fold = True
-    if args.refine:
+    if args.refine or args.ss_check:
         args.fold = True
     replace = args.inpaint_mode == "replace"
     if replace:
@@ -202,18 +211,26 @@ def main():
             tm_refs = TM.read_chains(tm_ref_files, args.chain) + ([os.path.basename(p) for p in tm_ref_files],)
         except ValueError as e:
             raise SystemExit(f"--tm_ref: {e}")
+    # --ss_check: the target letters of the `ss` condition, one string per chain of this rank (the same on every rank)
+    want_target = args.ss_check and config.data.num_channels == 8 and "ss" in config.model.condition
+    ss_target = None
     pdb_condition = None
     if args.pdb is not None:
         sse = args.sse
-        if sse is not None and os.path.exists(sse):
+        if sse is not None and sse != "psea" and os.path.exists(sse):
             sse = "".join(open(sse).read().split())
         try:
             # sampling_6d.py:146-147; the chain is the same for every iteration, so it is featurised once (and before the model is
             # built: a file that cannot be used is reported at once)
             pdb_condition = get_conditions_from_pdb(args.pdb, config, chain=args.chain, mask_info=args.mask_info or "1:5,10:15",
-                                                    batch_size=args.batch_size, sse=sse, with_batch=replace)
+                                                    batch_size=args.batch_size, sse=sse, with_batch=replace or want_target)
         except (OSError, ValueError, T2PError) as e:
             raise SystemExit(f"--pdb: {e}")
+        if want_target:
+            from text2protein_amd.encode import sse_target
+            ss_target = sse_target(pdb_condition["_batch"]["coords_6d"])
+            if not replace:
+                del pdb_condition["_batch"]
 
     # Initialize model (get_model + restore_checkpoint + ema.copy_to, sampling_6d.py:64-73)
     score_model = HipScoreModel(config, dtype=args.dtype, device=device)
@@ -313,6 +330,9 @@ def main():
         rep = B // coords.shape[0]
         known = {"coords_6d": coords.repeat(rep, 1, 1, 1),
                  **({"lengths": list(known["lengths"]) * rep} if "lengths" in known else {"aa_str": list(known["aa_str"]) * rep})}
+        if want_target:
+            from text2protein_amd.encode import sse_target
+            ss_target = sse_target(known["coords_6d"])
 
     def to_device(c):
         return {k: to_device(v) if isinstance(v, dict) else v.to(device) for k, v in c.items()}
@@ -366,6 +386,7 @@ def main():
                     from text2protein_amd import fold as F
                     xyz, status, placed, diag = F.fold_maps_batch(absval, lengths)
                     xyz_dev, xyz = xyz, xyz.cpu().numpy()
+                    fold_dev = xyz_dev
                     chains = F.diagnostics(status, placed, diag, lengths)
                     refined = None
                     if args.refine:                 # minimised against the restraint set; these are the chains scored below
@@ -377,6 +398,13 @@ def main():
                         refined = xyz_dev.cpu().numpy()
                         for d, r in zip(chains, R.diagnostics(r_status, r_diag, lengths)):
                             d["refine"] = r
+                    if args.ss_check:               # letters of the chains as folded and as refined, against the condition's blocks
+                        target = None if ss_target is None else ss_target * world
+                        stages = [("folded", F.ss_agreement(fold_dev, lengths, target))]
+                        if refined is not None:
+                            stages.append(("refined", F.ss_agreement(xyz_dev, lengths, target)))
+                        for i, d in enumerate(chains):
+                            d["sse"] = {name: rows[i] for name, rows in stages}
                     tm = None
                     if tm_refs is not None:         # every folded chain against every reference, and the samples against each other
                         keep = [i for i, d in enumerate(chains) if d["status"] >= 0]
@@ -400,6 +428,11 @@ def main():
                         if d["status"] != 0:
                             print(f"sample {sid}: fold status {d['status']} ({d['unreachable_pairs']} unreachable pairs, "
                                   f"{len(d['placed'])} residues placed without a frame of their own)")
+                        if args.ss_check and ss_target is not None:
+                            def pct(v):
+                                return "no target" if v is None else f"{100.0 * v:.1f} %"
+                            print(f"sample {sid}: secondary structure " + "; ".join(
+                                f"{name}: helix {pct(v['helix_agreement'])}, strand {pct(v['strand_agreement'])}" for name, v in d["sse"].items()))
                         if tm is not None:
                             t = tm["samples"][str(sid)]
                             if t["scored"]:

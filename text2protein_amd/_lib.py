@@ -153,6 +153,8 @@ SIGNATURES = {
     "t2p_debug_rowres_launches": (_i64, []),
     "t2p_op_decode_6d": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "t2p_op_encode_6d": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    # secondary structure of CA traces: P-SEA (csrc/sse.hip)
+    "t2p_op_annotate_sse": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     # backbones from decoded maps (csrc/fold.hip)
     "t2p_op_fold_ws": (_i64, [_i, _i]),
     "t2p_op_fold_6d": (_i, [_vp, _vp, _i, _i, _f, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),

@@ -9,7 +9,8 @@
                                               (text2protein_amd/encode.py: dataset.py:114-168, :200-239, :396-450)
 The reference's builder goes through biotite and calls ``ProteinDataset`` with a signature it does not have (SURVEY.md section 2,
 row 10); here the chain is read by ``encode.read_backbone`` and encoded by ``t2p_op_encode_6d``.  The secondary-structure letters
-of the 8-channel layout (biotite's P-SEA in the reference) are an input.  ``get_conditions_random`` (utils.py:108-120) draws from a
+of the 8-channel layout (biotite's P-SEA in the reference) are an input, or ``sse="psea"`` computes them on the device
+(``t2p_op_annotate_sse``).  ``get_conditions_random`` (utils.py:108-120) draws from a
 dataset directory and stays out of scope.
 """
 from __future__ import annotations
@@ -155,7 +156,8 @@ def get_condition_from_batch(config, batch, mask_info=None):
 def get_conditions_from_pdb(pdb, config, chain="A", mask_info=None, batch_size=8, sse=None, with_batch=False):
     """utils.py:122-137: chain ``chain`` of the file ``pdb``, featurised (dataset.py:311-325) and padded to ``max_res_num``
     (PaddingCollate), repeated over the batch, then ``get_condition_from_batch``; every tensor on ``config.device``, which must be a
-    GPU.  ``sse``: one of a / b / c per residue (P-SEA letters), required by the 8-channel layout.  ``with_batch`` adds the
+    GPU.  ``sse``: one of a / b / c per residue (P-SEA letters), required by the 8-channel layout, or the word ``"psea"``: the letters
+    are then computed from the chain's CA trace on the device (``encode.annotate_sse_batch``).  ``with_batch`` adds the
     featurised batch itself under ``"_batch"`` (replacement inpainting reads the maps and the residue counts from it).  A chain outside
     ``[min_res_num, max_res_num]`` is refused (the reference's dataset drops it, dataset.py:282-284)."""
     from .encode import encode_6d_batch, read_backbone
@@ -166,7 +168,7 @@ def get_conditions_from_pdb(pdb, config, chain="A", mask_info=None, batch_size=8
     if C == 8:
         if sse is None:
             raise ValueError("an 8-channel model needs the chain's secondary-structure letters (a / b / c per residue): pass --sse")
-        if len(sse) != nres:
+        if sse != "psea" and len(sse) != nres:
             raise ValueError(f"--sse holds {len(sse)} letters, chain {chain!r} of {pdb} has {nres} residues")
     elif sse is not None:
         raise ValueError("--sse applies to 8-channel models only (data.num_channels)")
@@ -174,7 +176,7 @@ def get_conditions_from_pdb(pdb, config, chain="A", mask_info=None, batch_size=8
     x = torch.zeros(1, hi, 3, 3)
     ok = torch.zeros(1, hi, 3, dtype=torch.uint8)
     x[0, :nres], ok[0, :nres] = torch.from_numpy(xyz), torch.from_numpy(atom_ok)
-    one = encode_6d_batch(x.to(device), torch.tensor([nres]), atom_ok=ok.to(device), sse=None if sse is None else [sse], num_channels=C)
+    one = encode_6d_batch(x.to(device), torch.tensor([nres]), atom_ok=ok.to(device), sse=sse if sse in (None, "psea") else [sse], num_channels=C)
     batch = {"coords_6d": one["coords_6d"].repeat(batch_size, 1, 1, 1), "mask_pair": one["mask_pair"].repeat(batch_size, 1, 1),
              "lengths": one["lengths"].repeat(batch_size), "ss_indices": one["ss_indices"] * batch_size}
     cond = get_condition_from_batch(config, batch, mask_info=mask_info)

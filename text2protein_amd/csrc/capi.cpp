@@ -867,6 +867,13 @@ int t2p_op_encode_6d(const float* xyz, const int32_t* nres, const uint8_t* atom_
   API_END
 }
 
+int t2p_op_annotate_sse(const float* xyz, const int32_t* len, const uint8_t* atom_ok, int batch, int L, int atoms, const uint8_t* target,
+                        uint8_t* letters, int32_t* counts, int32_t* status, void* stream) {
+  API_BEGIN
+  return launch_annotate_sse(xyz, len, atom_ok, batch, L, atoms, target, letters, counts, status, (hipStream_t)stream);
+  API_END
+}
+
 int64_t t2p_op_fold_ws(int batch, int L) { return (int64_t)fold6d_workspace_bytes(batch, L); }
 
 int t2p_op_fold_6d(const float* absval, const int32_t* lengths, int batch, int L, float known_below, int stress_steps, float dist_std,

@@ -286,6 +286,14 @@ int launch_fold6d(const float* absval, const int* lengths, int B, int L, float k
 int launch_restraint_score(const float* xyz, const float* absval, const int* lengths, int B, int L, float dist_std, float angle_std_deg,
                            double* out, int stride, void* workspace, long workspace_bytes, hipStream_t s);
 
+// ---- secondary structure of CA traces: P-SEA (sse.hip) ----
+// xyz [B][L][atoms][3] fp32 (atoms = 3: atom 1 is read; atoms = 1: a CA trace), len [B], atom_ok [B][L][atoms] or null, target [B][L]
+// letters or null -> letters [B][L] ('a' / 'b' / 'c', 0 past the length), counts [B][12], status [B].  One workgroup per chain; SSE_MAX_L
+// (= FOLD_MAX_L) bounds the trace and the flags it keeps in LDS.
+constexpr int SSE_MAX_L = FOLD_MAX_L;
+int launch_annotate_sse(const float* xyz, const int* len, const unsigned char* atom_ok, int B, int L, int atoms, const unsigned char* target,
+                        unsigned char* letters, int* counts, int* status, hipStream_t s);
+
 // ---- refinement of folded backbones against the restraint set (refine.hip) ----
 // One workgroup per chain, a persistent staged L-BFGS in double; REFINE_MAX_L bounds the five coordinate-sized vectors a workgroup keeps
 // in LDS (18 KB each at 256 residues) and is every shipped data.max_res_num, like TM_MAX_L.  A stage is six doubles on the host:

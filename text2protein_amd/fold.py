@@ -158,6 +158,25 @@ def restraint_score(xyz, decoded, dist_std=2.0, angle_std=10.0):
     return res[0] if single else res
 
 
+def ss_agreement(xyz, lengths, target=None):
+    """Does a folded (or refined) chain have its helices and strands where the ``ss`` condition put them?  ``xyz`` (B, L, 3, 3) or
+    (B, L, 3) on the device, ``lengths`` (B,), ``target`` one letter string per chain (``encode.sse_target`` of the condition) or None.
+    The chains are annotated on the device (``encode.annotate_sse_batch``, P-SEA).  Returns one dict per chain:
+    ``letters``, ``counts`` (``encode.COUNT_NAMES``), ``status`` and, with a target, ``target``, ``helix_agreement`` = target-``a``
+    residues labelled ``a`` / target-``a`` residues and ``strand_agreement`` likewise; each is None when its target is empty.  A chain
+    whose length lies outside [1, L] (an improper mask: -1) has empty letters and zero counts."""
+    from .encode import COUNT_NAMES, annotate_sse_batch
+    r = annotate_sse_batch(xyz, lengths, target=target)
+    counts, status = r["counts"].cpu().tolist(), r["status"].cpu().tolist()
+    out = []
+    for b, c in enumerate(counts):
+        d = {"letters": r["letters"][b], "counts": dict(zip(COUNT_NAMES, c)), "status": status[b]}
+        if target is not None:
+            d.update(target=target[b], helix_agreement=c[6] / c[5] if c[5] else None, strand_agreement=c[8] / c[7] if c[7] else None)
+        out.append(d)
+    return out
+
+
 def write_backbone_pdb(path, xyz, chain="A", resname="ALA", with_cb=False):
     """N / CA / C of one chain as fixed-column ATOM records (3 decimals), ``TER`` and ``END``; ``with_cb`` adds the virtual CB the
     featuriser builds from the three.  ``encode.read_backbone`` reads the file back."""
