@@ -808,6 +808,37 @@ int t2p_op_refine_backbone(const float* xyz_in, const float* absval, const int32
 int t2p_op_restraint_energy(const float* xyz, const float* absval, const int32_t* lengths, int batch, int L, const double* stage,
                             float dist_std, float angle_std, float arm_min, double* out9, double* grad, void* workspace,
                             int64_t workspace_bytes, void* stream);
+/* The reference's "diversify backbone" move (rosetta_min/run.py:104-109) on N / CA / C chains held in Cartesian coordinates (DESIGN.md
+ * 8j).  Atoms a_0 .. a_3n-1 run N, CA, C per residue, read as double from fp32.  For k >= 3: b_k = |a_k - a_k-1|, theta_k the angle at
+ * a_k-1, tau_k = dihedral(a_k-3, a_k-2, a_k-1, a_k).  tau_3i+2 (phi_i) takes + dphi_i for i >= 1, tau_3i+3 (psi_i) + dpsi_i for
+ * i <= n - 2; omega, bond lengths and bond angles stay as measured.  Atoms 0..2 are copied, every later atom is rebuilt from the three
+ * rebuilt atoms before it (NeRF); where that frame is undefined (three collinear atoms) the atom is placed with tau unchanged in the
+ * fallback frame DESIGN.md 8j states.  Draws: Philox4x32-10, key = seed, training layout, counter {residue i, chain_ids[b], stream lo,
+ * stream hi}; dphi_i = amp_deg (2 u(word 0) - 1), dpsi_i = amp_deg (2 u(word 1) - 1) degrees.  chain_ids = (batch) int32 on the
+ * device, or null for 0 .. batch - 1: a chain's move does not depend on its batch position or padding.
+ *   xyz_in = (batch, L, 3, 3) fp32, lengths = (batch) int32, L <= 256, replicas in 1..16.  xyz_out = (batch, replicas, L, 3, 3) fp32,
+ *   zero past lengths[b]: candidate k draws under stream + k; with keep_first != 0 candidate 0 is a bit-exact copy of the input.
+ *   status = (batch, replicas) int32: 0 ok, 2 a coordinate not finite (zeros), -1 lengths[b] < 2 or > L (zeros).  Always finite. */
+int t2p_op_perturb_torsions(const float* xyz_in, const int32_t* lengths, const int32_t* chain_ids, int batch, int L, int replicas,
+                            float amp_deg, uint64_t seed, uint64_t stream, int keep_first, float* xyz_out, int32_t* status,
+                            void* stream_handle);
+/* Refinement in rounds: the loop of rosetta_min/run.py:88-151 on the device.  Per chain the incumbent starts as xyz_in
+ * with E_inc = +inf; round r perturbs it into `replicas` candidates (t2p_op_perturb_torsions, stream = stream_base + 16 r, keep_first in
+ * round 0 only), minimises each as t2p_op_refine_backbone does under schedules[r] (batch x replicas workgroups in one launch), scores
+ * each with the weighted total of t2p_op_restraint_energy under select_stage (E_sel), and the lowest E_sel among the candidates of
+ * status 0 or 1 (ties: the lowest index) replaces the incumbent when it is below E_inc.  Four launches per round on `stream`, nothing
+ * read back.  schedules = rounds x n_stages x 6 doubles and select_stage = 6 doubles on the HOST; rounds in 1..8, replicas in 1..16,
+ * batch x replicas <= 65535.
+ *   Outputs, device: xyz_out (batch, L, 3, 3) fp32, status (batch) and diag (batch, 16) = the kept candidate's, as
+ *   t2p_op_refine_backbone writes them -- when no candidate was ever valid, the status t2p_op_refine_backbone gives xyz_in, with zeros;
+ *   trace = (batch, rounds, replicas, 4) double: E_sel, status, energy evaluations, 1 where that candidate became the incumbent.
+ *   workspace = t2p_op_refine_rounds_ws(batch, L, rounds, replicas) bytes (it does not grow with rounds; -1: L above 256, rounds or
+ *   replicas out of range, or an argument not positive).  rounds = replicas = 1 gives t2p_op_refine_backbone's bits. */
+int64_t t2p_op_refine_rounds_ws(int batch, int L, int rounds, int replicas);
+int t2p_op_refine_rounds(const float* xyz_in, const float* absval, const int32_t* lengths, const int32_t* chain_ids, int batch, int L,
+                         const double* schedules, int rounds, int n_stages, int replicas, const double* select_stage, float amp_deg,
+                         uint64_t seed, uint64_t stream_base, float dist_std, float angle_std, float arm_min, float* xyz_out,
+                         int32_t* status, double* diag, double* trace, void* workspace, int64_t workspace_bytes, void* stream);
 /* text context = embed_tokens(ids), sampling_6d.py:134-137: out[(b,t)][:] = table[ids[(b,t)]][:] as fp32; the table
  * ([vocab][dim], fp32 / bf16 / f16 by table_dtype) stays resident.  *bad_flag (device int, zeroed by the caller) is
  * set to 1 when an id falls outside [0, vocab). */

@@ -25,6 +25,12 @@ Differences, all at the edges of the hot path:
     rosetta_min/run.py takes between the maps and TM-align -- without Rosetta's own energy terms, relax or side chains; maps of
     at most 256 residues) and writes ``refined_<id>.pdb`` next to ``folded_<id>.pdb``; ``fold_<id>.json`` gains a ``"refine"`` block
     (status, energies, the eight terms, iterations, evaluations, closure).  With ``--tm_ref`` the refined chains are the ones scored.
+  * ``--refine_rounds R`` / ``--refine_replicas K`` (either implies ``--refine``; defaults 1 / 1 = the single minimisation above) run
+    the minimisation in rounds as rosetta_min/run.py:88-151 does (text2protein_amd/refine.py ``refine_rounds_batch``): every round
+    moves each phi and psi of the best chain so far by up to 10 degrees, K times, minimises the K candidates side by side with the
+    round's weights and keeps the lowest-scoring one if it beats the best so far.  ``refined_<id>.pdb`` is the kept chain and the
+    ``"refine"`` block gains ``"rounds"``: per round the candidates' E_sel, status and evaluations, and which was kept.  The draws
+    are keyed by ``--seed``, the sample id and the ``--n_iter`` index.
   * ``--tm_ref PATH`` (repeatable; a ``.pdb`` file or a directory of them, read with ``--chain``; implies ``--fold``) scores the
     folded chains with TM-align on the device (text2protein_amd/tmalign.py, in place of the reference's one TMalign process per
     pair: tm/TMalign.py:36-160, utils.py:150-158): every chain against every reference and the chains against each other.
@@ -114,6 +120,13 @@ def main():
                         help="also minimise every folded chain against the restraint set on the GPU (text2protein_amd/refine.py; implies "
                              "--fold; at most 256 residues): refined_<id>.pdb next to folded_<id>.pdb, a \"refine\" block in fold_<id>.json; "
                              "--tm_ref then scores the refined chains")
+    parser.add_argument("--refine_rounds", type=int, default=1, metavar="R",
+                        help="minimise in R rounds (1..8; implies --refine): from the second round on every phi and psi of the best chain so "
+                             "far moves by up to 10 degrees and the round's weights apply (rosetta_min/run.py); a result is kept only when it "
+                             "scores lower; fold_<id>.json's \"refine\" block gains \"rounds\"")
+    parser.add_argument("--refine_replicas", type=int, default=1, metavar="K",
+                        help="candidates per round (1..16; implies --refine): K moves of the best chain so far are minimised side by side on "
+                             "the GPU and the lowest-scoring one is the round's result")
     parser.add_argument("--ss_check", action="store_true",
                         help="also annotate the secondary structure of every folded (and refined) chain on the GPU (P-SEA; implies --fold): "
                              "an \"sse\" block in fold_<id>.json with the letters, the counts and, where the ss condition came from --pdb or "
@@ -156,6 +169,11 @@ def main():
         except ValueError as e:
             raise SystemExit(str(e))
         args.fold = True
+    if not 1 <= args.refine_rounds <= 8 or not 1 <= args.refine_replicas <= 16:
+        raise SystemExit("--refine_rounds takes 1..8 and --refine_replicas 1..16")
+    in_rounds = args.refine_rounds > 1 or args.refine_replicas > 1
+    if in_rounds:
+        args.refine = True
     if args.refine or args.ss_check:
         args.fold = True
     replace = args.inpaint_mode == "replace"
@@ -391,13 +409,24 @@ def main():
                     refined = None
                     if args.refine:                 # minimised against the restraint set; these are the chains scored below
                         from text2protein_amd import refine as R
+                        r_rounds = None
                         try:
-                            xyz_dev, r_status, r_diag = R.refine_backbone_batch(xyz_dev, absval, lengths)
+                            if in_rounds:           # draws: the run's seed, the sample ids, one block of streams per --n_iter call
+                                import zlib
+                                cids = [int(s) & 0x7FFFFFFF if str(s).isdigit() else zlib.crc32(str(s).encode()) & 0x7FFFFFFF for s in out_ids]
+                                xyz_dev, r_status, r_diag, r_trace = R.refine_rounds_batch(
+                                    xyz_dev, absval, lengths, args.refine_rounds, args.refine_replicas, seed=args.seed,
+                                    stream_base=it * R.STREAM_STRIDE * R.MAX_ROUNDS, chain_ids=cids)
+                                r_rounds = R.rounds_diagnostics(r_trace)
+                            else:
+                                xyz_dev, r_status, r_diag = R.refine_backbone_batch(xyz_dev, absval, lengths)
                         except ValueError as e:
                             raise SystemExit(f"--refine: {e}")
                         refined = xyz_dev.cpu().numpy()
-                        for d, r in zip(chains, R.diagnostics(r_status, r_diag, lengths)):
+                        for i, (d, r) in enumerate(zip(chains, R.diagnostics(r_status, r_diag, lengths))):
                             d["refine"] = r
+                            if r_rounds is not None:
+                                d["refine"]["rounds"] = r_rounds[i]
                     if args.ss_check:               # letters of the chains as folded and as refined, against the condition's blocks
                         target = None if ss_target is None else ss_target * world
                         stages = [("folded", F.ss_agreement(fold_dev, lengths, target))]

@@ -167,6 +167,10 @@ SIGNATURES = {
     "t2p_op_refine_ws": (_i64, [_i, _i]),
     "t2p_op_refine_backbone": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _i64, _vp]),
     "t2p_op_restraint_energy": (_i, [_vp, _vp, _vp, _i, _i, _vp, _f, _f, _f, _vp, _vp, _vp, _i64, _vp]),
+    # refinement in rounds: the phi / psi move and the loop perturb -> minimise -> select (csrc/refine_rounds.hip)
+    "t2p_op_perturb_torsions": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _u64, _u64, _i, _vp, _vp, _vp]),
+    "t2p_op_refine_rounds_ws": (_i64, [_i, _i, _i, _i]),
+    "t2p_op_refine_rounds": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _f, _u64, _u64, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "t2p_op_embedding_gather": (_i, [_vp, _i, _vp, _vp, _i64, _i, _i, _vp, _vp]),
     "t2p_profile_end": (_i, [C.POINTER(C.c_double)]),
     "t2p_profile_dominant": (_i, [C.POINTER(C.c_double), C.c_char_p, C.c_int]),

@@ -913,6 +913,31 @@ int t2p_op_restraint_energy(const float* xyz, const float* absval, const int32_t
   API_END
 }
 
+int t2p_op_perturb_torsions(const float* xyz_in, const int32_t* lengths, const int32_t* chain_ids, int batch, int L, int replicas,
+                            float amp_deg, uint64_t seed, uint64_t stream, int keep_first, float* xyz_out, int32_t* status,
+                            void* stream_handle) {
+  API_BEGIN
+  return launch_perturb_torsions(xyz_in, lengths, chain_ids, nullptr, batch, L, replicas, amp_deg, (unsigned long long)seed,
+                                 (unsigned long long)stream, keep_first, xyz_out, status, nullptr, (hipStream_t)stream_handle);
+  API_END
+}
+
+int64_t t2p_op_refine_rounds_ws(int batch, int L, int rounds, int replicas) {
+  if (rounds < 1 || rounds > REFINE_MAX_ROUNDS) return -1;
+  return (int64_t)refine_rounds_workspace_bytes(batch, L, replicas);
+}
+
+int t2p_op_refine_rounds(const float* xyz_in, const float* absval, const int32_t* lengths, const int32_t* chain_ids, int batch, int L,
+                         const double* schedules, int rounds, int n_stages, int replicas, const double* select_stage, float amp_deg,
+                         uint64_t seed, uint64_t stream_base, float dist_std, float angle_std, float arm_min, float* xyz_out,
+                         int32_t* status, double* diag, double* trace, void* workspace, int64_t workspace_bytes, void* stream) {
+  API_BEGIN
+  return launch_refine_rounds(xyz_in, absval, lengths, chain_ids, batch, L, schedules, rounds, n_stages, replicas, select_stage, amp_deg,
+                              (unsigned long long)seed, (unsigned long long)stream_base, dist_std, angle_std, arm_min, xyz_out, status, diag,
+                              trace, workspace, (long)workspace_bytes, (hipStream_t)stream);
+  API_END
+}
+
 int64_t t2p_op_tm_align_ws(int n_pairs, int La, int Lb) { return (int64_t)tm_align_workspace_bytes(n_pairs, La, Lb); }
 
 int t2p_op_tm_align(const float* xyz_a, const int32_t* len_a, int n_a, int La, int atoms_a, const float* xyz_b, const int32_t* len_b, int n_b,

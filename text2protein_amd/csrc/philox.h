@@ -31,6 +31,9 @@
 //   t2p_op_inpaint_mask_draw                caller's seed  training  caller's                     -           as the trainer's inpaint mask
 //   t2p_op_context_drop                     caller's seed  training  caller's                     -           as the trainer's context drop
 //   t2p_op_ploss_draw_t                     caller's seed  training  caller's                     -           as the trainer's p_loss t
+//   t2p_op_perturb_torsions                 caller's seed  training  caller's + candidate k       -           residue i + 2^32 chain_id   word 0: dphi_i, word 1: dpsi_i
+//   (refine_rounds.hip)                                                                                                  = amp (2 u - 1) degrees
+//   t2p_op_refine_rounds                    caller's seed  training  stream_base + 16 round + k   -           as t2p_op_perturb_torsions
 //   (calls = Trainer::loss_calls_, the number of loss calls completed before the running one.)
 //
 // Two known defects, recorded here and left as they are (fixing either changes drawn bits):

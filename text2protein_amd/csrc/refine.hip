@@ -342,10 +342,11 @@ __device__ __forceinline__ double load_chain(const float* in, double* X, int n, 
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // One evaluation for given coordinates: out9 [B][9] = the eight unweighted terms and the weighted total, grad [B][L][3][3].
+template <bool GROUPED>                                        // as refine_kernel's; grad may then be null
 __global__ __launch_bounds__(REFINE_THREADS) void restraint_energy_kernel(const float* __restrict__ xyz, const float* __restrict__ absval,
                                                                           const int* __restrict__ lengths, int L, Stage st, Params pr,
                                                                           double* __restrict__ out9, double* __restrict__ grad, int* offsets_all,
-                                                                          Entry* entries_all) {
+                                                                          Entry* entries_all, int group) {
   extern __shared__ double lds[];
   double* X = lds;
   double* G = X + 9 * L;
@@ -353,20 +354,22 @@ __global__ __launch_bounds__(REFINE_THREADS) void restraint_energy_kernel(const 
   double* red = CB + 3 * L;
   const int b = blockIdx.x, t = threadIdx.x;
   const int n = lengths[b];
-  double* go = grad + (long)b * L * 9;
+  double* go = !GROUPED || grad ? grad + (long)b * L * 9 : nullptr;
   double terms[8];
   bool ok = refinable(n, L);                                   // uniform over the workgroup
   if (ok) ok = load_chain(xyz + (long)b * L * 9, X, n, red) == 0.0;
   if (!ok) {
-    for (int e = t; e < 9 * L; e += REFINE_THREADS) go[e] = 0.0;
+    if (go)
+      for (int e = t; e < 9 * L; e += REFINE_THREADS) go[e] = 0.0;
     if (t < 9) out9[(long)b * 9 + t] = 0.0;
     return;
   }
   int* offsets = offsets_all + (long)b * (L + 1);
   Entry* entries = entries_all + (long)b * L * (L - 1);
-  build_lists(absval + (long)b * 4 * L * L, L, n, pr.arm_min, offsets, entries);
+  build_lists(absval + (long)(GROUPED ? b / group : b) * 4 * L * L, L, n, pr.arm_min, offsets, entries);
   evaluate(X, G, CB, red, n, offsets, entries, st, pr, terms);
-  for (int e = t; e < 9 * L; e += REFINE_THREADS) go[e] = e < 9 * n ? finite_or_zero(G[e]) : 0.0;
+  if (go)
+    for (int e = t; e < 9 * L; e += REFINE_THREADS) go[e] = e < 9 * n ? finite_or_zero(G[e]) : 0.0;
   if (t == 0) {
     for (int k = 0; k < 8; ++k) out9[(long)b * 9 + k] = finite_or_zero(terms[k]);
     out9[(long)b * 9 + 8] = finite_or_zero(total_energy(terms, st));
@@ -375,11 +378,14 @@ __global__ __launch_bounds__(REFINE_THREADS) void restraint_energy_kernel(const 
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The staged L-BFGS of one chain.  Every vector operation is elementwise with element e owned by thread e mod REFINE_THREADS, so only
-// the dot products and the evaluations synchronise.
+// the dot products and the evaluations synchronise.  GROUPED (refinement in rounds): workgroup b is a candidate with its
+// own coordinates and its own entry of `lengths`, and reads the maps of chain b / group.  A template argument, not a run-time one: as
+// live run-time scalars the two cost the plain kernel 4 % (more spills at 256 registers, measured), so <false> keeps the code it had.
+template <bool GROUPED>
 __global__ __launch_bounds__(REFINE_THREADS) void refine_kernel(const float* __restrict__ xyz_in, const float* __restrict__ absval,
                                                                 const int* __restrict__ lengths, int L, Schedule sched, Params pr,
                                                                 float* __restrict__ xyz_out, int* __restrict__ status, double* __restrict__ diag,
-                                                                int* offsets_all, Entry* entries_all, double* history_all) {
+                                                                int* offsets_all, Entry* entries_all, double* history_all, int group) {
   extern __shared__ double lds[];
   double* X = lds;
   double* G = X + 9 * L;
@@ -408,7 +414,7 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_kernel(const float* __r
   double* S = history_all + (long)b * 2 * REFINE_HISTORY * 9 * L;      // slot k at S + k * 9 L
   double* Y = S + (long)REFINE_HISTORY * 9 * L;
   const long slot = 9L * L;
-  build_lists(absval + (long)b * 4 * L * L, L, n, pr.arm_min, offsets, entries);
+  build_lists(absval + (long)(GROUPED ? b / group : b) * 4 * L * L, L, n, pr.arm_min, offsets, entries);
 
   double terms[8];
   const Stage last = sched.s[sched.count - 1];
@@ -563,7 +569,16 @@ long refine_workspace_bytes(int B, int L) {
 int launch_restraint_energy(const float* xyz, const float* absval, const int* lengths, int B, int L, const double* stage6, float dist_std,
                             float angle_std_deg, float arm_min_deg, double* out9, double* grad, void* workspace, long workspace_bytes,
                             hipStream_t s) {
-  T2P_REQUIRE(xyz && absval && lengths && stage6 && out9 && grad && workspace && B > 0 && L > 0, "restraint_energy arguments");
+  T2P_REQUIRE(grad, "restraint_energy arguments");
+  return launch_restraint_energy_grouped(xyz, absval, lengths, B, 1, L, stage6, dist_std, angle_std_deg, arm_min_deg, out9, grad, workspace,
+                                         workspace_bytes, s);
+}
+
+// B candidates, each with its own coordinates and length; candidate c reads the maps of chain c / group; grad may be null
+int launch_restraint_energy_grouped(const float* xyz, const float* absval, const int* lengths, int B, int group, int L, const double* stage6,
+                                    float dist_std, float angle_std_deg, float arm_min_deg, double* out9, double* grad, void* workspace,
+                                    long workspace_bytes, hipStream_t s) {
+  T2P_REQUIRE(xyz && absval && lengths && stage6 && out9 && workspace && B > 0 && L > 0 && group > 0, "restraint_energy arguments");
   T2P_REQUIRE(L <= REFINE_MAX_L && B <= 65535, "restraint_energy: at most " + std::to_string(REFINE_MAX_L) + " residues and 65535 chains");
   Stage st;
   Params pr;
@@ -573,9 +588,10 @@ int launch_restraint_energy(const float* xyz, const float* absval, const int* le
   T2P_REQUIRE(workspace_bytes >= (long)ws.total, "restraint_energy: workspace smaller than t2p_op_refine_ws(batch, L)");
   char* w = (char*)workspace;
   const int lds = refine_lds_bytes(L);
-  T2P_TRY(ensure_dynamic_lds((const void*)restraint_energy_kernel, lds));
-  hipLaunchKernelGGL(restraint_energy_kernel, dim3(B), dim3(REFINE_THREADS), lds, s, xyz, absval, lengths, L, st, pr, out9, grad,
-                     (int*)(w + ws.offsets), (Entry*)(w + ws.entries));
+  auto kernel = group == 1 && grad ? restraint_energy_kernel<false> : restraint_energy_kernel<true>;
+  T2P_TRY(ensure_dynamic_lds((const void*)kernel, lds));
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(REFINE_THREADS), lds, s, xyz, absval, lengths, L, st, pr, out9, grad, (int*)(w + ws.offsets),
+                     (Entry*)(w + ws.entries), group);
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }
@@ -583,7 +599,17 @@ int launch_restraint_energy(const float* xyz, const float* absval, const int* le
 int launch_refine_backbone(const float* xyz_in, const float* absval, const int* lengths, int B, int L, const double* schedule, int n_stages,
                            float dist_std, float angle_std_deg, float arm_min_deg, float* xyz_out, int* status, double* diag, void* workspace,
                            long workspace_bytes, hipStream_t s) {
-  T2P_REQUIRE(xyz_in && absval && lengths && schedule && xyz_out && status && diag && workspace && B > 0 && L > 0, "refine_backbone arguments");
+  return launch_refine_grouped(xyz_in, absval, lengths, B, 1, L, schedule, n_stages, dist_std, angle_std_deg, arm_min_deg, xyz_out,
+                               status, diag, workspace, workspace_bytes, s);
+}
+
+// B candidates, each with its own coordinates and length (one below 2 is how a caller leaves a candidate out: status -1, zeros);
+// candidate c reads the maps of chain c / group
+int launch_refine_grouped(const float* xyz_in, const float* absval, const int* lengths, int B, int group, int L,
+                          const double* schedule, int n_stages, float dist_std, float angle_std_deg, float arm_min_deg, float* xyz_out,
+                          int* status, double* diag, void* workspace, long workspace_bytes, hipStream_t s) {
+  T2P_REQUIRE(xyz_in && absval && lengths && schedule && xyz_out && status && diag && workspace && B > 0 && L > 0 && group > 0,
+              "refine_backbone arguments");
   T2P_REQUIRE(L <= REFINE_MAX_L && B <= 65535, "refine_backbone: at most " + std::to_string(REFINE_MAX_L) + " residues and 65535 chains");
   T2P_REQUIRE(n_stages >= 1 && n_stages <= REFINE_MAX_STAGES, "refine_backbone: 1 to " + std::to_string(REFINE_MAX_STAGES) + " stages");
   Schedule sched;
@@ -596,9 +622,10 @@ int launch_refine_backbone(const float* xyz_in, const float* absval, const int* 
   T2P_REQUIRE(workspace_bytes >= (long)ws.total, "refine_backbone: workspace smaller than t2p_op_refine_ws(batch, L)");
   char* w = (char*)workspace;
   const int lds = refine_lds_bytes(L);
-  T2P_TRY(ensure_dynamic_lds((const void*)refine_kernel, lds));
-  hipLaunchKernelGGL(refine_kernel, dim3(B), dim3(REFINE_THREADS), lds, s, xyz_in, absval, lengths, L, sched, pr, xyz_out, status, diag,
-                     (int*)(w + ws.offsets), (Entry*)(w + ws.entries), (double*)(w + ws.history));
+  auto kernel = group == 1 ? refine_kernel<false> : refine_kernel<true>;
+  T2P_TRY(ensure_dynamic_lds((const void*)kernel, lds));
+  hipLaunchKernelGGL(kernel, dim3(B), dim3(REFINE_THREADS), lds, s, xyz_in, absval, lengths, L, sched, pr, xyz_out, status, diag,
+                     (int*)(w + ws.offsets), (Entry*)(w + ws.entries), (double*)(w + ws.history), group);
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }

@@ -307,6 +307,30 @@ int launch_refine_backbone(const float* xyz_in, const float* absval, const int* 
 int launch_restraint_energy(const float* xyz, const float* absval, const int* lengths, int B, int L, const double* stage6, float dist_std,
                             float angle_std_deg, float arm_min_deg, double* out9, double* grad, void* workspace, long workspace_bytes,
                             hipStream_t s);
+// the same two kernels over B candidates that share maps: every candidate has its own coordinates and its own entry of lengths, and
+// candidate c reads the maps of chain c / group (absval holds B / group chains; the workspace is that of B chains).  A length below 2
+// leaves a candidate out (status -1, zeros).  grad may be null.  group = 1 is the two launchers above.
+int launch_refine_grouped(const float* xyz_in, const float* absval, const int* lengths, int B, int group, int L,
+                          const double* schedule, int n_stages, float dist_std, float angle_std_deg, float arm_min_deg, float* xyz_out,
+                          int* status, double* diag, void* workspace, long workspace_bytes, hipStream_t s);
+int launch_restraint_energy_grouped(const float* xyz, const float* absval, const int* lengths, int B, int group, int L, const double* stage6,
+                                    float dist_std, float angle_std_deg, float arm_min_deg, double* out9, double* grad, void* workspace,
+                                    long workspace_bytes, hipStream_t s);
+
+// ---- refinement in rounds (refine_rounds.hip) ----
+// The phi / psi move on N / CA / C chains held in Cartesian coordinates, and the loop perturb -> minimise -> select of rosetta_min/run.py
+// on the device: per round one move launch, one refine launch over batch x replicas workgroups, one energy launch, one selection launch.
+constexpr int REFINE_MAX_ROUNDS = 8, REFINE_MAX_REPLICAS = 16, REFINE_STREAM_STRIDE = 16;
+// in_status (may be null): a chain whose entry is neither 0 nor 1 keeps it; cand_lengths (may be null): [B][replicas], the chain's length
+// for a candidate that was written and -1 for one that was refused -- what launch_refine_grouped takes
+int launch_perturb_torsions(const float* xyz_in, const int* lengths, const int* chain_ids, const int* in_status, int B, int L, int replicas,
+                            float amp_deg, unsigned long long seed, unsigned long long stream, int keep_first, float* xyz_out, int* status,
+                            int* cand_lengths, hipStream_t s);
+long refine_rounds_workspace_bytes(int B, int L, int replicas);      // -1 when L or replicas is out of range
+int launch_refine_rounds(const float* xyz_in, const float* absval, const int* lengths, const int* chain_ids, int B, int L,
+                         const double* schedules, int rounds, int n_stages, int replicas, const double* select_stage, float amp_deg,
+                         unsigned long long seed, unsigned long long stream_base, float dist_std, float angle_std_deg, float arm_min_deg,
+                         float* xyz_out, int* status, double* diag, double* trace, void* workspace, long workspace_bytes, hipStream_t s);
 
 // ---- scoring folded backbones: TM-align (tmalign.hip) ----
 // The default path of the reference's tm/TMalign.cpp for pairs of CA traces: xyz_* [n][L][atoms][3] fp32 (atoms = 3: N / CA / C, atom 1

@@ -80,7 +80,8 @@ def fold_maps_batch(absval, lengths, known_below=19.0, stress_steps=300, dist_st
     return xyz, status, placed, diag
 
 
-def fold_6d_batch(samples, known_below=19.0, stress_steps=300, dist_std=2.0, angle_std=10.0, refine=False, schedule=None, arm_min=None):
+def fold_6d_batch(samples, known_below=19.0, stress_steps=300, dist_std=2.0, angle_std=10.0, refine=False, schedule=None, arm_min=None,
+                  refine_rounds=1, refine_replicas=1, refine_seed=0, refine_stream=0, chain_ids=None):
     """``samples``: (B, C, L, L) float32 on the device, as the samplers return them.  Decodes and folds.  Returns a dict: ``xyz``
     (B, L, 3, 3), ``status`` (B,), ``placed`` (B, L), ``diag`` (B, 16) device tensors, ``absval`` (the decoded maps the fold read,
     (B, 4, L*L) on the device), ``lengths`` (B,) int32 on the host and
@@ -89,14 +90,25 @@ def fold_6d_batch(samples, known_below=19.0, stress_steps=300, dist_std=2.0, ang
 
     ``refine=True`` then minimises every chain against the restraint set (text2protein_amd/refine.py; ``schedule`` and ``arm_min`` as
     there, at most 256 residues): ``xyz`` is the refined backbone, ``xyz_fold`` the fold's own, ``refine`` the per-chain diagnostics
-    of the minimisation and ``refine_status`` / ``refine_diag`` its device tensors.  ``status``, ``diag`` and ``chains`` stay the fold's."""
+    of the minimisation and ``refine_status`` / ``refine_diag`` its device tensors.  ``status``, ``diag`` and ``chains`` stay the fold's.
+    With ``refine_rounds`` or ``refine_replicas`` above 1 the minimisation runs in rounds (``refine.refine_rounds_batch``: the
+    reference's schedules, ``refine_seed`` / ``refine_stream`` / ``chain_ids`` for its draws; ``schedule`` is not used) and the dict
+    gains ``refine_trace`` and ``refine_rounds`` (``refine.rounds_diagnostics``); with both at 1 the route and the bits are those of
+    ``refine_backbone_batch``."""
     lengths, _, absval = decode_6d_batch(samples)
     xyz, status, placed, diag = fold_maps_batch(absval, lengths, known_below, stress_steps, dist_std, angle_std)
     out = {"xyz": xyz, "status": status, "placed": placed, "diag": diag, "lengths": lengths, "absval": absval,
            "chains": diagnostics(status, placed, diag, lengths)}
     if refine:
         from . import refine as R
-        rx, rstatus, rdiag = R.refine_backbone_batch(xyz, absval, lengths, schedule, dist_std, angle_std, R.ARM_MIN if arm_min is None else arm_min)
+        arm = R.ARM_MIN if arm_min is None else arm_min
+        if int(refine_rounds) == 1 and int(refine_replicas) == 1:
+            rx, rstatus, rdiag = R.refine_backbone_batch(xyz, absval, lengths, schedule, dist_std, angle_std, arm)
+        else:
+            rx, rstatus, rdiag, trace = R.refine_rounds_batch(xyz, absval, lengths, refine_rounds, refine_replicas, seed=refine_seed,
+                                                              stream_base=refine_stream, chain_ids=chain_ids, dist_std=dist_std,
+                                                              angle_std=angle_std, arm_min=arm)
+            out.update(refine_trace=trace, refine_rounds=R.rounds_diagnostics(trace))
         out.update(xyz=rx, xyz_fold=xyz, refine_status=rstatus, refine_diag=rdiag, refine=R.diagnostics(rstatus, rdiag, lengths))
     return out
 
