@@ -7,7 +7,9 @@ restraint score (and only it) in another precision, which is how the fixture's f
 """
 import numpy as np
 
-K1, K2, K3 = -0.58273431, 0.56802827, -0.54067466          # the featuriser's virtual-Cb identity (dataset.py:409)
+import geom_oracle as GO
+
+K1, K2, K3 = GO.K1, GO.K2, GO.K3                            # the featuriser's virtual-Cb identity (dataset.py:409)
 N_CA, CA_C, N_CA_C, C_N = 1.458, 1.525, 111.0, 1.329
 DMAX, NEIGHBOUR = 20.0, 12.0
 
@@ -140,21 +142,7 @@ def closure(xyz):
 
 
 def virtual_cb(xyz):
-    b, c = xyz[:, 1] - xyz[:, 0], xyz[:, 2] - xyz[:, 1]
-    return K1 * np.cross(b, c) + K2 * b + K3 * c + xyz[:, 1]
-
-
-def _dihedral(a, b, c, d):
-    b0, b1, b2 = a - b, c - b, d - c
-    b1 = b1 / np.linalg.norm(b1, axis=-1, keepdims=True)
-    v = b0 - (b0 * b1).sum(-1, keepdims=True) * b1
-    w = b2 - (b2 * b1).sum(-1, keepdims=True) * b1
-    return np.arctan2((np.cross(b1, v) * w).sum(-1), (v * w).sum(-1))
-
-
-def _wrap(x, dtype):
-    two_pi = dtype(2.0 * np.pi)
-    return x - two_pi * np.round(x / two_pi)
+    return GO.virtual_cb(xyz[:, 0], xyz[:, 1], xyz[:, 2])
 
 
 def restraint_sets(maps):
@@ -178,12 +166,10 @@ def restraint_score(xyz, maps, dist_std=2.0, angle_std=10.0, dtype=np.float64):
     i, j = np.nonzero(sd)
     out.append((((np.linalg.norm(cb[i] - cb[j], axis=-1) - m["dist"][i, j]) / dtype(dist_std)) ** 2).sum(dtype=dtype))
     i, j = np.nonzero(so)
-    out.append(((_wrap(_dihedral(ca[i], cb[i], cb[j], ca[j]) - m["omega"][i, j], dtype) / astd) ** 2).sum(dtype=dtype))
+    out.append(((GO.wrap(GO.dihedral_projection(ca[i], cb[i], cb[j], ca[j]) - m["omega"][i, j], dtype) / astd) ** 2).sum(dtype=dtype))
     i, j = np.nonzero(sa)
-    out.append(((_wrap(_dihedral(nn[i], ca[i], cb[i], cb[j]) - m["theta"][i, j], dtype) / astd) ** 2).sum(dtype=dtype))
-    v, w = ca[i] - cb[i], cb[j] - cb[i]
-    ang = np.arctan2(np.linalg.norm(np.cross(v, w), axis=-1), (v * w).sum(-1))
-    out.append((((ang - m["phi"][i, j]) / astd) ** 2).sum(dtype=dtype))
+    out.append(((GO.wrap(GO.dihedral_projection(nn[i], ca[i], cb[i], cb[j]) - m["theta"][i, j], dtype) / astd) ** 2).sum(dtype=dtype))
+    out.append((((GO.angle(ca[i], cb[i], cb[j]) - m["phi"][i, j]) / astd) ** 2).sum(dtype=dtype))
     return np.array([float(v) for v in out]), np.array([int(sd.sum()), int(so.sum()), int(sa.sum()), int(sa.sum())])
 
 

@@ -8,9 +8,10 @@ gradient is scattered term by term with ``numpy.add.at`` where the kernel gather
 import numpy as np
 
 import fold_oracle as FO
+import geom_oracle as GO
 from oracle import philox
 
-K1, K2, K3 = FO.K1, FO.K2, FO.K3
+K1, K2, K3 = GO.K1, GO.K2, GO.K3
 NEIGHBOUR = FO.NEIGHBOUR
 DIST_STD, ANGLE_STD, ARM_MIN = 2.0, 10.0, 15.0
 BOND_SIGMA, ANGLE_SIGMA, PEPT_SIGMA = 0.02, 3.0, 6.0                     # A, degrees, degrees
@@ -20,7 +21,7 @@ REP_RADIUS, REP_MIN_SEP = 3.8, 2
 HISTORY, ARMIJO_C1, MAX_TRIALS, GRAD_TOL, CURVATURE_EPS = 8, 1e-4, 20, 1e-3, 1e-10
 W_DIST, W_ANG, W_REP, STAGE_ITERS = 3.0, 1.0, 3.0, 300
 SEP_ALL = 1 << 20                                                         # "up to the chain's end"
-GUARD = 1e-12                                                             # floor of every denominator
+GUARD = GO.GUARD                                                          # floor of every denominator
 TERMS = ("dist", "omega", "theta", "phi", "bond", "angle", "pept", "rep")
 
 
@@ -44,8 +45,7 @@ def restraint_lists(maps, arm_min=ARM_MIN):
     return dict(dist=np.nonzero(sd), omega=np.nonzero(so & ~flat & ~flat.T), theta=np.nonzero(sa & ~flat), phi=np.nonzero(sa))
 
 
-def _wrap(x):
-    return x - 2.0 * np.pi * np.round(x / (2.0 * np.pi))
+_wrap = GO.wrap
 
 
 def _dot(a, b):
@@ -53,11 +53,11 @@ def _dot(a, b):
 
 
 def _dihedral(p0, p1, p2, p3):
-    """Value (fold_oracle's sign) and the four gradients of the dihedral p0-p1-p2-p3, rows of points."""
+    """Value (geom_oracle.dihedral_cross) and the four gradients of the dihedral p0-p1-p2-p3, rows of points."""
+    val = GO.dihedral_cross(p0, p1, p2, p3)
     f, g, h = p0 - p1, p1 - p2, p3 - p2
     a, b = np.cross(f, g), np.cross(h, g)
     gl = np.sqrt(np.maximum(_dot(g, g), GUARD))
-    val = np.arctan2(_dot(np.cross(b, a), g) / gl, _dot(a, b))
     aa, bb = np.maximum(_dot(a, a), GUARD), np.maximum(_dot(b, b), GUARD)
     d0 = (-gl / aa)[:, None] * a
     d3 = (gl / bb)[:, None] * b
@@ -66,11 +66,11 @@ def _dihedral(p0, p1, p2, p3):
 
 
 def _angle(pa, pb, pc):
-    """Value and the three gradients of the angle at pb."""
+    """Value (geom_oracle.angle) and the three gradients of the angle at pb."""
+    val = GO.angle(pa, pb, pc)
     v, w = pa - pb, pc - pb
     cr = np.cross(v, w)
     sn = np.sqrt(_dot(cr, cr))
-    val = np.arctan2(sn, _dot(v, w))
     ga = np.cross(v, cr) / np.maximum(_dot(v, v) * sn, GUARD)[:, None]
     gc = -np.cross(w, cr) / np.maximum(_dot(w, w) * sn, GUARD)[:, None]
     return val, ga, -ga - gc, gc
@@ -83,7 +83,7 @@ def energy(xyz, maps, stage, dist_std=DIST_STD, angle_std=ANGLE_STD, arm_min=ARM
     lists = lists or restraint_lists(maps, arm_min)
     N, CA, C = x[:, 0], x[:, 1], x[:, 2]
     bv, cv = CA - N, C - CA
-    CB = K1 * np.cross(bv, cv) + K2 * bv + K3 * cv + CA
+    CB = GO.virtual_cb(N, CA, C)
     gN, gCA, gC, gCB = (np.zeros((n, 3)) for _ in range(4))
     terms = np.zeros(8)
     astd = np.deg2rad(angle_std)
@@ -253,8 +253,8 @@ def noisy_maps(clean, sd_dist, sd_ang, seed):
     out = {}
     out["dist"] = np.where(known, np.clip(d + sd_dist * sym(z[0]), 0.5, 19.99), d)
     om = np.asarray(clean["omega"], np.float64)
-    out["omega"] = np.where(known, _wrap(om + sd_ang * sym(z[1])), om)
-    out["theta"] = np.where(known, _wrap(np.asarray(clean["theta"], np.float64) + sd_ang * z[2]), clean["theta"])
+    out["omega"] = np.where(known, GO.wrap(om + sd_ang * sym(z[1])), om)
+    out["theta"] = np.where(known, GO.wrap(np.asarray(clean["theta"], np.float64) + sd_ang * z[2]), clean["theta"])
     out["phi"] = np.where(known, np.clip(np.asarray(clean["phi"], np.float64) + sd_ang * z[3], 0.01, np.pi - 0.01), clean["phi"])
     return {k: v.astype(np.float32) for k, v in out.items()}
 

@@ -9,6 +9,7 @@ infrastructure only.
 """
 import numpy as np
 
+import geom_oracle as GO
 import refine_oracle as RO
 from oracle import philox
 
@@ -42,14 +43,6 @@ def round_schedule(r, iters=RO.STAGE_ITERS, sep_lo=1):
     return [(sep_lo, hi, W_DIST_ROUNDS[r], W_ANG_ROUNDS[r], W_REP_ROUNDS[r], iters) for hi in (12, 24, RO.SEP_ALL)]
 
 
-def dihedral(p0, p1, p2, p3):
-    """The atan2 form of DESIGN.md 8i (refine_oracle._dihedral's value), for single points or rows of points."""
-    f, g, h = p0 - p1, p1 - p2, p3 - p2
-    a, b = np.cross(f, g), np.cross(h, g)
-    gl = np.sqrt(np.maximum((g * g).sum(-1), GUARD))
-    return np.arctan2((np.cross(b, a) * g).sum(-1) / gl, (a * b).sum(-1))
-
-
 def internals(xyz):
     """bond[k] = |a_k - a_k-1|, theta[k] = the angle at a_k-1, tau[k] = dihedral(a_k-3, a_k-2, a_k-1, a_k) for k >= 3 (zero before)."""
     a = np.asarray(xyz, np.float64).reshape(-1, 3)
@@ -58,9 +51,8 @@ def internals(xyz):
     if m > 3:
         p0, p1, p2, p3 = a[:-3], a[1:-2], a[2:-1], a[3:]
         bond[3:] = np.linalg.norm(p3 - p2, axis=-1)
-        v, w = p1 - p2, p3 - p2
-        theta[3:] = np.arctan2(np.linalg.norm(np.cross(v, w), axis=-1), (v * w).sum(-1))
-        tau[3:] = dihedral(p0, p1, p2, p3)
+        theta[3:] = GO.angle(p1, p2, p3)
+        tau[3:] = GO.dihedral_cross(p0, p1, p2, p3)
     return bond, theta, tau
 
 

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import geom_oracle as GO
 from helpers import GOLDEN, load_golden
 
 PDB = os.path.join(GOLDEN, "encode_chain.pdb")
@@ -112,8 +113,7 @@ def test_fixture_conditions_hold(gold):
         assert c.shape == (8, n, n) and mp.shape == (n, n) and np.array_equal(np.round(xyz, 3), xyz) and len(rep["sse"]) == n
         assert rep["cut_margin"] >= 1e-3 and rep["adj_margin"] >= 1e-3 and rep["shortest_projection"] >= 1e-2
         bb = xyz * ok[:, :, None]
-        b, cc = bb[:, 1] - bb[:, 0], bb[:, 2] - bb[:, 1]
-        cb = -0.58273431 * np.cross(b, cc) + 0.56802827 * b - 0.54067466 * cc + bb[:, 1]
+        cb = GO.virtual_cb(bb[:, 0], bb[:, 1], bb[:, 2])
         d = np.linalg.norm(cb[:, None] - cb[None, :], axis=-1)
         off = ~np.eye(n, dtype=bool)
         assert np.abs(d[off] - 20.0).min() >= 1e-3

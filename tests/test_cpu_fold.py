@@ -26,18 +26,30 @@ def _maps(gold, key):
 
 
 def test_ideal_cb_constants():
-    """The constexpr values the kernels are compiled with, read out of csrc/fold.hip, against the oracle's own derivation: |Cb - CA|
-    and N-CA-Cb from the virtual-Cb identity at N-CA 1.458, CA-C 1.525, N-CA-C 111.0, to the six decimals they are written with."""
+    """The constexpr values the kernels are compiled with, read out of csrc/backbone_geom.h (fold.hip takes them from there), against the
+    oracle's own derivation: |Cb - CA| and N-CA-Cb from the virtual-Cb identity at N-CA 1.458, CA-C 1.525, N-CA-C 111.0, to the six
+    decimals they are written with.  The float twins the fp32 kernels use are the doubles rounded once, each held by a static_assert to
+    the float literal of the same digits; no kernel file spells the identity's constants itself."""
+    import glob
     import os
     import re
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "text2protein_amd", "csrc", "fold.hip")).read()
-    found = {k: float(v) for k, v in re.findall(r"\b(K1|K2|K3|N_CA|C_N|R_CB|COS_NCACB|SIN_NCACB) = (-?\d+\.\d+)f[,;]", src)}
-    assert len(found) == 8, found
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "text2protein_amd", "csrc")
+    geom = open(os.path.join(csrc, "backbone_geom.h")).read()
+    names = {"K1": "K1", "K2": "K2", "K3": "K3", "N_CA": "BOND_N_CA", "C_N": "BOND_C_N", "R_CB": "R_CB", "COS_NCACB": "COS_NCACB", "SIN_NCACB": "SIN_NCACB"}
+    text = dict(re.findall(r"\b(K1|K2|K3|BOND_N_CA|BOND_C_N|R_CB|COS_NCACB|SIN_NCACB) = (-?\d+\.\d+)[,;]", geom))
+    assert len(text) == 8, text
+    found = {k: float(text[v]) for k, v in names.items()}
     want = {"K1": FO.K1, "K2": FO.K2, "K3": FO.K3, "N_CA": FO.N_CA, "C_N": FO.C_N, "R_CB": FO.R_CB, "COS_NCACB": math.cos(FO.A_NCACB),
             "SIN_NCACB": math.sin(FO.A_NCACB)}
     for k, v in want.items():
         assert abs(found[k] - v) <= (5.01e-7 if k in ("R_CB", "COS_NCACB", "SIN_NCACB") else 0.0), (k, found[k], v)
-    assert len(re.findall(r"-0\.58273431 \* cross|0\.56802827 \* bv|-0\.54067466 \* cv", src)) == 3      # the score's double copies
+    fold_src = open(os.path.join(csrc, "fold.hip")).read()
+    assert '#include "backbone_geom.h"' in fold_src and "using namespace geom;" in fold_src
+    for v in names.values():                                   # the fp32 kernels' constants: (float) of the double, equal to the float literal
+        assert f"{v}_F = (float){v}" in geom and f"{v}_F == {text[v]}f" in geom and f"{v}_F" in fold_src, v
+    assert "cb_offset(bv, cv)" in fold_src                     # the score's double Cb: the header's one formula
+    for path in glob.glob(os.path.join(csrc, "*.hip")):
+        assert not re.search(r"0\.58273431|0\.56802827|0\.54067466", open(path).read()), path
 
 
 @pytest.mark.parametrize("key", KEYS)

@@ -339,3 +339,14 @@ def test_vp_tables_follow_the_reference_arithmetic():
         assert float(scale[i]) == float(-1.0 / s1m[k])
         assert abs(float(xc[i]) - float(1.0 - (torch.sqrt(alphas[k]) - 1.0))) < 1e-7
         assert float(alpha[i]) == float(alphas[k]) and float(g[i]) == float(torch.sqrt(betas[k]))
+
+
+def test_structure_workspace_sizes_are_pinned():
+    """t2p_op_fold_ws / t2p_op_refine_ws / t2p_op_refine_rounds_ws are pure host functions over one 256-byte carve (WorkspaceCarve): a
+    handful of their values, recorded from the library before the three workspace structs shared that carve, refusals included."""
+    from text2protein_amd import _lib
+    lib = _lib.load()
+    assert [lib.t2p_op_fold_ws(*a) for a in ((1, 1), (3, 129), (32, 512), (1, 513), (0, 5))] == [1280, 261120, 36111360, -1, -1]
+    assert [lib.t2p_op_refine_ws(*a) for a in ((1, 1), (3, 129), (32, 256), (1, 512), (0, 5))] == [1792, 2032896, 76316928, -1, -1]
+    got = [lib.t2p_op_refine_rounds_ws(*a) for a in ((1, 5, 1, 1), (3, 129, 5, 8), (32, 256, 1, 8), (3, 128, 1, 17), (1, 512, 1, 1))]
+    assert got == [8960, 16489472, 615307520, -1, -1]

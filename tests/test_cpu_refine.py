@@ -100,8 +100,11 @@ def test_noisy_maps_are_reproducible_and_clipped(fold_gold):
 
 
 def test_kernel_constants_equal_the_oracles():
-    src = open(os.path.join(ROOT, "text2protein_amd", "csrc", "refine.hip")).read()
-    found = {k: float(v) for k, v in re.findall(r"\b([A-Z][A-Z0-9_]*) = (-?\d+(?:\.\d+)?(?:e-?\d+)?)[,;]", src)}
+    csrc = os.path.join(ROOT, "text2protein_amd", "csrc")
+    geom = open(os.path.join(csrc, "backbone_geom.h")).read()                                          # the shared geometry: K1..K3, the ideal backbone, GUARD
+    src = open(os.path.join(csrc, "refine.hip")).read()
+    assert '#include "backbone_geom.h"' in src and "using namespace geom;" in src
+    found = {k: float(v) for k, v in re.findall(r"\b([A-Z][A-Z0-9_]*) = (-?\d+(?:\.\d+)?(?:e-?\d+)?)[,;]", geom + src)}
     want = {"K1": RO.K1, "K2": RO.K2, "K3": RO.K3, "BOND_N_CA": RO.BOND_N_CA, "BOND_CA_C": RO.BOND_CA_C, "BOND_C_N": RO.BOND_C_N,
             "BOND_SIGMA": RO.BOND_SIGMA, "ANGLE_N_CA_C": RO.ANGLE_N_CA_C, "ANGLE_CA_C_N": RO.ANGLE_CA_C_N, "ANGLE_C_N_CA": RO.ANGLE_C_N_CA,
             "ANGLE_SIGMA": RO.ANGLE_SIGMA, "PEPT_SIGMA": RO.PEPT_SIGMA, "REP_RADIUS": RO.REP_RADIUS, "REP_MIN_SEP": RO.REP_MIN_SEP,
@@ -109,9 +112,9 @@ def test_kernel_constants_equal_the_oracles():
             "CURVATURE_EPS": RO.CURVATURE_EPS, "NEIGHBOUR": RO.NEIGHBOUR, "GUARD": RO.GUARD}
     for k, v in want.items():
         assert found.get(k) == v, (k, found.get(k), v)
-    fold_src = open(os.path.join(ROOT, "text2protein_amd", "csrc", "fold.hip")).read()
-    for k in ("K1", "K2", "K3"):
-        assert f"{k} = {want[k]:.8f}f" in fold_src, k                                                  # the same identity as the fold's
+    fold_src = open(os.path.join(csrc, "fold.hip")).read()
+    for k in ("K1", "K2", "K3"):                                                                       # the same identity as the fold's: its float
+        assert f"{k}_F == {want[k]:.8f}f" in geom and f"{k}_F = (float){k}" in geom and f"{k}_F" in fold_src, k      # twin, held to the literal
     hdr = open(os.path.join(ROOT, "text2protein_amd", "csrc", "t2p_kernels.h")).read()
     assert re.search(r"REFINE_MAX_L = 256, REFINE_MAX_STAGES = 8;", hdr)
 

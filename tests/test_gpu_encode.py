@@ -17,6 +17,7 @@ import pytest
 import torch
 import yaml
 
+import geom_oracle as GO
 from helpers import GOLDEN, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -145,8 +146,7 @@ def test_round_trip_through_decode(gold, encoded):
         xyz = gold[f"xyz_{keys[b]}"]
         n = xyz.shape[0]
         assert d["L"] == n
-        bv, cv = xyz[:, 1] - xyz[:, 0], xyz[:, 2] - xyz[:, 1]
-        cb = -0.58273431 * np.cross(bv, cv) + 0.56802827 * bv - 0.54067466 * cv + xyz[:, 1]
+        cb = GO.virtual_cb(xyz[:, 0], xyz[:, 1], xyz[:, 2])
         want = np.minimum(np.linalg.norm(cb[:, None] - cb[None, :], axis=-1), 20.0)
         np.fill_diagonal(want, 20.0)
         err = float(np.abs(d["dist_abs"].astype(np.float64) - want).max())

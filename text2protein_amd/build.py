@@ -14,7 +14,7 @@ LIB_ABLATION = os.path.join(CSRC, "libt2p_hip_ablation.so")   # measurement buil
 SOURCES = ["gemm.hip", "rowgemm.hip", "kernels.hip", "attention.hip", "smallconv.hip", "stfuse.hip", "ddim.hip", "fold.hip", "refine.hip", "refine_rounds.hip", "tmalign.hip", "sse.hip", "weightpack.hip", "engine.cpp", "sampler.cpp", "capi.cpp",
            "train_kernels.hip", "train.cpp", "train_capi.cpp"]
 GEMM_PARTS = 7          # gemm.hip is compiled once per -DT2P_GEMM_PART=k: the LDS-DMA instantiations build in parallel
-HEADERS = ["t2p_common.h", "plan.h", "t2p_kernels.h", "gemm_mfma.h", "philox.h", "update_loop.h", "engine.h", "sampler.h", "ddim.h", "train_kernels.h", "train.h", os.path.join("..", "..", "include", "t2p.h")]
+HEADERS = ["t2p_common.h", "plan.h", "t2p_kernels.h", "gemm_mfma.h", "philox.h", "update_loop.h", "engine.h", "sampler.h", "ddim.h", "train_kernels.h", "train.h", "wave_reduce.h", "backbone_geom.h", os.path.join("..", "..", "include", "t2p.h")]
 ARCH = "gfx950"
 
 

@@ -15,10 +15,13 @@
 //   fold_finish_kernel    one workgroup per chain: residues without a frame placed, closure of both hands, the hand kept, xyz
 //   restraint_rows_kernel one workgroup per map row (L x B): the four harmonic sums of that row, in double
 //   restraint_final_kernel  the rows of a chain summed in row order
-// Every reduction is a fixed butterfly over the lanes followed by a sum over the waves in wave order, every loop over residues runs in
-// index order: two calls give the same bits, and a chain gives the same bits whatever batch or padding it sits in.
+// Every reduction is a fixed butterfly over the lanes followed by a sum over the waves in wave order (wave_reduce.h), every loop over
+// residues runs in index order: two calls give the same bits, and a chain gives the same bits whatever batch or padding it sits in.
+// The vectors, the virtual Cb, the ideal backbone, the angle and the dihedral are backbone_geom.h's, shared with refine.hip.
+#include "backbone_geom.h"
 #include "t2p_common.h"
 #include "t2p_kernels.h"
+#include "wave_reduce.h"
 
 namespace t2p {
 namespace {
@@ -33,47 +36,7 @@ constexpr float FOLD_UNREACHED = 1.0e30f;
 constexpr float FOLD_DMAX = 20.f;       // an encoded far pair decodes to exactly this
 constexpr float FOLD_NEIGHBOUR = 12.f;  // the reference's restraint filter (rosetta_min/utils.py:137)
 
-// The featuriser's virtual Cb: Cb - CA = K1 (b x c) + K2 b + K3 c with b = CA - N, c = C - CA (dataset.py:409).
-constexpr float K1 = -0.58273431f, K2 = 0.56802827f, K3 = -0.54067466f;
-// Ideal backbone: |b| = 1.458, |c| = 1.525, angle N-CA-C = 111.0 deg, so b . c = -|b||c| cos(111 deg) = 0.796813 and
-// |b x c| = |b||c| sin(111 deg) = 2.075769.  b x c is orthogonal to b and c, hence
-//   |Cb - CA|^2 = K1^2 |b x c|^2 + K2^2 |b|^2 + K3^2 |c|^2 + 2 K2 K3 (b . c)
-//              = 1.463186 + 0.685891 + 0.679848 - 0.489432 = 2.339492          ->  R_CB = 1.529540 A
-//   cos(N-CA-Cb) = (-b) . (Cb - CA) / (|b| R_CB) = -(K2 |b|^2 + K3 (b . c)) / (|b| R_CB) = -0.776677 / 2.230069 = -0.348275
-//                                                                              ->  N-CA-Cb = 110.3818 deg, sin = 0.937392
-constexpr float N_CA = 1.458f, C_N = 1.329f;
-constexpr float R_CB = 1.529540f, COS_NCACB = -0.348275f, SIN_NCACB = 0.937392f;
-
-struct F3 { float x, y, z; };
-__device__ __forceinline__ F3 operator+(F3 a, F3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ F3 operator-(F3 a, F3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ F3 operator*(float s, F3 a) { return {s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ float dot(F3 a, F3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ F3 cross(F3 a, F3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ F3 load3(const float* p) { return {p[0], p[1], p[2]}; }
-__device__ __forceinline__ void store3(float* p, F3 a) { p[0] = a.x; p[1] = a.y; p[2] = a.z; }
-
-template <typename T> __device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-// sums of NV values over the workgroup, the same bits in every thread; `red` holds NW * NV values
-template <int NV, int NW, typename T> __device__ __forceinline__ void block_sum(T (&v)[NV], T* red) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = wave_sum(v[k]);
-  __syncthreads();
-  if (lane == 0)
-    for (int k = 0; k < NV; ++k) red[w * NV + k] = v[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    T s = 0;
-    for (int q = 0; q < NW; ++q) s += red[q * NV + k];
-    v[k] = s;
-  }
-}
+using namespace geom;        // V3 / F3 / D3, the virtual Cb, the ideal backbone, the dihedrals (backbone_geom.h)
 
 __device__ __forceinline__ bool proper_length(int n, int L) { return n >= 1 && n <= L; }
 // the symmetric distance of a pair: the upper-triangle entry
@@ -122,8 +85,7 @@ __global__ __launch_bounds__(FOLD_THREADS) void fold_embed_kernel(const float* _
     if (v < 0.5f * FOLD_UNREACHED) longest = fmaxf(longest, v);
     else unreached[0] += 1.f;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) longest = fmaxf(longest, __shfl_xor(longest, off, 64));
+  longest = wave_max(longest);
   if (lane == 0) rowmean[wave] = longest;
   __syncthreads();
   for (int q = 0; q < FOLD_WAVES; ++q) longest = fmaxf(longest, rowmean[q]);
@@ -246,10 +208,7 @@ __global__ __launch_bounds__(FOLD_THREADS) void fold_embed_kernel(const float* _
           gx += coef * dx; gy += coef * dy; gz += coef * dz;
         }
       }
-#pragma unroll
-      for (int off = FOLD_LANES / 2; off > 0; off >>= 1) {
-        gx += __shfl_xor(gx, off, 64); gy += __shfl_xor(gy, off, 64); gz += __shfl_xor(gz, off, 64);
-      }
+      lanes_sum<FOLD_LANES>(gx, gy, gz);
       if (i < n && sub == 0) {
         const float s = 0.5f / (float)degree[i];
         Y[3 * i] = X[3 * i] - s * gx; Y[3 * i + 1] = X[3 * i + 1] - s * gy; Y[3 * i + 2] = X[3 * i + 2] - s * gz;
@@ -295,12 +254,12 @@ __global__ __launch_bounds__(256) void fold_frames_kernel(const float* __restric
   const float* theta = maps + 2L * L * L;
   const float* phi = maps + 3L * L * L;
   const float* X = cb + (long)b * L * 3;
-  const F3 ci = load3(X + 3 * i);
+  const F3 ci = load3<float>(X + 3 * i);
   float s[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};     // A: xx xy xz yy yz zz, rhs x y z, count
   for (int j = lane; j < n; j += 64) {
     const float d = pair_dist(dmap, n, i, j);
     if (j == i || !(d < known_below) || !(d <= FOLD_NEIGHBOUR)) continue;
-    F3 e = load3(X + 3 * j) - ci;
+    F3 e = load3<float>(X + 3 * j) - ci;
     e = (1.f / fmaxf(sqrtf(dot(e, e)), 1e-6f)) * e;
     const float cp = cosf(phi[(long)i * n + j]);
     s[0] += e.x * e.x; s[1] += e.x * e.y; s[2] += e.x * e.z; s[3] += e.y * e.y; s[4] += e.y * e.z; s[5] += e.z * e.z;
@@ -325,7 +284,7 @@ __global__ __launch_bounds__(256) void fold_frames_kernel(const float* __restric
   for (int j = lane; j < n; j += 64) {
     const float d = pair_dist(dmap, n, i, j);
     if (j == i || !(d < known_below) || !(d <= FOLD_NEIGHBOUR)) continue;
-    F3 e = load3(X + 3 * j) - ci;
+    F3 e = load3<float>(X + 3 * j) - ci;
     e = (1.f / fmaxf(sqrtf(dot(e, e)), 1e-6f)) * e;
     F3 w = e - dot(e, a) * a;
     const float wn = sqrtf(dot(w, w));
@@ -352,13 +311,13 @@ __global__ __launch_bounds__(256) void fold_frames_kernel(const float* __restric
     }
     p = (1.f / pn) * p;
     const F3 cbh = {ci.x, ci.y, m * ci.z}, uh = {u.x, u.y, m * u.z}, ah = -1.f * uh;
-    const F3 ca = cbh + R_CB * uh;
-    const F3 nn = ca + N_CA * (COS_NCACB * ah + SIN_NCACB * p);
+    const F3 ca = cbh + R_CB_F * uh;
+    const F3 nn = ca + BOND_N_CA_F * (COS_NCACB_F * ah + SIN_NCACB_F * p);
     // C from the identity, linear in c: (K3 I + K1 [b]x) c = (Cb - CA) - K2 b, and
     // (alpha I + beta [b]x)^-1 = (alpha^2 I - alpha beta [b]x + beta^2 b b^T) / (alpha (alpha^2 + beta^2 |b|^2))
-    const F3 bv = ca - nn, r = (cbh - ca) - K2 * bv;
-    const float den = K3 * (K3 * K3 + K1 * K1 * dot(bv, bv));
-    const F3 c = (1.f / den) * ((K3 * K3) * r - (K3 * K1) * cross(bv, r) + (K1 * K1 * dot(bv, r)) * bv);
+    const F3 bv = ca - nn, r = (cbh - ca) - K2_F * bv;
+    const float den = K3_F * (K3_F * K3_F + K1_F * K1_F * dot(bv, bv));
+    const F3 c = (1.f / den) * ((K3_F * K3_F) * r - (K3_F * K1_F) * cross(bv, r) + (K1_F * K1_F * dot(bv, r)) * bv);
     store3(f, nn); store3(f + 3, ca); store3(f + 6, ca + c);
   }
 }
@@ -398,11 +357,11 @@ __global__ __launch_bounds__(256) void fold_finish_kernel(const int* __restrict_
     const float m = h ? -1.f : 1.f;
     const F3 ci = {X[3 * i], X[3 * i + 1], m * X[3 * i + 2]};
     if (k >= n) {
-      store3(f, ci + F3{-1.2f, -0.9f, 0.f}); store3(f + 3, ci + F3{0.f, -R_CB, 0.f}); store3(f + 6, ci + F3{1.25f, -0.9f, 0.f});
+      store3(f, ci + F3{-1.2f, -0.9f, 0.f}); store3(f + 3, ci + F3{0.f, -R_CB_F, 0.f}); store3(f + 6, ci + F3{1.25f, -0.9f, 0.f});
     } else {
       const float* g = frames + (((long)b * 2 + h) * L + k) * 9;      // a framed residue: never written here
       const F3 ck = {X[3 * k], X[3 * k + 1], m * X[3 * k + 2]};
-      for (int q = 0; q < 3; ++q) store3(f + 3 * q, ci + (load3(g + 3 * q) - ck));
+      for (int q = 0; q < 3; ++q) store3(f + 3 * q, ci + (load3<float>(g + 3 * q) - ck));
     }
   }
   __syncthreads();
@@ -411,8 +370,8 @@ __global__ __launch_bounds__(256) void fold_finish_kernel(const int* __restrict_
     for (int h = 0; h < 2; ++h) {
       const float* f = frames + (((long)b * 2 + h) * L + i) * 9;
       if (i + 1 < n) {
-        const F3 d = load3(f + 6) - load3(f + 9);
-        s[h] += fabsf(sqrtf(dot(d, d)) - C_N);
+        const F3 d = load3<float>(f + 6) - load3<float>(f + 9);
+        s[h] += fabsf(sqrtf(dot(d, d)) - BOND_C_N_F);
       }
       s[2 + h] += (float)bad[((long)b * 2 + h) * L + i];
     }
@@ -444,32 +403,10 @@ __global__ __launch_bounds__(256) void fold_finish_kernel(const int* __restrict_
 //   theta  a != b, d[a][b] <= 12              circular, dihedral N_a CA_a Cb_a Cb_b
 //   phi    the same pairs                     harmonic, angle CA_a Cb_a Cb_b
 // with Cb the virtual Cb of the given backbone.  The filter reads d[a][b] as stored, not symmetrised, as the reference does.
-struct D3 { double x, y, z; };
-__device__ __forceinline__ D3 operator+(D3 a, D3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ D3 operator-(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ D3 operator*(double s, D3 a) { return {s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ double dot(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ D3 cross(D3 a, D3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ D3 loadd3(const float* p) { return {(double)p[0], (double)p[1], (double)p[2]}; }
 __device__ __forceinline__ void residue_atoms(const float* r, D3& nn, D3& ca, D3& cbeta) {
-  nn = loadd3(r); ca = loadd3(r + 3);
-  const D3 bv = ca - nn, cv = loadd3(r + 6) - ca;
-  cbeta = ca + (-0.58273431 * cross(bv, cv) + 0.56802827 * bv + -0.54067466 * cv);       // K1, K2, K3 as doubles
-}
-// dihedral a-b-c-d; a degenerate one (zero axis or zero projections) is 0, as in the encode
-__device__ __forceinline__ double dihedral(D3 a, D3 b, D3 c, D3 d) {
-  const D3 b0 = a - b, b2 = d - c;
-  D3 b1 = c - b;
-  const double l = sqrt(dot(b1, b1));
-  if (!(l > 0.0)) return 0.0;
-  b1 = (1.0 / l) * b1;
-  const D3 v = b0 - dot(b0, b1) * b1, w = b2 - dot(b2, b1) * b1;
-  const double y = dot(cross(b1, v), w), x = dot(v, w);
-  return (x == 0.0 && y == 0.0) ? 0.0 : atan2(y, x);
-}
-__device__ __forceinline__ double wrap_angle(double x) {
-  const double two_pi = 6.283185307179586476925;
-  return x - two_pi * rint(x / two_pi);
+  nn = load3<double>(r); ca = load3<double>(r + 3);
+  const D3 bv = ca - nn, cv = load3<double>(r + 6) - ca;
+  cbeta = ca + cb_offset(bv, cv);
 }
 
 __global__ __launch_bounds__(128) void restraint_rows_kernel(const float* __restrict__ xyz, const float* __restrict__ absval,
@@ -502,17 +439,14 @@ __global__ __launch_bounds__(128) void restraint_rows_kernel(const float* __rest
     }
     const double om = maps[LL + e];
     if (i < j && om != 0.0) {
-      term = wrap_angle(dihedral(cai, cbi, cbj, caj) - om) * inv_angle_std;
+      term = wrap_angle(dihedral_or_zero(cai, cbi, cbj, caj) - om) * inv_angle_std;
       term *= term;
       s[1] += isfinite(term) ? term : 0.0; s[5] += 1.0;
     }
-    term = wrap_angle(dihedral(ni, cai, cbi, cbj) - (double)maps[2 * LL + e]) * inv_angle_std;
+    term = wrap_angle(dihedral_or_zero(ni, cai, cbi, cbj) - (double)maps[2 * LL + e]) * inv_angle_std;
     term *= term;
     s[2] += isfinite(term) ? term : 0.0; s[6] += 1.0;
-    const D3 v = cai - cbi, cr = cross(v, dv);
-    const double sn = sqrt(dot(cr, cr)), cs = dot(v, dv);
-    const double ang = (sn == 0.0 && cs == 0.0) ? 0.0 : atan2(sn, cs);
-    term = (ang - (double)maps[3 * LL + e]) * inv_angle_std;
+    term = (angle(cai, cbi, cbj) - (double)maps[3 * LL + e]) * inv_angle_std;
     term *= term;
     s[3] += isfinite(term) ? term : 0.0; s[7] += 1.0;
   }
@@ -532,18 +466,17 @@ __global__ __launch_bounds__(64) void restraint_final_kernel(const int* __restri
   out[(long)b * stride + t] = s;
 }
 
-struct FoldWorkspace {            // byte offsets into the caller's workspace, every part 256-byte aligned
+struct FoldWorkspace {            // byte offsets into the caller's workspace (WorkspaceCarve)
   size_t cb, frames, bad, info, rows, mat, total;
   FoldWorkspace(int B, int L) {
-    size_t o = 0;
-    auto take = [&o](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
-    cb = take((size_t)B * L * 3 * 4);
-    frames = take((size_t)B * 2 * L * 9 * 4);
-    bad = take((size_t)B * 2 * L * 4);
-    info = take((size_t)B * 8 * 4);
-    rows = take((size_t)B * L * 8 * 8);
-    mat = take(L > FOLD_LDS_MAX ? (size_t)B * L * L * 4 : 0);
-    total = o;
+    WorkspaceCarve w;
+    cb = w.take((size_t)B * L * 3 * 4);
+    frames = w.take((size_t)B * 2 * L * 9 * 4);
+    bad = w.take((size_t)B * 2 * L * 4);
+    info = w.take((size_t)B * 8 * 4);
+    rows = w.take((size_t)B * L * 8 * 8);
+    mat = w.take(L > FOLD_LDS_MAX ? (size_t)B * L * L * 4 : 0);
+    total = w.total;
   }
 };
 
@@ -563,7 +496,7 @@ int launch_restraint_score(const float* xyz, const float* absval, const int* len
   T2P_REQUIRE(workspace_bytes >= (long)ws.total, "restraint_score: workspace smaller than t2p_op_fold_ws(batch, L)");
   double* rows = (double*)((char*)workspace + ws.rows);
   hipLaunchKernelGGL(restraint_rows_kernel, dim3(L, B), dim3(128), 0, s, xyz, absval, lengths, L, 1.0 / (double)dist_std,
-                     1.0 / ((double)angle_std_deg * 0.017453292519943295), rows);
+                     1.0 / ((double)angle_std_deg * DEG), rows);
   T2P_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(restraint_final_kernel, dim3(B), dim3(64), 0, s, lengths, L, rows, out, stride);
   T2P_HIP_CHECK(hipGetLastError());

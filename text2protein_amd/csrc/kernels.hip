@@ -1,27 +1,14 @@
 // HBM-bound kernels of the score network and the SDE update (gfx950).
 // All activations are NHWC ([batch][pixel][channel], channel contiguous) so that 64-lane
 // wavefronts read 16-byte vectors of consecutive channels (coalesced 1 KiB per wave-instruction).
+#include "backbone_geom.h"
 #include "philox.h"
 #include "t2p_kernels.h"
 #include "update_loop.h"
+#include "wave_reduce.h"
 
 namespace t2p {
 
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ inline float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ inline double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ inline float silu_f(float x) { return x / (1.f + expf(-x)); }
 
 template <typename T> __device__ inline void store4(T* p, float a, float b, float c, float d);
@@ -167,8 +154,8 @@ __global__ __launch_bounds__(256) void gn_finalize_cols_kernel(const float* cs0,
     s += v.x;
     q += v.y;
   }
-  s = wave_sum_d(s);
-  q = wave_sum_d(q);
+  s = wave_sum(s);
+  q = wave_sum(q);
   if (lane == 0) { red[0][wave] = s; red[1][wave] = q; }
   __syncthreads();
   if (tid == 0) {
@@ -1451,8 +1438,8 @@ __global__ __launch_bounds__(64) void langevin_norm_finalize_kernel(const float*
   for (int b = 0; b < B; ++b) {
     double g = (double)sq_ws[((long)b * NORM_BLOCKS + lane) * 2 + 0];
     double z = (double)sq_ws[((long)b * NORM_BLOCKS + lane) * 2 + 1];
-    g = wave_sum_d(g);
-    z = wave_sum_d(z);
+    g = wave_sum(g);
+    z = wave_sum(z);
     tg += sqrt(g);
     tz += sqrt(z);
   }
@@ -1749,28 +1736,23 @@ int launch_decode6d(const float* x, int B, int C, int L, float* clipped, float* 
 // dataset.py:396-450 (get_coords6d), :200-239 (masks, padding channel) and :114-168 (get_coarse_constraints) for a padded batch.
 // Every vector the angles are taken from is built from SHORT differences -- the virtual-Cb offset of a residue (about 1.5 A) and
 // Ca_j - Ca_i -- so fp32 rounding of coordinates far from the origin does not enter: Cb_j - Cb_i = (Ca_j - Ca_i) + (off_j - off_i).
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 v3sub(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 v3add(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 v3neg(V3 a) { return {-a.x, -a.y, -a.z}; }
-__device__ __forceinline__ float v3dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 v3cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ V3 v3axpy(float s, V3 a, V3 b) { return {b.x - s * a.x, b.y - s * a.y, b.z - s * a.z}; }   // b - s a
+using geom::F3;
 
 // atom `a` (0 N, 1 Ca, 2 C) of residue r; a missing atom is (0, 0, 0) whatever the buffer holds (dataset.py:219)
-__device__ __forceinline__ V3 enc_atom(const float* xyz, const unsigned char* ok, long r, int a) {
+__device__ __forceinline__ F3 enc_atom(const float* xyz, const unsigned char* ok, long r, int a) {
   if (ok && !ok[r * 3 + a]) return {0.f, 0.f, 0.f};
   const float* p = xyz + (r * 3 + a) * 3;
   return {p[0], p[1], p[2]};
 }
 // Ca, b = Ca - N and off = Cb - Ca of residue r (dataset.py:405-409)
-__device__ __forceinline__ void enc_residue(const float* xyz, const unsigned char* ok, long r, V3& ca, V3& bv, V3& off) {
-  const V3 n = enc_atom(xyz, ok, r, 0), c = enc_atom(xyz, ok, r, 2);
+__device__ __forceinline__ void enc_residue(const float* xyz, const unsigned char* ok, long r, F3& ca, F3& bv, F3& off) {
+  const F3 n = enc_atom(xyz, ok, r, 0), c = enc_atom(xyz, ok, r, 2);
   ca = enc_atom(xyz, ok, r, 1);
-  bv = v3sub(ca, n);
-  const V3 cv = v3sub(c, ca), av = v3cross(bv, cv);
-  off = {-0.58273431f * av.x + 0.56802827f * bv.x - 0.54067466f * cv.x, -0.58273431f * av.y + 0.56802827f * bv.y - 0.54067466f * cv.y,
-         -0.58273431f * av.z + 0.56802827f * bv.z - 0.54067466f * cv.z};
+  bv = ca - n;
+  const F3 cv = c - ca, av = cross(bv, cv);
+  // geom::cb_offset(bv, cv) spelt per component: the order this kernel's code was generated from
+  off = {geom::K1_F * av.x + geom::K2_F * bv.x + geom::K3_F * cv.x, geom::K1_F * av.y + geom::K2_F * bv.y + geom::K3_F * cv.y,
+         geom::K1_F * av.z + geom::K2_F * bv.z + geom::K3_F * cv.z};
 }
 // residue r takes part iff r - 1, r and r + 1 (where they exist) hold all three atoms (dataset.py:209-218)
 __device__ __forceinline__ bool enc_valid(const unsigned char* ok, long base, int r, int n) {
@@ -1779,18 +1761,6 @@ __device__ __forceinline__ bool enc_valid(const unsigned char* ok, long base, in
   bool v = true;
   for (int q = lo; q <= hi; ++q) v = v && ok[(base + q) * 3] && ok[(base + q) * 3 + 1] && ok[(base + q) * 3 + 2];
   return v;
-}
-// get_dihedrals (dataset.py:364-380) with b0 = -(b - a), b1 = c - b, b2 = d - c given; |b1| = 0 is the reference's NaN -> nan_to_num -> 0.
-// A zero-length projected vector leaves x = y = 0 with signs that depend on the other vector (atan2(+-0, -0) is +-pi): the angle is
-// undefined there and 0 is written, whatever the signs of the zeros
-__device__ __forceinline__ float enc_dihedral(V3 b0, V3 b1, V3 b2) {
-  const float n1 = sqrtf(v3dot(b1, b1));
-  if (!(n1 > 0.f)) return 0.f;
-  const float inv = 1.f / n1;
-  b1 = {b1.x * inv, b1.y * inv, b1.z * inv};
-  const V3 v = v3axpy(v3dot(b0, b1), b1, b0), w = v3axpy(v3dot(b2, b1), b1, b2);
-  const float y = v3dot(v3cross(b1, v), w), x = v3dot(v, w);
-  return (x == 0.f && y == 0.f) ? 0.f : atan2f(y, x);
 }
 #define T2P_ENC_DMAX 20.f
 // one (sample, i, j) pixel per thread, consecutive threads along j: every channel row of the NCHW output is stored coalesced; every
@@ -1810,18 +1780,18 @@ __global__ __launch_bounds__(256) void encode_6d_kernel(const float* __restrict_
   if (m) {
     g0 = 1.f; g3 = -1.f;                                  // far pairs and the diagonal: dist = dmax, the angles 0 (dataset.py:422-434)
     if (i != j) {
-      V3 cai, bi, oi, caj, bj, oj;
+      F3 cai, bi, oi, caj, bj, oj;
       enc_residue(xyz, atom_ok, base + i, cai, bi, oi);
       enc_residue(xyz, atom_ok, base + j, caj, bj, oj);
-      const V3 d = v3add(v3sub(caj, cai), v3sub(oj, oi));  // Cb_j - Cb_i
-      const float dist = sqrtf(v3dot(d, d));
+      const F3 d = (caj - cai) + (oj - oi);                // Cb_j - Cb_i
+      const float dist = sqrtf(dot(d, d));
       if (dist <= T2P_ENC_DMAX) {
         g0 = dist / T2P_ENC_DMAX * 2.f - 1.f;
-        g1 = enc_dihedral(v3neg(oi), d, v3neg(oj)) / PI_F;          // Ca_i, Cb_i, Cb_j, Ca_j
-        g2 = enc_dihedral(v3neg(bi), oi, d) / PI_F;                  // N_i, Ca_i, Cb_i, Cb_j
-        const V3 v = v3neg(oi), cr = v3cross(v, d);                  // angle Ca_i, Cb_i, Cb_j
-        const bool degenerate = !(v3dot(v, v) > 0.f) || !(dist > 0.f);     // get_angles' 0 / 0 -> nan_to_num -> 0
-        g3 = degenerate ? 0.f : atan2f(sqrtf(v3dot(cr, cr)), v3dot(v, d)) / PI_F * 2.f - 1.f;
+        g1 = geom::dihedral_or_zero(-oi, d, -oj) / PI_F;             // Ca_i, Cb_i, Cb_j, Ca_j
+        g2 = geom::dihedral_or_zero(-bi, oi, d) / PI_F;              // N_i, Ca_i, Cb_i, Cb_j
+        const F3 v = -oi, cr = cross(v, d);                          // angle Ca_i, Cb_i, Cb_j
+        const bool degenerate = !(dot(v, v) > 0.f) || !(dist > 0.f);             // get_angles' 0 / 0 -> nan_to_num -> 0
+        g3 = degenerate ? 0.f : atan2f(sqrtf(dot(cr, cr)), dot(v, d)) / PI_F * 2.f - 1.f;
         g0 = g0 == g0 ? g0 : 0.f; g1 = g1 == g1 ? g1 : 0.f; g2 = g2 == g2 ? g2 : 0.f; g3 = g3 == g3 ? g3 : 0.f;   // never a NaN out
       }
     }
@@ -1854,11 +1824,11 @@ __global__ __launch_bounds__(256) void ss_constraints_kernel(const float* __rest
       const int i = s1 + e / w, j = s2 + e % w;
       float dn = 1.f;                                     // dist = dmax on the diagonal and beyond the cut-off
       if (i != j) {
-        V3 cai, bi, oi, caj, bj, oj;
+        F3 cai, bi, oi, caj, bj, oj;
         enc_residue(xyz, atom_ok, base + i, cai, bi, oi);
         enc_residue(xyz, atom_ok, base + j, caj, bj, oj);
-        const V3 d = v3add(v3sub(caj, cai), v3sub(oj, oi));
-        const float dist = sqrtf(v3dot(d, d));
+        const F3 d = (caj - cai) + (oj - oi);
+        const float dist = sqrtf(dot(d, d));
         if (dist <= T2P_ENC_DMAX) dn = dist / T2P_ENC_DMAX * 2.f - 1.f;
       }
       mn = fminf(mn, dn);

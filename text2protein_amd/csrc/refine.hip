@@ -15,13 +15,16 @@
 // sum, fill in j order), so an evaluation never rescans the maps.  The gradient is gathered: eight lanes own a residue, walk its list,
 // evaluate every term the residue takes part in -- (i, j) and (j, i) -- keep the share of their own residue and add it up by a fixed
 // butterfly; the energy of a term is counted by the residue that owns it (the smaller index, or the first of an ordered pair).  No
-// atomics, every reduction in a fixed order, nothing depends on the batch position or the padding: two calls give the same bits.
-// Every loop has a fixed bound.
+// atomics, every reduction in a fixed order (wave_reduce.h), nothing depends on the batch position or the padding: two calls give the
+// same bits.  Every loop has a fixed bound.  The virtual Cb, the angle and the dihedral's value are backbone_geom.h's: fold.hip scores
+// with the same Cb and angle, refine_rounds.hip measures with the same angle and dihedral.
 #include <algorithm>
 #include <cmath>
 
+#include "backbone_geom.h"
 #include "t2p_common.h"
 #include "t2p_kernels.h"
+#include "wave_reduce.h"
 
 namespace t2p {
 namespace {
@@ -34,13 +37,9 @@ constexpr int REFINE_HISTORY = 8;
 constexpr int REFINE_MAX_TRIALS = 20;
 constexpr double ARMIJO_C1 = 1e-4, GRAD_TOL = 1e-3, CURVATURE_EPS = 1e-10;
 constexpr double NEIGHBOUR = 12.0;       // the reference's restraint filter (rosetta_min/utils.py:137)
-constexpr double GUARD = 1e-12;          // floor of every denominator
-constexpr double PI = 3.14159265358979323846, DEG = 0.017453292519943295;
-// the featuriser's virtual Cb (dataset.py:409), as in fold.hip
-constexpr double K1 = -0.58273431, K2 = 0.56802827, K3 = -0.54067466;
-// ideal backbone (the geometry the fixture chains and fold.hip are built on)
-constexpr double BOND_N_CA = 1.458, BOND_CA_C = 1.525, BOND_C_N = 1.329, BOND_SIGMA = 0.02;
-constexpr double ANGLE_N_CA_C = 111.0, ANGLE_CA_C_N = 116.2, ANGLE_C_N_CA = 121.7, ANGLE_SIGMA = 3.0, PEPT_SIGMA = 6.0;
+using namespace geom;        // D3, GUARD, PI / DEG, K1..K3, the ideal bonds and ANGLE_N_CA_C, the dihedral and the angle (backbone_geom.h)
+constexpr double BOND_SIGMA = 0.02;
+constexpr double ANGLE_CA_C_N = 116.2, ANGLE_C_N_CA = 121.7, ANGLE_SIGMA = 3.0, PEPT_SIGMA = 6.0;
 constexpr double REP_RADIUS = 3.8;
 constexpr int REP_MIN_SEP = 2;
 
@@ -53,56 +52,12 @@ struct Stage { int sep_lo, sep_hi, max_iter; double w_dist, w_ang, w_rep; };
 struct Schedule { int count; Stage s[REFINE_MAX_STAGES]; };
 struct Params { double inv_dist_std, inv_angle_std, arm_min; };        // arm_min in rad
 
-struct D3 { double x, y, z; };
-__device__ __forceinline__ D3 operator+(D3 a, D3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ D3 operator-(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ D3 operator*(double s, D3 a) { return {s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ double dot(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ D3 cross(D3 a, D3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ D3 ld3(const double* p) { return {p[0], p[1], p[2]}; }
-__device__ __forceinline__ void st3(double* p, D3 a) { p[0] = a.x; p[1] = a.y; p[2] = a.z; }
-__device__ __forceinline__ void axpy(D3& acc, double s, D3 a) { acc.x += s * a.x; acc.y += s * a.y; acc.z += s * a.z; }
-__device__ __forceinline__ double wrap_angle(double x) { return x - 2.0 * PI * rint(x / (2.0 * PI)); }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-// sums of NV values over the workgroup, the same bits in every thread; `red` holds REFINE_WAVES * NV doubles
-template <int NV> __device__ __forceinline__ void block_sum(double (&v)[NV], double* red) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = wave_sum(v[k]);
-  __syncthreads();
-  if (lane == 0)
-    for (int k = 0; k < NV; ++k) red[w * NV + k] = v[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    double s = 0.0;
-    for (int q = 0; q < REFINE_WAVES; ++q) s += red[q * NV + k];
-    v[k] = s;
-  }
-}
-__device__ __forceinline__ double block_max(double v, double* red) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  for (int q = 0; q < REFINE_WAVES; ++q) v = fmax(v, red[q]);
-  return v;
-}
-
-// dihedral p0-p1-p2-p3 (the sign of fold.hip's dihedral) and its gradient with respect to the four points
+// dihedral p0-p1-p2-p3 (geom::dihedral_guarded) and its gradient with respect to the four points
 __device__ __forceinline__ double dihedral_grad(D3 p0, D3 p1, D3 p2, D3 p3, D3& d0, D3& d1, D3& d2, D3& d3) {
+  const double val = dihedral_guarded(p0, p1, p2, p3);
   const D3 f = p0 - p1, g = p1 - p2, h = p3 - p2;
   const D3 a = cross(f, g), b = cross(h, g);
   const double gl = sqrt(fmax(dot(g, g), GUARD));
-  const double y = dot(cross(b, a), g) / gl, x = dot(a, b);
-  const double val = (x == 0.0 && y == 0.0) ? 0.0 : atan2(y, x);
   const double aa = fmax(dot(a, a), GUARD), bb = fmax(dot(b, b), GUARD);
   d0 = (-gl / aa) * a;
   d3 = (gl / bb) * b;
@@ -111,11 +66,11 @@ __device__ __forceinline__ double dihedral_grad(D3 p0, D3 p1, D3 p2, D3 p3, D3& 
   d2 = (hb - fa) - d3;
   return val;
 }
-// angle at pb and its gradient with respect to pa and pc (that of pb is minus their sum)
+// angle at pb (geom::angle) and its gradient with respect to pa and pc (that of pb is minus their sum)
 __device__ __forceinline__ double angle_grad(D3 pa, D3 pb, D3 pc, D3& ga, D3& gc) {
-  const D3 v = pa - pb, w = pc - pb, cr = cross(v, w);
-  const double sn = sqrt(dot(cr, cr)), cs = dot(v, w);
-  const double val = (sn == 0.0 && cs == 0.0) ? 0.0 : atan2(sn, cs);
+  D3 v, w, cr;
+  double sn;
+  const double val = angle(pa, pb, pc, v, w, cr, sn);
   ga = (1.0 / fmax(dot(v, v) * sn, GUARD)) * cross(v, cr);
   gc = (-1.0 / fmax(dot(w, w) * sn, GUARD)) * cross(w, cr);
   return val;
@@ -156,7 +111,7 @@ __device__ void build_lists(const float* maps, int L, int n, double arm_min, int
     for (int j = lane; j < n; j += 64)
       if (j != i) c += pair_entry(maps, LL, n, i, j, arm_min).flags != 0;
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);      // not wave_sum(c): as a call it moves the generated code
     if (lane == 0) offsets[i + 1] = c;
   }
   __syncthreads();
@@ -187,9 +142,8 @@ __device__ void evaluate(const double* X, double* G, double* CB, double* red, in
                          const Params& pr, double (&terms)[8]) {
   const int t = threadIdx.x, sub = t & (REFINE_LANES - 1);
   for (int i = t; i < n; i += REFINE_THREADS) {
-    const D3 nn = ld3(X + 9 * i), ca = ld3(X + 9 * i + 3), cc = ld3(X + 9 * i + 6);
-    const D3 bv = ca - nn, cv = cc - ca;
-    st3(CB + 3 * i, ca + (K1 * cross(bv, cv) + K2 * bv + K3 * cv));
+    const D3 nn = load3<double>(X + 9 * i), ca = load3<double>(X + 9 * i + 3), cc = load3<double>(X + 9 * i + 6);
+    store3(CB + 3 * i, virtual_cb(nn, ca, cc));
   }
   __syncthreads();
   const double ca_coef = 2.0 * pr.inv_angle_std * st.w_ang, cd_coef = 2.0 * pr.inv_dist_std * st.w_dist;
@@ -199,13 +153,13 @@ __device__ void evaluate(const double* X, double* G, double* CB, double* red, in
     const int i = base + t / REFINE_LANES;
     D3 gN = {0, 0, 0}, gCA = {0, 0, 0}, gC = {0, 0, 0}, gCB = {0, 0, 0};
     if (i < n) {
-      const D3 ni = ld3(X + 9 * i), cai = ld3(X + 9 * i + 3), ci = ld3(X + 9 * i + 6), cbi = ld3(CB + 3 * i);
+      const D3 ni = load3<double>(X + 9 * i), cai = load3<double>(X + 9 * i + 3), ci = load3<double>(X + 9 * i + 6), cbi = load3<double>(CB + 3 * i);
       const int end = offsets[i + 1];
       for (int k = offsets[i] + sub; k < end; k += REFINE_LANES) {
         const Entry en = entries[k];
         const int j = en.j, sep = abs(i - j);
         if (sep < st.sep_lo || sep >= st.sep_hi) continue;
-        const D3 nj = ld3(X + 9 * j), caj = ld3(X + 9 * j + 3), cbj = ld3(CB + 3 * j);
+        const D3 nj = load3<double>(X + 9 * j), caj = load3<double>(X + 9 * j + 3), cbj = load3<double>(CB + 3 * j);
         const bool first = i < j;
         if (en.flags & HAS_DIST) {
           const D3 dv = cbi - cbj;
@@ -250,7 +204,7 @@ __device__ void evaluate(const double* X, double* G, double* CB, double* red, in
       // repulsion between CA atoms
       for (int j = sub; j < n; j += REFINE_LANES) {
         if (abs(i - j) < REP_MIN_SEP) continue;
-        const D3 dv = cai - ld3(X + 9 * j + 3);
+        const D3 dv = cai - load3<double>(X + 9 * j + 3);
         const double r = sqrt(dot(dv, dv));
         if (!(r < REP_RADIUS)) continue;
         const double res = REP_RADIUS - r;
@@ -275,7 +229,7 @@ __device__ void evaluate(const double* X, double* G, double* CB, double* red, in
       } else if ((sub == 1 && i > 0) || (sub == 2 && i + 1 < n)) {
         const bool mine = sub == 2;                           // residue i is the first of the link (a, a + 1): it owns the energy
         const int a = mine ? i : i - 1;
-        const D3 caa = ld3(X + 9 * a + 3), ca_c = ld3(X + 9 * a + 6), nb = ld3(X + 9 * a + 9), cab = ld3(X + 9 * a + 12);
+        const D3 caa = load3<double>(X + 9 * a + 3), ca_c = load3<double>(X + 9 * a + 6), nb = load3<double>(X + 9 * a + 9), cab = load3<double>(X + 9 * a + 12);
         D3& gCAa = gCA; D3& gCa = gC;                         // a-side shares (kept when mine)
         D3& gNb = gN; D3& gCAb = gCA;                         // b-side shares (kept otherwise)
         D3 dv = ca_c - nb;
@@ -295,35 +249,28 @@ __device__ void evaluate(const double* X, double* G, double* CB, double* red, in
         else { axpy(gNb, cpep * res, d2); axpy(gCAb, cpep * res, d3); }
       }
     }
-#pragma unroll
-    for (int off = REFINE_LANES / 2; off > 0; off >>= 1) {
-      gN.x += __shfl_xor(gN.x, off, 64); gN.y += __shfl_xor(gN.y, off, 64); gN.z += __shfl_xor(gN.z, off, 64);
-      gCA.x += __shfl_xor(gCA.x, off, 64); gCA.y += __shfl_xor(gCA.y, off, 64); gCA.z += __shfl_xor(gCA.z, off, 64);
-      gC.x += __shfl_xor(gC.x, off, 64); gC.y += __shfl_xor(gC.y, off, 64); gC.z += __shfl_xor(gC.z, off, 64);
-      gCB.x += __shfl_xor(gCB.x, off, 64); gCB.y += __shfl_xor(gCB.y, off, 64); gCB.z += __shfl_xor(gCB.z, off, 64);
-    }
+    lanes_sum<REFINE_LANES>(gN.x, gN.y, gN.z, gCA.x, gCA.y, gCA.z, gC.x, gC.y, gC.z, gCB.x, gCB.y, gCB.z);
     if (i < n && sub == 0) {                                  // through the virtual Cb: Cb = CA + K1 (b x c) + K2 b + K3 c
-      const D3 nn = ld3(X + 9 * i), ca = ld3(X + 9 * i + 3), cc = ld3(X + 9 * i + 6);
+      const D3 nn = load3<double>(X + 9 * i), ca = load3<double>(X + 9 * i + 3), cc = load3<double>(X + 9 * i + 6);
       const D3 bv = ca - nn, cv = cc - ca;
       const D3 gb = K1 * cross(cv, gCB) + K2 * gCB, gc = K1 * cross(gCB, bv) + K3 * gCB;
-      st3(G + 9 * i, gN - gb); st3(G + 9 * i + 3, (gCA + gCB) + (gb - gc)); st3(G + 9 * i + 6, gC + gc);
+      store3(G + 9 * i, gN - gb); store3(G + 9 * i + 3, (gCA + gCB) + (gb - gc)); store3(G + 9 * i + 6, gC + gc);
     }
   }
-  block_sum<8>(terms, red);
+  block_sum<8, REFINE_WAVES>(terms, red);
 }
 __device__ __forceinline__ double total_energy(const double (&t)[8], const Stage& st) {
   return st.w_dist * t[0] + st.w_ang * (t[1] + t[2] + t[3]) + t[4] + t[5] + t[6] + st.w_rep * t[7];
 }
 
-struct RefineWorkspace {          // byte offsets into the caller's workspace, every part 256-byte aligned
+struct RefineWorkspace {          // byte offsets into the caller's workspace (WorkspaceCarve)
   size_t offsets, entries, history, total;
   RefineWorkspace(int B, int L) {
-    size_t o = 0;
-    auto take = [&o](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
-    offsets = take((size_t)B * (L + 1) * 4);
-    entries = take((size_t)B * L * (L > 1 ? L - 1 : 1) * sizeof(Entry));
-    history = take((size_t)B * 2 * REFINE_HISTORY * 9 * L * 8);
-    total = o;
+    WorkspaceCarve w;
+    offsets = w.take((size_t)B * (L + 1) * 4);
+    entries = w.take((size_t)B * L * (L > 1 ? L - 1 : 1) * sizeof(Entry));
+    history = w.take((size_t)B * 2 * REFINE_HISTORY * 9 * L * 8);
+    total = w.total;
   }
 };
 __host__ __device__ constexpr int refine_lds_bytes(int L) { return (5 * 9 * L + 3 * L + REFINE_WAVES * 8 + REFINE_HISTORY) * 8; }
@@ -336,7 +283,7 @@ __device__ __forceinline__ double load_chain(const float* in, double* X, int n, 
     if (!isfinite(v)) bad[0] += 1.0;
     X[e] = (double)v;
   }
-  block_sum<1>(bad, red);
+  block_sum<1, REFINE_WAVES>(bad, red);
   return bad[0];
 }
 
@@ -430,8 +377,8 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_kernel(const float* __r
     for (int it = 0; it < st.max_iter; ++it) {
       double gg[1] = {0.0}, gmax = 0.0;
       for (int e = t; e < nv; e += REFINE_THREADS) { gg[0] += G[e] * G[e]; gmax = fmax(gmax, fabs(G[e])); }
-      gmax = block_max(gmax, red);
-      block_sum<1>(gg, red);
+      gmax = block_max<REFINE_WAVES>(gmax, red);
+      block_sum<1, REFINE_WAVES>(gg, red);
       if (!(gmax >= GRAD_TOL)) break;
       bool steepest = m == 0;
       double gd = 0.0;
@@ -444,7 +391,7 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_kernel(const float* __r
             const int idx = (head - 1 - k + 2 * REFINE_HISTORY) % REFINE_HISTORY;
             double sq[1] = {0.0};
             for (int e = t; e < nv; e += REFINE_THREADS) sq[0] += S[idx * slot + e] * D[e];
-            block_sum<1>(sq, red);
+            block_sum<1, REFINE_WAVES>(sq, red);
             alpha[k] = rho[idx] * sq[0];
             for (int e = t; e < nv; e += REFINE_THREADS) D[e] -= alpha[k] * Y[idx * slot + e];
           }
@@ -456,14 +403,14 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_kernel(const float* __r
             const int idx = (head - 1 - k + 2 * REFINE_HISTORY) % REFINE_HISTORY;
             double yq[1] = {0.0};
             for (int e = t; e < nv; e += REFINE_THREADS) yq[0] += Y[idx * slot + e] * D[e];
-            block_sum<1>(yq, red);
+            block_sum<1, REFINE_WAVES>(yq, red);
             const double c = alpha[k] - rho[idx] * yq[0];
             for (int e = t; e < nv; e += REFINE_THREADS) D[e] += c * S[idx * slot + e];
           }
         }
         double dd[1] = {0.0};
         for (int e = t; e < nv; e += REFINE_THREADS) { D[e] = -D[e]; dd[0] += G[e] * D[e]; }
-        block_sum<1>(dd, red);
+        block_sum<1, REFINE_WAVES>(dd, red);
         gd = dd[0];
         if (!(gd < 0.0)) { steepest = true; m = 0; }
       }
@@ -495,7 +442,7 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_kernel(const float* __r
         const double s = XT[e] - X[e], y = GT[e] - G[e];
         d3[0] += s * y; d3[1] += s * s; d3[2] += y * y;
       }
-      block_sum<3>(d3, red);
+      block_sum<3, REFINE_WAVES>(d3, red);
       const bool keep = d3[0] > CURVATURE_EPS * sqrt(d3[1]) * sqrt(d3[2]);      // else the slot keeps the oldest pair
       for (int e = t; e < nv; e += REFINE_THREADS) {
         if (keep) { S[head * slot + e] = XT[e] - X[e]; Y[head * slot + e] = GT[e] - G[e]; }
@@ -517,19 +464,19 @@ __global__ __launch_bounds__(REFINE_THREADS) void refine_kernel(const float* __r
   ++evals;
   double gmax = 0.0, cl[1] = {0.0};
   for (int e = t; e < nv; e += REFINE_THREADS) gmax = fmax(gmax, fabs(G[e]));
-  gmax = block_max(gmax, red);
+  gmax = block_max<REFINE_WAVES>(gmax, red);
   for (int i = t; i + 1 < n; i += REFINE_THREADS) {
-    const D3 dv = ld3(X + 9 * i + 6) - ld3(X + 9 * i + 9);
+    const D3 dv = load3<double>(X + 9 * i + 6) - load3<double>(X + 9 * i + 9);
     cl[0] += fabs(sqrt(dot(dv, dv)) - BOND_C_N);
   }
-  block_sum<1>(cl, red);
+  block_sum<1, REFINE_WAVES>(cl, red);
   double broken[1] = {0.0};
   for (int e = t; e < 9 * L; e += REFINE_THREADS) {
     float v = e < nv ? (float)X[e] : 0.f;
     if (!isfinite(v)) { v = 0.f; broken[0] += 1.0; }
     out[e] = v;
   }
-  block_sum<1>(broken, red);
+  block_sum<1, REFINE_WAVES>(broken, red);
   if (t == 0) {
     status[b] = st_bits | (broken[0] != 0.0 ? 1 : 0);
     dg[0] = finite_or_zero(e_start);

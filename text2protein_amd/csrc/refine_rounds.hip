@@ -22,6 +22,7 @@
 // replaces the incumbent when strictly lower).  The incumbent lives in the caller's xyz_out / status / diag.
 #include <cmath>
 
+#include "backbone_geom.h"
 #include "philox.h"
 #include "t2p_common.h"
 #include "t2p_kernels.h"
@@ -30,25 +31,7 @@ namespace t2p {
 namespace {
 
 constexpr int PERTURB_THREADS = 256;
-constexpr double GUARD = 1e-12;          // refine.hip's floor of every denominator
-constexpr double DEG = 0.017453292519943295;
-
-struct D3 { double x, y, z; };
-__device__ __forceinline__ D3 operator+(D3 a, D3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ D3 operator-(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ D3 operator*(double s, D3 a) { return {s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ double dot(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ D3 cross(D3 a, D3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ D3 ld3f(const float* p) { return {(double)p[0], (double)p[1], (double)p[2]}; }
-
-// the value of refine.hip's dihedral_grad
-__device__ __forceinline__ double dihedral(D3 p0, D3 p1, D3 p2, D3 p3) {
-  const D3 f = p0 - p1, g = p1 - p2, h = p3 - p2;
-  const D3 a = cross(f, g), b = cross(h, g);
-  const double gl = sqrt(fmax(dot(g, g), GUARD));
-  const double y = dot(cross(b, a), g) / gl, x = dot(a, b);
-  return (x == 0.0 && y == 0.0) ? 0.0 : atan2(y, x);
-}
+using namespace geom;        // D3, GUARD, DEG, angle, dihedral_guarded: the minimiser's own definitions (backbone_geom.h)
 
 __device__ __forceinline__ D3 place(D3 a, D3 b, D3 c, double bond, double cs_theta, double sn_theta, double tau) {
   D3 bc = c - b;
@@ -106,13 +89,12 @@ __global__ __launch_bounds__(PERTURB_THREADS) void perturb_kernel(const float* _
   }
   const int na = 3 * n;
   for (int k = 3 + t; k < na; k += PERTURB_THREADS) {
-    const D3 p0 = ld3f(in + 3 * (k - 3)), p1 = ld3f(in + 3 * (k - 2)), p2 = ld3f(in + 3 * (k - 1)), p3 = ld3f(in + 3 * k);
-    const D3 v = p1 - p2, w = p3 - p2, cr = cross(v, w);
-    const double sn = sqrt(dot(cr, cr)), cs = dot(v, w);
-    const double theta = (sn == 0.0 && cs == 0.0) ? 0.0 : atan2(sn, cs);
+    const D3 p0 = load3<double>(in + 3 * (k - 3)), p1 = load3<double>(in + 3 * (k - 2)), p2 = load3<double>(in + 3 * (k - 1)), p3 = load3<double>(in + 3 * k);
+    const double theta = angle(p1, p2, p3);
+    const D3 w = p3 - p2;
     bond[k] = sqrt(dot(w, w));
     sincos(theta, &sth[k], &cth[k]);
-    tau[k] = dihedral(p0, p1, p2, p3);
+    tau[k] = dihedral_guarded(p0, p1, p2, p3);
   }
   // the tail past the chain, the first three atoms, and candidate 0 when it is the input itself
   for (long e = t; e < (long)K * L * 9; e += PERTURB_THREADS) {
@@ -130,7 +112,7 @@ __global__ __launch_bounds__(PERTURB_THREADS) void perturb_kernel(const float* _
   const unsigned long long st_k = stream + (unsigned long long)t;
   const long id_hi = (long)((unsigned long long)(uint32_t)(chain_ids ? chain_ids[b] : b) << 32);
   float* o = out + (long)t * L * 9;
-  D3 a = ld3f(in), bb = ld3f(in + 3), c = ld3f(in + 6);
+  D3 a = load3<double>(in), bb = load3<double>(in + 3), c = load3<double>(in + 6);
   uint32_t w[4];
   philox_counter_training(w, id_hi, st_k);                      // residue 0: its psi moves N_1
   philox4x32_10(w, seed);
@@ -194,24 +176,23 @@ __global__ __launch_bounds__(64) void select_kernel(const float* __restrict__ ca
   }
 }
 
-struct RoundsWorkspace {          // byte offsets into the caller's workspace, every part 256-byte aligned
+struct RoundsWorkspace {          // byte offsets into the caller's workspace (WorkspaceCarve)
   size_t moved, refined, move_status, cand_lengths, cand_status, cand_diag, esel, e_inc, refine, total;
   long refine_bytes;
   RoundsWorkspace(int B, int L, int K) {
-    size_t o = 0;
-    auto take = [&o](size_t bytes) { const size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
+    WorkspaceCarve w;
     const size_t C = (size_t)B * K;
-    moved = take(C * L * 9 * 4);
-    refined = take(C * L * 9 * 4);
-    move_status = take(C * 4);
-    cand_lengths = take(C * 4);
-    cand_status = take(C * 4);
-    cand_diag = take(C * 16 * 8);
-    esel = take(C * 9 * 8);
-    e_inc = take((size_t)B * 8);
+    moved = w.take(C * L * 9 * 4);
+    refined = w.take(C * L * 9 * 4);
+    move_status = w.take(C * 4);
+    cand_lengths = w.take(C * 4);
+    cand_status = w.take(C * 4);
+    cand_diag = w.take(C * 16 * 8);
+    esel = w.take(C * 9 * 8);
+    e_inc = w.take((size_t)B * 8);
     refine_bytes = refine_workspace_bytes((int)C, L);
-    refine = take((size_t)refine_bytes);
-    total = o;
+    refine = w.take((size_t)refine_bytes);
+    total = w.total;
   }
 };
 

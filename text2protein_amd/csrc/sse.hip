@@ -12,6 +12,7 @@
 //   runs      the thread of a letter run's first residue counts it when it holds at least 4 residues (encode.sse_blocks' blocks)
 // Only integers are counted and only integer LDS atomics add them, so two calls give the same bits; tests/sse_oracle.py is the same
 // text in numpy and the GPU test asks for equality.
+#include "backbone_geom.h"
 #include "t2p_common.h"
 #include "t2p_kernels.h"
 
@@ -20,7 +21,6 @@ namespace {
 
 constexpr int SSE_THREADS = 256;
 constexpr double SSE_MAX_COORD = 1.0e6;
-constexpr double SSE_DEG = 57.29577951308232;            // 180 / pi
 enum : unsigned char { SSE_PH = 1, SSE_PS = 2, SSE_HEXT = 4, SSE_SEXT = 8 };
 
 __device__ inline bool within(double v, double lo, double hi) { return v >= lo && v <= hi; }      // false for NaN
@@ -82,14 +82,14 @@ __global__ __launch_bounds__(SSE_THREADS) void annotate_sse_kernel(const float* 
         const double ux = ax - px[i], uy = ay - py[i], uz = az - pz[i];
         const double vx = px[i + 1] - px[i], vy = py[i + 1] - py[i], vz = pz[i + 1] - pz[i];
         const double c = (ux * vx + uy * vy + uz * vz) / (sqrt(ux * ux + uy * uy + uz * uz) * sqrt(vx * vx + vy * vy + vz * vz));
-        if (c == c) r = acos(fmin(1.0, fmax(-1.0, c))) * SSE_DEG;                 // coincident CAs: 0 / 0, r stays undefined
+        if (c == c) r = acos(fmin(1.0, fmax(-1.0, c))) * geom::RAD;                 // coincident CAs: 0 / 0, r stays undefined
         if (p2) {
           const double b0x = -ux, b0y = -uy, b0z = -uz, b1x = vx, b1y = vy, b1z = vz;
           const double b2x = px[i + 2] - px[i + 1], b2y = py[i + 2] - py[i + 1], b2z = pz[i + 2] - pz[i + 1];
           const double n1x = b0y * b1z - b0z * b1y, n1y = b0z * b1x - b0x * b1z, n1z = b0x * b1y - b0y * b1x;
           const double n2x = b1y * b2z - b1z * b2y, n2y = b1z * b2x - b1x * b2z, n2z = b1x * b2y - b1y * b2x;
           const double mx = n1y * n2z - n1z * n2y, my = n1z * n2x - n1x * n2z, mz = n1x * n2y - n1y * n2x;
-          a = atan2((mx * b1x + my * b1y + mz * b1z) / sqrt(b1x * b1x + b1y * b1y + b1z * b1z), n1x * n2x + n1y * n2y + n1z * n2z) * SSE_DEG;
+          a = atan2((mx * b1x + my * b1y + mz * b1z) / sqrt(b1x * b1x + b1y * b1y + b1z * b1z), n1x * n2x + n1y * n2y + n1z * n2z) * geom::RAD;
         }
       }
     }

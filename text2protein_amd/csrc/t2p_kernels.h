@@ -274,6 +274,15 @@ int launch_decode6d(const float* x, int B, int C, int L, float* clipped, float* 
 int launch_encode6d(const float* xyz, const int* nres, const unsigned char* atom_ok, int B, int C, int L, const int* blocks, const int* pairs,
                     int npairs, float* coords_6d, unsigned char* mask_pair, hipStream_t s);
 int launch_embedding_gather(const void* table, int dtype, const int* ids, float* out, long ntok, int dim, int vocab, int* bad, hipStream_t s);
+// Byte offsets into a caller's workspace, every part 256-byte aligned (FoldWorkspace, RefineWorkspace, RoundsWorkspace).
+struct WorkspaceCarve {
+  size_t total = 0;
+  size_t take(size_t bytes) {
+    const size_t at = total;
+    total += (bytes + 255) / 256 * 256;
+    return at;
+  }
+};
 // ---- after the decode: backbones from the maps (fold.hip) ----
 // absval / lengths as launch_decode6d writes them -> xyz [B][L][3][3] (N, CA, C), status [B] (0 ok, 1 degraded, -1 improper mask),
 // placed [B][L] (1 = residue without a frame of its own), diag [B][16] double.  The geodesic matrix of a chain stays in LDS up to

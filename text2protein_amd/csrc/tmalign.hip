@@ -27,6 +27,7 @@
 // Double throughout; the float32 inputs are widened on load (they are kept as float32 in LDS, which loses nothing).
 #include "t2p_common.h"
 #include "t2p_kernels.h"
+#include "wave_reduce.h"
 
 namespace t2p {
 namespace {
@@ -61,11 +62,6 @@ struct TmLayout {                               // byte offsets into the dynamic
 
 int tm_waves(int La) { return La <= 192 ? 4 : 3; }        // 64 KB of LDS without opting in: DESIGN.md 8g has the figures
 
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 __device__ __forceinline__ int bcount(bool b) { return __popcll(__ballot(b)); }
 __device__ __forceinline__ double pick3(int i, double a0, double a1, double a2) { return i == 0 ? a0 : (i == 1 ? a1 : a2); }
 __device__ __forceinline__ void wave_fence() {
@@ -329,7 +325,7 @@ __device__ __forceinline__ void fit(const Pairs& P, unsigned sel, double (&t)[3]
     }
   }
 #pragma unroll
-  for (int k = 0; k < 15; ++k) s[k] = wsum(s[k]);
+  for (int k = 0; k < 15; ++k) s[k] = wave_sum(s[k]);
   kabsch_core(n, s, t, u);
 }
 
@@ -343,7 +339,7 @@ __device__ __forceinline__ double distances(const Pairs& P, const double (&t)[3]
     di[r] = dist2(xr, P.y[r]);
     if (((P.valid >> r) & 1u) && (cut < 0.0 || di[r] <= cut)) sum += 1.0 / (1.0 + di[r] / d02);
   }
-  return wsum(sum);
+  return wave_sum(sum);
 }
 
 // get_score_fast (TMalign.cpp:2194)
@@ -969,7 +965,7 @@ __global__ __launch_bounds__(256) void tm_align_kernel(const float* __restrict__
       rot(tz, uz, P.x[r], xt);
       if ((P.valid >> r) & 1u) e += dist2(xt, P.y[r]);
     }
-    e = wsum(e);
+    e = wave_sum(e);
     rmsd0 = n_ali8 > 0 ? sqrt(e / n_ali8) : 0.0;
   }
   // parameter_set4final (TMalign.cpp:1687) for len_b (TM-align's TM1, whose superposition it prints) and for len_a (TM2)

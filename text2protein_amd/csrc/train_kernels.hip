@@ -19,6 +19,7 @@
 
 #include "philox.h"
 #include "train_kernels.h"
+#include "wave_reduce.h"
 
 namespace t2p {
 
@@ -502,18 +503,8 @@ int launch_tgemm16(const TGemmArgs& a, int dtype, float* ws, hipStream_t s) {
 }
 
 // =====================================================================================================================================
-// reductions shared below
+// reductions shared below: wave_sum comes from wave_reduce.h
 // =====================================================================================================================================
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ inline double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 __device__ inline float sigmoidf_(float v) { return 1.f / (1.f + __expf(-v)); }
 
 // =====================================================================================================================================
@@ -1053,6 +1044,8 @@ int launch_conv_w_grad_fold(const float* dwc, float* gw, int Co, int Ci, int Cip
 // =====================================================================================================================================
 // denoising score matching (VE, VP and sub-VP SDEs)
 // =====================================================================================================================================
+// Not wave_reduce.h's block_sum<1, 4>: these add sh[0] + sh[1] + sh[2] + sh[3] without a leading zero (the sign of a -0 total differs)
+// and put their second barrier after the read, so `sh` may be reused at once.
 __device__ inline float block_sum_256(float v, float* sh) {
   v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
@@ -1062,7 +1055,7 @@ __device__ inline float block_sum_256(float v, float* sh) {
   return r;
 }
 __device__ inline double block_sum_256_d(double v, double* sh) {
-  v = wave_sum_d(v);
+  v = wave_sum(v);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
   __syncthreads();
   const double r = sh[0] + sh[1] + sh[2] + sh[3];
