@@ -201,6 +201,18 @@ gemm.hip:3:1: remark:     ScratchSize [bytes/lane]: 16 [-Rpass-analysis=kernel-r
     assert scratch_users(remarks, "gemm_dma_kernel") == [("_ZN3t2p15gemm_dma_kernelIaEEv", 544)]
 
 
+def test_build_hashes_every_source_and_header():
+    """Every file of csrc/ is in build.SOURCES or build.HEADERS and every listed file exists: a file left out of source_hash
+    lets a stale library load."""
+    from text2protein_amd import build
+    listed = build.SOURCES + build.HEADERS
+    assert len(set(listed)) == len(listed)
+    for f in listed:
+        assert os.path.isfile(os.path.join(build.CSRC, f)), f
+    on_disk = {f for f in os.listdir(build.CSRC) if f.endswith((".hip", ".cpp", ".h"))}
+    assert on_disk and on_disk <= set(listed), sorted(on_disk - set(listed))
+
+
 def test_oracle_stands_on_its_own_topology():
     """The oracle derives the module sequence from the config itself (no import of the product package) and agrees with the
     product's arch table -- and so, through param_tables.json, with the reference's named_parameters() -- on every shipped YAML."""

@@ -11,10 +11,11 @@ import sys
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libt2p_hip.so")
 LIB_ABLATION = os.path.join(CSRC, "libt2p_hip_ablation.so")   # measurement builds only (tools/bench_conv.py --ablation)
-SOURCES = ["gemm.hip", "rowgemm.hip", "kernels.hip", "attention.hip", "smallconv.hip", "stfuse.hip", "ddim.hip", "fold.hip", "refine.hip", "refine_rounds.hip", "tmalign.hip", "sse.hip", "weightpack.hip", "engine.cpp", "sampler.cpp", "capi.cpp",
+SOURCES = ["gemm_dma.hip", "gemm.hip", "gemm_splitk.hip", "thin_conv.hip", "launch_prof.cpp", "rowgemm.hip", "kernels.hip", "attention.hip", "smallconv.hip", "stfuse.hip", "ddim.hip", "fold.hip", "refine.hip", "refine_rounds.hip", "tmalign.hip", "sse.hip", "weightpack.hip", "engine.cpp", "sampler.cpp", "capi.cpp",
            "train_kernels.hip", "train.cpp", "train_capi.cpp"]
-GEMM_PARTS = 7          # gemm.hip is compiled once per -DT2P_GEMM_PART=k: the LDS-DMA instantiations build in parallel
-HEADERS = ["t2p_common.h", "plan.h", "t2p_kernels.h", "gemm_mfma.h", "philox.h", "update_loop.h", "engine.h", "sampler.h", "ddim.h", "train_kernels.h", "train.h", "wave_reduce.h", "backbone_geom.h", os.path.join("..", "..", "include", "t2p.h")]
+DMA_INSTS = 6           # gemm_dma.hip is compiled once per -DT2P_DMA_INST=k: the launch_dma_mode<dtype, MODE> instantiations build in parallel
+SCRATCH_CHECKED = ("gemm_dma.hip", "gemm.hip", "gemm_splitk.hip", "thin_conv.hip")   # their kernels must not use scratch memory (scratch_users)
+HEADERS = ["t2p_common.h", "plan.h", "t2p_kernels.h", "gemm_mfma.h", "gemm_device.h", "launch_prof.h", "philox.h", "update_loop.h", "engine.h", "sampler.h", "ddim.h", "train_kernels.h", "train.h", "wave_reduce.h", "backbone_geom.h", os.path.join("..", "..", "include", "t2p.h")]
 ARCH = "gfx950"
 
 
@@ -73,6 +74,19 @@ def unit_hash(src: str, flags) -> str:
         for inc in re.findall(rb'^\s*#\s*include\s+"([^"]+)"', data, re.M):
             todo.append(os.path.join(os.path.dirname(f), inc.decode()))
     return h.hexdigest()
+
+
+def units():
+    """(source, object stem, extra flags) of every object file; the LDS-DMA units, the longest to compile, come first."""
+    out = []
+    for src in SOURCES:
+        stem = os.path.splitext(src)[0]
+        check = ["-Rpass-analysis=kernel-resource-usage"] if src in SCRATCH_CHECKED else []
+        if src == "gemm_dma.hip":
+            out += [(src, f"{stem}_inst{k}", check + [f"-DT2P_DMA_INST={k}"]) for k in range(DMA_INSTS)]
+        else:
+            out.append((src, stem, check))
+    return out
 
 
 def _read(path) -> str:
@@ -139,14 +153,10 @@ def _build_locked(lib: str, stamp: str, verbose: bool, ablation: bool) -> str:
     flags = FLAGS + (["-DT2P_ABLATION"] if ablation else [])
     if os.path.exists(stamp):
         os.remove(stamp)
-    units = [(src, None) for src in SOURCES if src != "gemm.hip"] + [("gemm.hip", k) for k in range(GEMM_PARTS)]
-    for src, part in sorted(units, key=lambda u: u[1] is None):       # the long gemm.hip units first
-        stem = os.path.splitext(src)[0] + ("" if part is None else f"_part{part}") + ("_abl" if ablation else "")
-        obj = os.path.join(CSRC, stem + ".o")
+    for src, stem, extra in units():
+        obj = os.path.join(CSRC, stem + ("_abl" if ablation else "") + ".o")
         objs.append(obj)
-        cmd = [hipcc, *flags, "-x", "hip", "-c", os.path.join(CSRC, src), "-o", obj]
-        if part is not None:
-            cmd[1:1] = ["-Rpass-analysis=kernel-resource-usage", f"-DT2P_GEMM_PART={part}"]
+        cmd = [hipcc, *extra, *flags, "-x", "hip", "-c", os.path.join(CSRC, src), "-o", obj]
         uh = unit_hash(src, cmd[1:-4])
         if os.path.exists(obj) and _read(obj + ".hash") == uh:
             continue
@@ -160,7 +170,7 @@ def _build_locked(lib: str, stamp: str, verbose: bool, ablation: bool) -> str:
         out, _ = p.communicate()
         if p.returncode != 0:
             raise RuntimeError(f"hipcc failed on {src}:\n{out}")
-        if src == "gemm.hip":
+        if src in SCRATCH_CHECKED:
             bad = scratch_users(out)
             if bad:
                 raise RuntimeError("LDS-DMA GEMM kernels spill to scratch memory (accumulator loop left rolled?): "

@@ -21,6 +21,7 @@
 // (keys) x 16 columns (d) is delivered column-major, i.e. lane (d) receives its 4 keys -- exactly the fragment's halves.
 // Lane 4 q + p of a group supplies the address of key row q, columns 4 p .. 4 p + 3; rows are VRS bytes apart, an
 // odd multiple of 16 dwords, which puts the four key rows of a block into four different 16-bank windows: conflict-free.
+#include "launch_prof.h"
 #include "t2p_kernels.h"
 
 namespace t2p {
@@ -268,17 +269,13 @@ static int launch_flash_t(const FlashArgs& a, int B, int heads, hipStream_t s) {
   auto kern = attn_flash_kernel<TC, D, VROW>;
   T2P_TRY(ensure_dynamic_lds((const void*)kern, smem));
   dim3 grid((a.nq + 127) / 128, heads, B);
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (prof_on()) {                     // bench.py roofline leg: HIP events on the launch stream
-    T2P_HIP_CHECK(hipEventCreate(&e0));
-    T2P_HIP_CHECK(hipEventCreate(&e1));
-    T2P_HIP_CHECK(hipEventRecord(e0, s));
-  }
+  ProfScope prof;                      // bench.py roofline leg: HIP events on the launch stream
+  prof.rec.kind = 3;
+  prof.rec.flops = 4.0 * (double)a.nq * a.nk * D * heads * B;      // q k^T and p v
+  T2P_TRY(prof.open(s));
   hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, a);
-  if (e0) {
-    T2P_HIP_CHECK(hipEventRecord(e1, s));
-    prof_attention(e0, e1, 4.0 * (double)a.nq * a.nk * D * heads * B);      // q k^T and p v
-  }
+  T2P_TRY(prof.close());
+  prof.commit();
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }
@@ -618,17 +615,13 @@ static int launch_strip_t(const StripArgs& a, int B, hipStream_t s) {
   static_assert(smem <= 160 * 1024, "attn_strip: LDS budget");
   auto kern = attn_strip_kernel<TC, D, NKT, FM>;
   T2P_TRY(ensure_dynamic_lds((const void*)kern, smem));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (prof_on()) {
-    T2P_HIP_CHECK(hipEventCreate(&e0));
-    T2P_HIP_CHECK(hipEventCreate(&e1));
-    T2P_HIP_CHECK(hipEventRecord(e0, s));
-  }
+  ProfScope prof;
+  prof.rec.kind = 3;
+  prof.rec.flops = 4.0 * (double)a.n * a.n * D * B;
+  T2P_TRY(prof.open(s));
   hipLaunchKernelGGL(kern, dim3((a.n + 63) / 64, B), dim3(512), smem, s, a);
-  if (e0) {
-    T2P_HIP_CHECK(hipEventRecord(e1, s));
-    prof_attention(e0, e1, 4.0 * (double)a.n * a.n * D * B);
-  }
+  T2P_TRY(prof.close());
+  prof.commit();
   T2P_HIP_CHECK(hipGetLastError());
   return T2P_OK;
 }

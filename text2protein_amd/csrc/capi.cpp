@@ -3,6 +3,7 @@
 
 #include "ddim.h"
 #include "engine.h"
+#include "launch_prof.h"
 #include "sampler.h"
 
 using namespace t2p;

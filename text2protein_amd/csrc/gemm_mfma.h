@@ -1,4 +1,4 @@
-// Device helpers shared by the 16x16x32 MFMA kernels (gemm.hip, rowgemm.hip): fragment types, the MFMA wrapper, buffer
+// Device helpers shared by the 16x16x32 MFMA kernels (gemm_dma.hip, thin_conv.hip, rowgemm.hip): fragment types, the MFMA wrapper, buffer
 // descriptors, the channel permutation of a wave's 64-column block and the arithmetic of the register epilogue.
 #pragma once
 #include "t2p_common.h"
@@ -69,7 +69,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, in
 }
 
 // The 16x16x32 kernels feed the WEIGHT fragment as the MFMA's first operand and permute the weight rows of a wave's 64-column
-// block (see reg_epilogue in gemm.hip): row rho (0..63) of the block as the MFMA sees it -> channel of the block
+// block (see reg_epilogue in gemm_dma.hip): row rho (0..63) of the block as the MFMA sees it -> channel of the block
 __host__ __device__ __forceinline__ int hperm(int rho) {
   const int j = rho >> 4, g = (rho >> 2) & 3, v = rho & 3;
   return 32 * (j >> 1) + 8 * g + 4 * (j & 1) + v;

@@ -6,7 +6,7 @@
 namespace t2p {
 
 struct Plan {
-  // ---- GEMM / implicit-GEMM convolution (gemm.hip, rowgemm.hip) ----
+  // ---- GEMM / implicit-GEMM convolution (gemm.hip, gemm_dma.hip, rowgemm.hip) ----
   bool dma = true;             // 0: 16-bit products on the LDS-DMA kernels where eligible (else the register-staged kernel)
   int dbg = 0;                 // 1: mask of the LDS-DMA kernels: 128 / 256 DMA issue order, 4096 LDS-staged instead of register epilogue, 8192 general
                                //    instead of specialised register epilogue (same results); timing-only ablations of the -DT2P_ABLATION build (results

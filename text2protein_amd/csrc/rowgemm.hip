@@ -1,12 +1,12 @@
 // Row-resident GEMM for the K = 512 projections of the SpatialTransformer (gfx950): C = alpha (A W^T + bias_n + R), or the fused
 // GEGLU form, with 16-bit A, W and C.
 //
-// The 256 x 256 LDS-DMA kernel (gemm.hip) has 8 K-tiles at K = 512: set-up, the first stage and the epilogue are half of a tile's
+// The 256 x 256 LDS-DMA kernel (gemm_dma.hip) has 8 K-tiles at K = 512: set-up, the first stage and the epilogue are half of a tile's
 // time, one workgroup owns the CU, and a barrier in every K-tile keeps its waves in step, so nothing hides them.  Here
 //   * a workgroup of 8 wavefronts owns 128 rows and brings all 128 x 512 activations into LDS once (128 KiB, LDS-DMA, the K-tile
 //     image and chunk swizzle of gemm_dma_body); LDS holds nothing else;
 //   * wavefront w owns the 64-column slices w, w + 8, ... over all 128 rows (the 128 x 64 wave tile, 128 accumulator registers, of
-//     the 16x16x32 loop in gemm.hip) and streams its own weight fragments L2 -> registers, two K-tiles ahead, from a
+//     the 16x16x32 loop in gemm_dma.hip) and streams its own weight fragments L2 -> registers, two K-tiles ahead, from a
 //     fragment-major copy of the weights (rowres_pack_kernel, weightpack.hip: the four fragments of a 32-deep step are 4 KiB
 //     contiguous);
 //   * only a wave's first slice synchronises, once per K-tile, so that its MFMAs start while later K-tiles of A are still

@@ -183,15 +183,7 @@ bool gemm_fuses_col_stats_lowp(const GemmParams& p);
 bool gemm_fuses_post_gn(const GemmParams& p, int groups);   // p without gn_*: would launch_gemm apply a following GroupNorm of `groups` groups?
 bool gemm_applies_a_norm(const GemmParams& p);      // p without an_*: would launch_gemm normalise A0 on the fly (head convolution)?
 #ifdef T2P_ABLATION
-int dxs_stamps_read(unsigned long long* out, int n);   // measurement builds: in-kernel timeline of gemm_dxs_kernel (gemm.hip)
+int dxs_stamps_read(unsigned long long* out, int n);   // measurement builds: in-kernel timeline of gemm_dxs_kernel (gemm_dma.hip)
 #endif
-void profile_begin();
-int profile_end(double out[3][3]);
-int profile_dominant(double out[4], const char** name);
-int profile_shapes(char* buf, int len);
-int profile_conv_kernels(char* buf, int len);
-bool prof_on();
-void prof_attention(hipEvent_t a, hipEvent_t b, double flops);
-int profile_attention(double out[3]);
 
 }  // namespace t2p

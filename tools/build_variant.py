@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Build a measurement variant of the library with extra -D flags (in-call A/B against the shipped build: bench.py --lib).
     python tools/build_variant.py nt -DT2P_C_AUX=2        ->  variants/libt2p_nt.so
-Only the units named with --units (default: the gemm.hip parts) are recompiled with the flags; the other objects are the
-shipped ones.  The output is git-ignored (*.so) and travels to the GPU box with the snapshot."""
+Only the sources named with --units (default: the files that hold the GEMM kernels -- gemm_dma.hip, every instantiation of it,
+gemm.hip, gemm_splitk.hip and thin_conv.hip) are recompiled with the flags; the other objects are the shipped ones.  The output is git-ignored (*.so) and travels to the GPU box with the snapshot."""
 import os
 import subprocess
 import sys
@@ -15,26 +15,21 @@ def main():
     name = sys.argv[1]
     defs = [a for a in sys.argv[2:] if a.startswith("-D")]
     units = [a.split("=", 1)[1].split(",") for a in sys.argv[2:] if a.startswith("--units=")]
-    units = units[0] if units else ["gemm.hip"]
+    units = units[0] if units else ["gemm_dma.hip", "gemm.hip", "gemm_splitk.hip", "thin_conv.hip"]
     B.build(verbose=False)
     out_dir = os.path.join(os.path.dirname(B.CSRC), "..", "variants")
     out_dir = os.path.abspath(out_dir)
     os.makedirs(out_dir, exist_ok=True)
     hipcc = B._hipcc()
     objs, procs = [], []
-    for src in B.SOURCES:
-        parts = list(range(B.GEMM_PARTS)) if src == "gemm.hip" else [None]
-        for part in parts:
-            stem = os.path.splitext(src)[0] + ("" if part is None else f"_part{part}")
-            if src not in units:
-                objs.append(os.path.join(B.CSRC, stem + ".o"))
-                continue
-            obj = os.path.join(out_dir, f"{name}_{stem}.o")
-            objs.append(obj)
-            cmd = [hipcc, *B.FLAGS, *defs, "-x", "hip", "-c", os.path.join(B.CSRC, src), "-o", obj]
-            if part is not None:
-                cmd[1:1] = [f"-DT2P_GEMM_PART={part}"]
-            procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
+    for src, stem, extra in B.units():
+        if src not in units:
+            objs.append(os.path.join(B.CSRC, stem + ".o"))
+            continue
+        obj = os.path.join(out_dir, f"{name}_{stem}.o")
+        objs.append(obj)
+        cmd = [hipcc, *[f for f in extra if f.startswith("-D")], *B.FLAGS, *defs, "-x", "hip", "-c", os.path.join(B.CSRC, src), "-o", obj]
+        procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
     for cmd, p in procs:
         out, _ = p.communicate()
         if p.returncode != 0:
